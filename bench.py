@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Tramba hot-path benchmark on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself: the parent
@@ -11,10 +11,16 @@ exits with its code.
 One "step" = one forward of Tramba-V (VMamba-B encoder + Dual-Frequency/Helix decoder) over one synthetic batch already
 resident in HBM (BASELINE.json configs[1]: 384x384, bf16, batch 4 per GPU).  Inference shards by image: every rank runs
 an independent replica on its own batch, no data-path collective ("weak" scaling); the barrier only brackets the timed
-region.  `value` = images/s of that forward, whole job.
+region.  `value` = images/s of that forward, whole job; `ms_per_step` = host time of one timed step (K steps between two
+device synchronisations, divided by K).
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step if --dump-outputs is given
+(rank 0's, as DIR/output_<i>.npy in float32, the model's return order) and prints the line.  Everything else is measured
+only with --full.
 
 Rank 0 prints ONE JSON line.  Objects on that line besides the contract's fields:
   std_ms        standard deviation of the per-step device time (HIP events between the steps of the timed region)
+and with --full only:
   latency_b1    the reference's own latency protocol (Trambav6.py:219-255): batch 1, 50 warm-up + 500 timed forwards
                 (`wall_clock`: its other protocol, test_TSOD.py:71-108 -- 5 + 195 synchronised forwards on the host's clock),
                 one HIP-event pair per forward, mean / std / FPS
@@ -62,11 +68,16 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured 
 MFMA_PEAK_TFS = 2500.0  # dense bf16 MFMA peak (no 2:1 sparsity)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline forward also run the batch-1 latency protocol, the rooflines, the training leg "
+                         "and the CPU baseline (each can still be left out with its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/output_<i>.npy (float32, rank 0's replica)")
     ap.add_argument("--batch", type=int, default=4, help="images per GPU per step (config: 4)")
     ap.add_argument("--img", type=int, default=384)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
@@ -92,7 +103,10 @@ def parse():
                          "cannot cost the run its forward measurement")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend (gloo only to rehearse the N > 1 plumbing on a one-GPU box)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -148,6 +162,24 @@ def pmc_traffic(key):
             best = {"bytes": round(d["traffic_bytes"]), "algorithmic_bytes": d.get("algorithmic_bytes"),
                     "source": os.path.relpath(path, ROOT), "what": d.get("what")}
     return best
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outs, path):
+    """`outs` (a tensor or the model's list of maps) as float32 DIR/output_<i>.npy.  If they exceed DUMP_LIMIT_BYTES in all,
+    every array is cut to the same fixed, seeded sample of its flattened elements, so that two runs stay comparable."""
+    import numpy as np
+    import torch
+    arrays = [t.detach().float().cpu().numpy() for t in ([outs] if torch.is_tensor(outs) else outs)]
+    os.makedirs(path, exist_ok=True)
+    keep = (DUMP_LIMIT_BYTES - 4096 * len(arrays)) // 4 // len(arrays)       # (room for the .npy headers)
+    over = sum(a.nbytes for a in arrays) > DUMP_LIMIT_BYTES
+    for i, a in enumerate(arrays):
+        if over and a.size > keep:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, f"output_{i}.npy"), a)
 
 
 def build_model(img, dtype):
@@ -736,13 +768,18 @@ def main():
         try:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                out_static = step()  # noqa: F841
+                out_static = step()
         except Exception as e:  # graph capture is an optimisation, never a requirement
             if rank == 0:
                 print(f"bench.py: hipGraph capture unavailable ({type(e).__name__}: {e}); running eager", file=sys.stderr)
             graph = None
             torch.cuda.synchronize()
-    run = (lambda: graph.replay()) if graph is not None else step
+    if graph is not None:
+        def run():
+            graph.replay()
+            return out_static
+    else:
+        run = step
     graph_used = graph is not None
 
     for _ in range(args.warmup):
@@ -752,7 +789,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
-        run()
+        out = run()
         marks[i + 1].record()
     sync_all()
     dt = time.perf_counter() - t0
@@ -763,6 +800,29 @@ def main():
     value = world * args.batch * args.steps / dt
     per = torch.tensor([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)], dtype=torch.float64)
     std_ms = float(per.std(unbiased=False)) if args.steps > 1 else 0.0
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
+    line = None
+    if rank == 0:
+        line = {
+            "metric": f"images/sec fwd Tramba-V {args.img}x{args.img}", "value": round(value, 2), "unit": "img/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(dt / args.steps * 1e3, 3), "std_ms": round(std_ms, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"Tramba-V (VMamba-B encoder) {args.img}x{args.img} {args.dtype} inference, "
+                                   f"batch {args.batch} per GPU, random-init weights (seed 1026), randn images",
+                       "global_batch": args.batch * world,
+                       "parallelism": f"dp{world}: the forward leg (`value`) is {world} independent replica(s), no collective; "
+                                      f"the data-parallel figure is train.scaling_value (--full; gradient all-reduce over RCCL)",
+                       "launch": ("hipGraph replay" if graph_used else "eager") +
+                                 ("" if args.no_overlap else ", decoder guide branches on a side stream")},
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- rank 0: latency protocol, rooflines (eager single-stream passes with HIP events around the library's
     #      launches; events cannot live inside a captured graph), CPU baseline
@@ -802,26 +862,14 @@ def main():
             extras_error = f"{type(e).__name__}: {e}"[:400]
             print(f"bench.py: latency / roofline section failed: {extras_error}", file=sys.stderr)
             _models.OVERLAP_BRANCHES = True if not args.no_overlap else False
-    line = None
     if rank == 0:
-        line = {
-            "metric": f"images/sec fwd Tramba-V {args.img}x{args.img}", "value": round(value, 2), "unit": "img/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3), "std_ms": round(std_ms, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"Tramba-V (VMamba-B encoder) {args.img}x{args.img} {args.dtype} inference, "
-                                   f"batch {args.batch} per GPU, random-init weights (seed 1026), randn images",
-                       "global_batch": args.batch * world,
-                       "parallelism": f"dp{world}: the forward leg (`value`) is {world} independent replica(s), no collective; "
-                                      f"the data-parallel figure is train.scaling_value (gradient all-reduce over RCCL)",
-                       "launch": ("hipGraph replay" if graph_used else "eager") +
-                                 ("" if args.no_overlap else ", decoder guide branches on a side stream")},
+        line.update({
             # (filled in last -- the CPU passes run after the GPU legs -- but kept HERE, in front of the long objects, with its
             #  all_cores / single_thread members: `cores` = 1 beside `physical_cores` = 128 reads correctly only with both)
             "cpu_baseline": None,
             "roofline": roof, "latency_b1": lat, "roofline_kernel_boundary": roof_kb, "roofline_fused_scan_all": roof_all,
             "roofline_boundary": roof_b, "roofline_gemm": roof_g, "train": None,
-        }
+        })
         if extras_error is not None:
             line["extras_error"] = extras_error
     # From here on the ranks exchange gradients.  A watchdog thread bounds the leg: if it (or the final barrier) has not

@@ -6,7 +6,7 @@ TAG=${1:-r01}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py --steps 30 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 30 --warmup 10 > $OUT/bench.json 2> $OUT/bench.err
 # (bench.py --no-overlap: one stream, per-kernel durations of kernels running alone)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 5 --warmup 2 --no-graph --no-overlap --no-cpu-baseline --no-train --no-latency > $OUT/trace.log 2>&1
 

@@ -165,3 +165,20 @@ def test_worker_processes_draw_distinct_streams(tmp_path):
     dl = D.train_loader(root, 32, batch_size=1, num_workers=2)
     got = {b["name"][0]: b["image"] for b in dl}
     assert set(got) == {"a", "b"} and not torch.equal(got["a"], got["b"])
+
+
+def test_train_dataset_survives_pickling_for_spawned_workers(tmp_path):
+    """On a GPU build train_loader spawns its workers, which receive the dataset pickled: the augmentation on the global
+    numpy stream must pickle and come back drawing from the (receiving process's) global numpy stream."""
+    import pickle
+    root = str(tmp_path)
+    _write_split(root, "Train", ["a"], [(48, 48)])
+    ds = D.RGB_Dataset(root, ["Train"], 32, "train")
+    back = pickle.loads(pickle.dumps(ds))
+    assert back.transform.augment.rng is np.random and back.images == ds.images
+    np.random.seed(3)
+    want = ds[0]["image"]
+    np.random.seed(3)
+    assert torch.equal(back[0]["image"], want)
+    own = np.random.RandomState(5)
+    assert pickle.loads(pickle.dumps(D.Augment(own))).rng.random() == np.random.RandomState(5).random()

@@ -191,7 +191,7 @@ def test_bench_line_survives_a_stuck_training_leg():
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-latency",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--no-latency",
                           "--no-cpu-baseline", "--train-timeout", "0.05"], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
     line = json.loads(run.stdout.strip().splitlines()[-1])
@@ -208,7 +208,7 @@ def test_bench_starts_its_own_ranks_and_reports_the_dp_step():
     import json
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4",
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "4",
                           "--warmup", "1", "--no-latency"], capture_output=True, text=True, timeout=900)
     assert run.returncode == 0, run.stderr[-2000:]
     lines = [ln for ln in run.stdout.strip().splitlines() if ln.startswith("{")]
@@ -218,3 +218,40 @@ def test_bench_starts_its_own_ranks_and_reports_the_dp_step():
     t = line["train"]
     assert t["global_batch"] == 16 and t["grad_bytes_per_step"] == t["grad_bucket_bytes"] > 4e8
     assert t["allreduce"]["allreduce_alone_ms"] > 0 and "dp2" in t["parallelism"] and t["value"] > 0
+
+
+def test_plain_bench_times_the_forward_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run is the headline forward alone: one line with the contract's fields and none of the --full
+    objects, `value` and `ms_per_step` of the same timed steps, and --dump-outputs writes what the last timed step (a hipGraph
+    replay) returned -- the maps an eager forward of the same seeded model and input gives."""
+    import importlib.util
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    run = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = [ln for ln in run.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"].startswith("images/sec fwd") and line["unit"] == "img/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] / (4 * 1000.0) - 1.0) < 0.01
+    assert not {"train", "cpu_baseline", "latency_b1", "roofline", "roofline_gemm"} & set(line)
+    files = sorted(os.listdir(out))
+    assert files == [f"output_{i}.npy" for i in range(len(files))] and len(files) == 4
+    got = [np.load(out / f) for f in files]
+    assert all(g.dtype == np.float32 and np.isfinite(g).all() for g in got)
+    assert sum(g.nbytes for g in got) <= 64 << 20
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    model = bench.build_model(384, torch.bfloat16)
+    x = torch.randn(4, 3, 384, 384, generator=torch.Generator().manual_seed(0)).cuda()
+    with torch.no_grad():
+        want = [w.float().cpu().numpy() for w in model(x)]
+    for g, w in zip(got, want):
+        assert g.shape == w.shape
+        np.testing.assert_allclose(g, w, rtol=1e-3, atol=1e-3 * float(np.sqrt(np.mean(w.astype(np.float64) ** 2))))

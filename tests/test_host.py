@@ -204,3 +204,28 @@ def test_bench_relay_keeps_a_printed_line_when_the_rank_job_dies(capfd):
     assert ok == 0 and '"metric"' in out.out and "exiting 0" in out.err
     bad = bench.relay_child([sys.executable, "-c", "import sys; print('no result'); sys.exit(7)"])
     assert bad == 7
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py: --full is off by default, --steps / --warmup are validated, and --dump-outputs writes float32 .npy files in
+    the model's return order -- whole below the size limit, above it the same seeded sample of every array on every run."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    args = bench.parse(["--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+    outs = [torch.arange(12, dtype=torch.bfloat16).reshape(3, 4), torch.linspace(-1, 1, 10000).reshape(100, 100)]
+    bench.dump_outputs(outs, str(tmp_path / "whole"))
+    a, b = (np.load(tmp_path / "whole" / f"output_{i}.npy") for i in range(2))
+    assert a.dtype == b.dtype == np.float32 and a.shape == (3, 4) and b.shape == (100, 100)
+    assert np.array_equal(a, np.arange(12).reshape(3, 4)) and np.array_equal(b, outs[1].numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096 * 2 + 4 * 200)     # room for 100 elements per array
+    for d in ("s1", "s2"):
+        bench.dump_outputs(outs, str(tmp_path / d))
+    s1, s2 = (np.load(tmp_path / d / "output_1.npy") for d in ("s1", "s2"))
+    assert s1.shape == (100,) and np.array_equal(s1, s2) and np.isin(s1, b).all()
+    assert np.array_equal(np.load(tmp_path / "s1" / "output_0.npy"), a)

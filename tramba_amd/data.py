@@ -59,7 +59,21 @@ class Augment:
         # custom_transforms.py:109-116 fills the list in this fixed order whatever order the caller names them in
         self.enhancers = [ImageEnhance.Contrast, ImageEnhance.Brightness, ImageEnhance.Sharpness]
 
-    def _scale_crop(self, s):                                       # custom_transforms.py:46-66
+    # A spawned DataLoader worker (train_loader on a GPU build) receives the dataset pickled, and the global `numpy.random`
+    # is a module, which pickle refuses: it travels as None and becomes the worker's own `numpy.random` again, which is
+    # what a forked worker uses too.
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        if state["rng"] is np.random:
+            state["rng"] = None
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        if self.rng is None:
+            self.rng = np.random
+
+    def _scale_crop(self, s):                                      # custom_transforms.py:46-66
         factor = self.rng.random() * (self.scale[1] - self.scale[0]) + self.scale[0]
         if not self.rng.random() < 0.5:
             return
