@@ -458,6 +458,23 @@ int tramba_stem_conv_ln_gelu(const void *img, const float *w, const float *bias,
 #define TRAMBA_EVAL_NDBL 48
 int tramba_saliency_stats(const float *pred, const unsigned char *gt, long long *ints, double *dbl, int batch, int h,
                           int w, void *stream);
+/* The weighted F-measure (Evaluation/metrics.py:379-441), in two steps.  1 <= h, w <= TRAMBA_WFM_MAX_DIM, batch <= 65535.
+ * Exact Euclidean feature transform of gt (B, H, W) u8 (0 / non-zero), the one metrics.py:391 takes from
+ * scipy.ndimage.distance_transform_edt(gt == 0, return_indices=True): idx (B, H, W) i32 = r * W + c of the nearest mask
+ * pixel (identical to scipy's indices, ties included: Maurer's separable algorithm as scipy runs it), dist2 (B, H, W) i32 =
+ * its squared distance.  An image with an empty mask gets idx = dist2 = -1 everywhere. */
+#define TRAMBA_WFM_MAX_DIM 4096
+int tramba_feature_transform(const unsigned char *gt, int *idx, int *dist2, int batch, int h, int w, void *stream);
+/* sums (B, 3) f64 per image = { sum gt, sum Ew[gt], sum Ew[~gt] } of metrics.py:393-419 (then R = 1 - sums[1] / sums[0],
+ * P = TPw / (TPw + sums[2] + eps) with TPw = sums[0] - sums[1], on the host): pred (B, H, W) f32 min-max normalised in fp32
+ * (metrics.py:13-19), E = |p - g|, Et = E of the nearest mask pixel (idx / dist2 from the feature transform of the same gt),
+ * EA = 7x7 filter of Et with zero padding (fp64 accumulation, fp32 result), MIN_E_EA, B = 2 - exp(ln(0.5) / 5 * dist) in
+ * fp64, Ew = MIN_E_EA * B.  gauss: HOST array of the 49 filter weights, row-major (matlab_style_gauss2D, metrics.py:429-441);
+ * it travels by value.  workspace: device memory of the size the workspace query returns.  Fixed summation order: bitwise
+ * reproducible, independent of the batch an image is in.  An empty mask gives sums = 0. */
+size_t tramba_weighted_f_workspace(int batch, int h, int w);
+int tramba_weighted_f_sums(const float *pred, const unsigned char *gt, const int *idx, const int *dist2, const double *gauss,
+                           double *sums, void *workspace, size_t workspace_bytes, int batch, int h, int w, void *stream);
 
 /* ------------------------------------------------------------------ loss and optimizer of the training step */
 /* The deep-supervision loss (train.py:76-85; utils/loss.py:6-11) of ONE output: logits (planes, h, w) f32 bilinearly resized

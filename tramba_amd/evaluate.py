@@ -8,13 +8,17 @@ and S-measure are finished from those on the host in fp64.  The classes keep the
 `step(pred, gt)` / `get_results()` interface (and result dictionaries), so `test_one_epoch` reads like the
 reference's; stepping the five objects with the same arrays launches the kernel once.
 
-WeightedFmeasure needs an exact Euclidean distance transform with nearest-pixel indices (scipy's, in the
-reference); it is host-side post-processing here exactly as it is there -- there is no HIP variant of it, and it is
-not on the path bench.py measures.
+WeightedFmeasure needs an exact Euclidean distance transform with nearest-pixel indices (scipy's, in the reference).
+`tramba_feature_transform` (csrc/saliency_wfm.hip) computes it on the GPU, index for index scipy's, and
+`tramba_weighted_f_sums` reduces the error spreading, the 7x7 Gaussian, the pixel weights and the weighted sums to three
+numbers per image; R, P and Q are finished on the host in fp64.  It shares the upload of the other four (one copy of a
+host map per step).  `WeightedFmeasure(host=True)` keeps the reference's scipy path, for A/B and for hosts without a
+device.  `evaluate_folder` is the package's counterpart of Evaluation/evaluate_TSOD.py for one folder pair.
 """
 import os
 import struct
 import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -110,28 +114,52 @@ class ImageStats:
         return max(0, score + (1 - alpha) * reg)
 
 
-def image_stats(pred, gt):
-    """pred, gt: (H, W) or (B, H, W), numpy or torch (any device) -> list of ImageStats.  pred = sigmoid(logits)."""
+def _upload(pred, gt):
+    """pred, gt: (H, W) or (B, H, W), numpy or torch (any device) -> (B, H, W) f32 and bool on the current device"""
     dev = torch.device("cuda", torch.cuda.current_device())
     p = torch.as_tensor(pred).to(dev, torch.float32)
     g = torch.as_tensor(np.asarray(gt).astype(bool) if isinstance(gt, np.ndarray) else gt).to(dev)
     if p.dim() == 2:
         p, g = p[None], g[None]
-    ints, dbl = hip.saliency_stats(p, g != 0)
+    return p, g != 0
+
+
+def _stats(p, g):
+    ints, dbl = hip.saliency_stats(p, g)
     ints, dbl = ints.cpu().numpy(), dbl.cpu().numpy()
     return [ImageStats(ints[i], dbl[i], p.shape[1:]) for i in range(p.shape[0])]
 
 
-_memo = {"key": None, "stats": None}
+def image_stats(pred, gt):
+    """pred, gt: (H, W) or (B, H, W), numpy or torch (any device) -> list of ImageStats.  pred = sigmoid(logits)."""
+    return _stats(*_upload(pred, gt))
+
+
+_memo = {"key": None}
+
+
+def _memo_for(pred, gt):
+    """one upload, one statistics launch and one weighted-F launch for the five metric objects of test_one_epoch
+    stepped with the same (pred, gt)"""
+    key = (id(pred), id(gt))
+    if _memo["key"] != key:
+        _memo.clear()
+        _memo.update(key=key, hold=(pred, gt), dev=_upload(pred, gt))     # hold: keep the ids alive with the entry
+    return _memo
 
 
 def _stats_for(pred, gt):
-    """one launch for the five metric objects of test_one_epoch stepped with the same (pred, gt)"""
-    key = (id(pred), id(gt))
-    if _memo["key"] != key:
-        _memo["key"], _memo["stats"] = key, image_stats(pred, gt)
-        _memo["hold"] = (pred, gt)          # keep the ids alive for as long as the memo entry
-    return _memo["stats"]
+    m = _memo_for(pred, gt)
+    if "stats" not in m:
+        m["stats"] = _stats(*m["dev"])
+    return m["stats"]
+
+
+def _wfm_sums_for(pred, gt):
+    m = _memo_for(pred, gt)
+    if "wfm" not in m:
+        m["wfm"] = hip.weighted_f_sums(*m["dev"]).cpu().numpy()
+    return m["wfm"]
 
 
 # ----------------------------------------------------------------------------- the reference's metric objects
@@ -194,19 +222,33 @@ class Emeasure:
 
 
 class WeightedFmeasure:
-    """Evaluation/metrics.py:379-441.  Host-side (scipy distance transform), as in the reference."""
+    """Evaluation/metrics.py:379-441.  On the GPU (tramba_weighted_f_sums, finished here in fp64); `host=True` runs the
+    reference's scipy distance transform and convolution on the host instead."""
 
-    def __init__(self, beta: float = 1):
+    def __init__(self, beta: float = 1, host: bool = False):
         self.beta = beta
+        self.host = host
         self.weighted_fms = []
 
     def step(self, pred, gt):
+        if not self.host:
+            self.weighted_fms.extend(self._finish(*row) for row in _wfm_sums_for(pred, gt))
+            return
         pred = pred.detach().cpu().numpy() if isinstance(pred, torch.Tensor) else np.asarray(pred)
         gt = gt.detach().cpu().numpy() if isinstance(gt, torch.Tensor) else np.asarray(gt)
         if pred.ndim == 2:
             pred, gt = pred[None], gt[None]
         for p, g in zip(pred, gt):
             self.weighted_fms.append(self._one(p, g.astype(bool)))
+
+    def _finish(self, n_fg, s_fg, s_bg):
+        """metrics.py:384-425 from { sum gt, sum Ew[gt], sum Ew[~gt] }"""
+        if n_fg == 0:
+            return 0
+        tp = n_fg - s_fg
+        rec = 1 - s_fg / n_fg
+        prec = tp / (tp + s_bg + _EPS)
+        return (1 + self.beta) * rec * prec / (rec + self.beta * prec + _EPS)
 
     def _one(self, pred, gt):
         from scipy.ndimage import convolve, distance_transform_edt
@@ -313,3 +355,56 @@ def save_predictions(model, batches, save_path, graph=False):
                 write_png_gray8(out, pred)
                 written.append(out)
     return written
+
+
+def _load_pair(paths):
+    """Evaluation/evaluate_TSOD.py:23-40, 64-65: PIL convert('L') -> float32; pred / 255, gt / (max + 1e-8)"""
+    from PIL import Image
+
+    def grey(path):
+        with open(path, "rb") as f:
+            return np.asarray(Image.open(f).convert("L"), np.float32)
+
+    pred, gt = grey(paths[0]), grey(paths[1])
+    if pred.shape != gt.shape:
+        raise ValueError(f"{paths[0]}: prediction {pred.shape} and mask {gt.shape} differ in size")
+    gt /= gt.max() + 1e-8
+    return pred / 255, gt
+
+
+def evaluate_folder(salmap_root, gt_root, model=None, dataset=None, save_dir=None, workers=8):
+    """Evaluation/evaluate_TSOD.py:53-112 (evaluate_model) for one folder pair: the .png / .jpg files present in both
+    folders, sorted, each map against its mask with the five metrics on the device.  Returns the reference's results
+    dictionary plus its `precision` / `recall` curves (float32, as it saves them); with `save_dir` they are also written
+    there as precision.npy / recall.npy.  PNG decoding runs on a pool of at most 16 threads, ahead of the metrics."""
+    ext = (".jpg", ".png")
+    names = sorted({f for f in os.listdir(salmap_root) if f.endswith(ext)} & {f for f in os.listdir(gt_root) if f.endswith(ext)})
+    fm, wfm, sm, em, mae = Fmeasure_and_FNR(), WeightedFmeasure(), Smeasure(), Emeasure(), MAE()
+    pairs = [(os.path.join(salmap_root, n), os.path.join(gt_root, n)) for n in names]
+    workers = max(1, min(16, int(workers)))
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        ahead = [pool.submit(_load_pair, p) for p in pairs[:2 * workers]]     # bounded read-ahead, in order
+        for i in range(len(pairs)):
+            pred, gt = ahead[i].result()
+            ahead[i] = None
+            if i + 2 * workers < len(pairs):
+                ahead.append(pool.submit(_load_pair, pairs[i + 2 * workers]))
+            for m in (fm, wfm, sm, em, mae):
+                m.step(pred=pred, gt=gt)
+    (f, fnr), e = fm.get_results(), em.get_results()["em"]
+    precision, recall = np.array(f["pr"]["p"], np.float32), np.array(f["pr"]["r"], np.float32)
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+        np.save(os.path.join(save_dir, "precision.npy"), precision)
+        np.save(os.path.join(save_dir, "recall.npy"), recall)
+    r4 = lambda v: np.round(v, 4)
+    return {
+        "model": model, "dataset": dataset,
+        "Smeasure_r": r4(sm.get_results()["sm"]),
+        "Wmeasure_r": r4(wfm.get_results()["wfm"]),
+        "MAE_r": r4(mae.get_results()["mae"]),
+        "adpEm_r": r4(e["adp"]), "meanEm_r": r4(e["curve"].mean()), "maxEm_r": r4(e["curve"].max()),
+        "adpFm_r": r4(f["fm"]["adp"]), "meanFm_r": r4(f["fm"]["curve"].mean()), "maxFm_r": r4(f["fm"]["curve"].max()),
+        "fnr_r": r4(fnr),
+        "precision": precision, "recall": recall,
+    }

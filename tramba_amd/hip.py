@@ -69,6 +69,9 @@ SIGNATURES = {
     "tramba_rowdot_bwd_parts": (c_i64, [c_i64, c_int, c_int]),
     "tramba_rowdot_bwd_cl": (c_int, [c_vp] * 5 + [c_i64, c_int, c_int, c_vp]),
     "tramba_saliency_stats": (c_int, [c_vp] * 4 + [c_int] * 3 + [c_vp]),
+    "tramba_feature_transform": (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp]),
+    "tramba_weighted_f_workspace": (ctypes.c_size_t, [c_int] * 3),
+    "tramba_weighted_f_sums": (c_int, [c_vp] * 7 + [ctypes.c_size_t] + [c_int] * 3 + [c_vp]),
     "tramba_dw_pack": (c_int, [c_vp] * 8 + [c_int] * 2 + [c_vp]),
     "tramba_dwconv_cl": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
     "tramba_dwconv_dual_cl": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp]),
@@ -665,6 +668,66 @@ def saliency_stats(pred, gt):
     dbl = torch.empty((b, EVAL_NDBL), dtype=torch.float64, device=pred.device)
     _check(lib().tramba_saliency_stats(_ptr(pred), _ptr(g8), _ptr(ints), _ptr(dbl), b, h, w, _stream()), "saliency_stats")
     return ints, dbl
+
+
+WFM_MAX_DIM = 4096     # TRAMBA_WFM_MAX_DIM
+
+
+def _mask_u8(what, gt, shape=None):
+    if gt.dtype not in (torch.bool, torch.uint8) or gt.dim() != 3 or (shape is not None and gt.shape != shape):
+        raise TrambaHipError(f"{what}: gt must be a (B, H, W) bool / uint8 mask" +
+                             (f" of the prediction's shape {tuple(shape)}" if shape is not None else "") +
+                             f", got {gt.dtype} {tuple(gt.shape)}")
+    b, h, w = gt.shape
+    if not (0 < b <= 65535 and 0 < h <= WFM_MAX_DIM and 0 < w <= WFM_MAX_DIM):
+        raise TrambaHipError(f"{what}: shape {tuple(gt.shape)} outside 1 .. {WFM_MAX_DIM} per side")
+    gt = gt.contiguous()
+    _dev(gt)
+    return gt.view(torch.uint8)
+
+
+def feature_transform(gt):
+    """gt (B, H, W) bool / u8 -> (idx, dist2), both (B, H, W) int32 on the device: the flat index r * W + c of the nearest
+    non-zero pixel and its squared distance, index for index what scipy.ndimage.distance_transform_edt(gt == 0,
+    return_indices=True) gives (ties included).  An image with no non-zero pixel gets -1 everywhere."""
+    g8 = _mask_u8("feature_transform", gt)
+    b, h, w = g8.shape
+    idx = torch.empty((b, h, w), dtype=torch.int32, device=g8.device)
+    dist2 = torch.empty_like(idx)
+    _check(lib().tramba_feature_transform(_ptr(g8), _ptr(idx), _ptr(dist2), b, h, w, _stream()), "feature_transform")
+    return idx, dist2
+
+
+def _gauss7():
+    """Evaluation/metrics.py:429-441 matlab_style_gauss2D((7, 7), sigma=5), row-major, fp64"""
+    y, x = np.ogrid[-3:4, -3:4]
+    g = np.exp(-(x * x + y * y) / (2 * 5 * 5))
+    g[g < np.finfo(g.dtype).eps * g.max()] = 0
+    if g.sum() != 0:
+        g /= g.sum()
+    return np.ascontiguousarray(g, dtype=np.float64).ravel()
+
+
+_GAUSS7 = _gauss7()
+
+
+def weighted_f_sums(pred, gt):
+    """pred (B, H, W) f32 = sigmoid(logits), gt (B, H, W) bool / u8 -> sums (B, 3) f64 on the device:
+    { sum gt, sum Ew[gt], sum Ew[~gt] } of the weighted F-measure (layout: include/tramba_hip.h)."""
+    if pred.dtype != torch.float32 or pred.dim() != 3:
+        raise TrambaHipError(f"weighted_f_sums: pred must be (B, H, W) float32, got {pred.dtype} {tuple(pred.shape)}")
+    pred = pred.contiguous()
+    _dev(pred)
+    g8 = _mask_u8("weighted_f_sums", gt, pred.shape)
+    if g8.device != pred.device:
+        raise TrambaHipError("weighted_f_sums: pred and gt are on different devices")
+    b, h, w = pred.shape
+    idx, dist2 = feature_transform(g8)
+    ws = torch.empty(lib().tramba_weighted_f_workspace(b, h, w), dtype=torch.uint8, device=pred.device)
+    sums = torch.empty((b, 3), dtype=torch.float64, device=pred.device)
+    _check(lib().tramba_weighted_f_sums(_ptr(pred), _ptr(g8), _ptr(idx), _ptr(dist2), _GAUSS7.ctypes.data, _ptr(sums),
+                                        _ptr(ws), ws.numel(), b, h, w, _stream()), "weighted_f_sums")
+    return sums
 
 
 def rowdot_cl(x, w, bias: float):
