@@ -29,6 +29,10 @@
  *   tramba_linear_cl            Linear2d.forward (1x1 conv)     Models/modules.py:10-13
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
  *   tramba_stem_conv_ln_gelu
+ *   tramba_resize_table /       get_transform(S, 'Test'): Resize + ToTensor + Normalize
+ *   tramba_frames_to_input                                      data/dataloader.py:22-39, data/custom_transforms.py
+ *   tramba_logits_to_u8         F.interpolate + sigmoid * 255 -> uint8 of the saved maps
+ *                                                               test_TSOD.py:61-66
  *
  * "_cl" = channels-last: activations are (B, H*W, C) row-major, C contiguous.
  */
@@ -475,6 +479,30 @@ int tramba_feature_transform(const unsigned char *gt, int *idx, int *dist2, int 
 size_t tramba_weighted_f_workspace(int batch, int h, int w);
 int tramba_weighted_f_sums(const float *pred, const unsigned char *gt, const int *idx, const int *dist2, const double *gauss,
                            double *sums, void *workspace, size_t workspace_bytes, int batch, int h, int w, void *stream);
+
+/* ------------------------------------------------------------------ deployment: frames in, saliency maps out */
+/* Camera frames to model input, bit for bit the loader's test transform (data/dataloader.py:22-39 get_transform(S, 'Test'):
+ * custom_transforms.py Resize(BILINEAR) + ToTensor/Normalize).  The resize is PIL's separable 8-bit bilinear resample
+ * (horizontal pass into a u8 intermediate, then vertical; fixed-point weights with 22 fractional bits; an axis whose size
+ * does not change is copied), the normalisation f = u8 / 255 in fp32, t = fp32(f - mean[c]), out = fp32(t / std[c]) with
+ * mean / std in fp64.  Sizes: 1 <= in_h, in_w <= TRAMBA_FRAME_MAX_DIM, 1 <= out_h, out_w <= TRAMBA_FRAME_MAX_OUT.
+ * tramba_resize_table fills the HOST int32 table for one (frame size, output size) pair, in fp64 on the host:
+ * tramba_resize_table_words() words (0: sizes rejected); the caller uploads it once and reuses it.
+ * tramba_frames_to_input: frames (B, in_h, in_w, 3) u8 contiguous, RGB (bgr = 0) or BGR (bgr = 1); table: the DEVICE copy of
+ * the table for these sizes; out (B, 3, out_h, out_w) f32, channels in RGB order.  batch <= 65535. */
+#define TRAMBA_FRAME_MAX_DIM 16384
+#define TRAMBA_FRAME_MAX_OUT 2048
+size_t tramba_resize_table_words(int in_h, int in_w, int out_h, int out_w);
+int tramba_resize_table(int in_h, int in_w, int out_h, int out_w, const double *mean, const double *std, int *table,
+                        size_t words);
+int tramba_frames_to_input(const unsigned char *frames, const int *table, float *out, int batch, int h, int w, int out_h,
+                           int out_w, int bgr, void *stream);
+/* Logits to saliency maps at the frame's size (test_TSOD.py:61-66): logits (B, 1, in_h, in_w) f32 / f16 / bf16 (dtype), out
+ * (B, h, w) u8 = uint8(sigmoid(F.interpolate(logits.float(), (h, w), mode='bilinear', align_corners=False)) * 255), with
+ * torch's source-index and lambda arithmetic.  1 <= in_h, in_w <= TRAMBA_FRAME_MAX_OUT, 1 <= h, w <= TRAMBA_FRAME_MAX_DIM,
+ * batch <= 65535. */
+int tramba_logits_to_u8(const void *logits, unsigned char *out, int batch, int in_h, int in_w, int h, int w, int dtype,
+                        void *stream);
 
 /* ------------------------------------------------------------------ loss and optimizer of the training step */
 /* The deep-supervision loss (train.py:76-85; utils/loss.py:6-11) of ONE output: logits (planes, h, w) f32 bilinearly resized

@@ -5,7 +5,7 @@ Trambav6_enc.bulid_model, SS2D scan/merge plugin API, selective_scan_cuda_oflex 
 every hot op a hand-written HIP kernel behind the C ABI of include/tramba_hip.h.
 """
 from .graph import GraphedForward, GraphedTrainStep  # noqa: F401
-from . import data, evaluate, hip  # noqa: F401  (hip: ctypes binding, loads lazily)
+from . import data, evaluate, hip, infer  # noqa: F401  (hip: ctypes binding, loads lazily)
 from .models import (BaseUMamba, BaseUMambaEnc, VSSMDecoder, build, bulid_model, bulid_model_enc,  # noqa: F401
                      prepare_inference)
 from .modules import (DCT2D, SS2D, DropPath, DWConv, DWMSMlp, FinalPatchExpand_X4, FreqBlockv6,  # noqa: F401

@@ -72,6 +72,10 @@ SIGNATURES = {
     "tramba_feature_transform": (c_int, [c_vp] * 3 + [c_int] * 3 + [c_vp]),
     "tramba_weighted_f_workspace": (ctypes.c_size_t, [c_int] * 3),
     "tramba_weighted_f_sums": (c_int, [c_vp] * 7 + [ctypes.c_size_t] + [c_int] * 3 + [c_vp]),
+    "tramba_resize_table_words": (ctypes.c_size_t, [c_int] * 4),
+    "tramba_resize_table": (c_int, [c_int] * 4 + [c_vp] * 3 + [ctypes.c_size_t]),
+    "tramba_frames_to_input": (c_int, [c_vp] * 3 + [c_int] * 6 + [c_vp]),
+    "tramba_logits_to_u8": (c_int, [c_vp] * 2 + [c_int] * 6 + [c_vp]),
     "tramba_dw_pack": (c_int, [c_vp] * 8 + [c_int] * 2 + [c_vp]),
     "tramba_dwconv_cl": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
     "tramba_dwconv_dual_cl": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp]),
@@ -728,6 +732,56 @@ def weighted_f_sums(pred, gt):
     _check(lib().tramba_weighted_f_sums(_ptr(pred), _ptr(g8), _ptr(idx), _ptr(dist2), _GAUSS7.ctypes.data, _ptr(sums),
                                         _ptr(ws), ws.numel(), b, h, w, _stream()), "weighted_f_sums")
     return sums
+
+
+FRAME_MAX_DIM, FRAME_MAX_OUT = 16384, 2048     # TRAMBA_FRAME_MAX_DIM / TRAMBA_FRAME_MAX_OUT
+
+
+def resize_table_host(in_h: int, in_w: int, out_h: int, out_w: int, mean, std) -> np.ndarray:
+    """int32 host table of tramba_frames_to_input for one (frame size, output size): PIL's bilinear fixed-point weights per
+    axis and the 3 x 256 normalisation table (layout: csrc/frames.hip), computed by the library in fp64."""
+    words = lib().tramba_resize_table_words(in_h, in_w, out_h, out_w)
+    if words == 0:
+        raise TrambaHipError(f"resize_table: {in_h}x{in_w} -> {out_h}x{out_w} outside 1 .. {FRAME_MAX_DIM} per frame side, "
+                             f"1 .. {FRAME_MAX_OUT} per output side")
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    std = np.ascontiguousarray(std, dtype=np.float64)
+    if mean.shape != (3,) or std.shape != (3,):
+        raise TrambaHipError("resize_table: mean and std need 3 values each")
+    out = np.empty(words, dtype=np.int32)
+    _check(lib().tramba_resize_table(in_h, in_w, out_h, out_w, mean.ctypes.data, std.ctypes.data, out.ctypes.data, words),
+           "resize_table")
+    return out
+
+
+def frames_to_input(frames, table, out_h: int, out_w: int, bgr: bool = False):
+    """frames (B, H, W, 3) u8 on the device + the device copy of resize_table_host(H, W, out_h, out_w, ...) ->
+    (B, 3, out_h, out_w) f32: the loader's test transform (resize + normalisation), bit for bit."""
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
+        raise TrambaHipError(f"frames_to_input: frames must be (B, H, W, 3) uint8, got {frames.dtype} {tuple(frames.shape)}")
+    _dev(frames, table)
+    b, h, w, _ = frames.shape
+    if not (0 < b <= 65535 and 0 < h <= FRAME_MAX_DIM and 0 < w <= FRAME_MAX_DIM):
+        raise TrambaHipError(f"frames_to_input: frames {tuple(frames.shape)} outside 1 .. {FRAME_MAX_DIM} per side")
+    if table.dtype != torch.int32 or table.numel() < lib().tramba_resize_table_words(h, w, out_h, out_w):
+        raise TrambaHipError("frames_to_input: table does not belong to these sizes")
+    out = torch.empty((b, 3, out_h, out_w), dtype=torch.float32, device=frames.device)
+    _check(lib().tramba_frames_to_input(_ptr(frames), _ptr(table), _ptr(out), b, h, w, out_h, out_w, int(bool(bgr)),
+                                        _stream()), "frames_to_input")
+    return out
+
+
+def logits_to_u8(logits, h: int, w: int):
+    """logits (B, 1, S, S') f32 / f16 / bf16 on the device -> (B, h, w) u8 =
+    uint8(sigmoid(F.interpolate(logits.float(), (h, w), mode="bilinear", align_corners=False)) * 255)."""
+    if logits.dim() != 4 or logits.shape[1] != 1:
+        raise TrambaHipError(f"logits_to_u8: logits must be (B, 1, H, W), got {tuple(logits.shape)}")
+    logits = logits.contiguous()
+    _dev(logits)
+    b, _, ih, iw = logits.shape
+    out = torch.empty((b, h, w), dtype=torch.uint8, device=logits.device)
+    _check(lib().tramba_logits_to_u8(_ptr(logits), _ptr(out), b, ih, iw, h, w, dt(logits), _stream()), "logits_to_u8")
+    return out
 
 
 def rowdot_cl(x, w, bias: float):
