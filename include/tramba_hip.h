@@ -100,19 +100,14 @@ int tramba_tune_get(int knob);
 #define TRAMBA_TUNE_MERGE_FORM 0
 #define TRAMBA_TUNE_SCAN_FORM 1      /* 1 = chained (register ring), 2 = wave-segment, 3 = chained on LDS-DMA staged operands */
 #define TRAMBA_TUNE_SCAN_W 2         /* waves per sequence of the register-ring chained scan (capped by the library's own choice) */
-#define TRAMBA_TUNE_GEMM_TILE 3      /* plain GEMMs with K % 64 == 0: 0 = 64x64 staged by LDS-DMA, 3 or 4 stages by shape (the default), 6 / 7 = 3 / 4 stages;
-                                        register-staged
-                                        forms: 1 = 64x64, 2 = 128x128, 3 = 128x64, 4 = 96x64 where it saves a round of the chip,
-                                        5 = 64x64 on a 4-stage ring; 13 / 14 = the LDS-DMA kernel on 2 stages everywhere / nowhere (default:
-                                        K <= 256 on grids of >= 1024 tiles); 15 = 96x64 LDS-DMA tiles (3 compute waves + a loader wave) wherever M >= 96.
-                                        weight-gradient TN GEMMs (tramba_wgrad_cl): 0 = token tiles staged by LDS-DMA on 3 stages, one
-                                        workgroup per CU (the default); 8 = register-staged, one tile in flight; 9 = LDS-DMA on 4 stages;
-                                        10 / 11 / 12 = 384 / 512 / 768 workgroups wanted by the token split */
+#define TRAMBA_TUNE_GEMM_TILE 3      /* 16-bit GEMMs with K % 64 == 0 (tramba_linear_cl / _ln_cl / _dual_cl): forces one form wherever it can run,
+                                        else the entry's own rule.  0 = the library's rule; 7 = 64x64 LDS-DMA tiles on 4 stages (plain
+                                        entry only); 13 / 14 = the same on 2 / 3 stages; 16 / 17 = producer / consumer tiles on 3 / 4
+                                        stages; 18 = the rule without the producer / consumer and weight-stationary forms (the r03
+                                        kernels); 19 = weight-stationary wherever it can run.  Other values are refused. */
 #define TRAMBA_TUNE_MAILBOX_SKIP 4   /* tests only: > 0 withholds the carry hand-over of that tile (chain order) in the fused scans, so that
                                         the wave waiting for it runs out of polls (~0.1 s) and the device error word is raised; 0 = off */
-#define TRAMBA_TUNE_WGRAD_FORM 5     /* weight-gradient TN GEMM alone: 1 = the register-staged kernel (as TRAMBA_TUNE_GEMM_TILE 8, which also switches
-                                        the projections); 2 = the LDS-DMA kernel with r03's counted lgkmcnt waits on its transposed reads
-                                        (NOT safe beside other kernels on the same CU: scripts/dev/debug_wgrad_concurrent.py) */
+                                     /* knob 5 (the weight-gradient form) is retired: refused */
 #define TRAMBA_TUNE_DW_FORM 6        /* 7x7 depth-wise stencil and its weight gradient: 1 = the r03 kernels (one output row per thread / tap row outer),
                                         0 = the kernels that march down a band of rows (default) */
 #define TRAMBA_TUNE_DW_ROWS 7        /* rows per band of the marching 7x7 kernels (0 = the library's choice) */

@@ -2,15 +2,15 @@
 """Same-box A/B of the whole model between settings of the library's tune knobs (include/tramba_hip.h): every variant is captured
 as a hipGraph with its knobs set -- the batch-4 bf16 inference forward (BASELINE configs[1]) and the batch-8 training step
 (configs[2], GraphedTrainStep) -- and the graphs are replayed alternately in ONE process (box-to-box spread is 3-5 %, more than most
-single changes).  A variant is a comma-separated list of knob=value, knobs: gemm, dw, dwrows, wgrad, scan, merge; "base" = all 0.
+single changes).  A variant is a comma-separated list of knob=value, knobs: gemm, dw, dwrows, scan, merge; "base" = all 0.
 usage: python scripts/ab_knobs.py [fwd|train|both] variant [variant ...]     e.g.  ab_knobs.py both dw=1 base"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import tramba_amd as ta
 from tramba_amd import hip, train
 
-KNOBS = {"gemm": hip.TUNE_GEMM_TILE, "dw": hip.TUNE_DW_FORM, "dwrows": hip.TUNE_DW_ROWS, "wgrad": hip.TUNE_WGRAD_FORM,
-         "scan": hip.TUNE_SCAN_FORM, "merge": hip.TUNE_MERGE_FORM}
+KNOBS = {"gemm": hip.TUNE_GEMM_TILE, "dw": hip.TUNE_DW_FORM, "dwrows": hip.TUNE_DW_ROWS, "scan": hip.TUNE_SCAN_FORM,
+         "merge": hip.TUNE_MERGE_FORM}
 legs = sys.argv[1] if len(sys.argv) > 1 else "both"
 variants = sys.argv[2:] or ["base"]
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The tall, short-K GEMMs of the model (output-bound: K <= 512, thousands of tiles), hipGraph-timed, per LDS stage count of
-linear_dma_kernel: TRAMBA_TUNE_GEMM_TILE 0 = the library's choice, 13 = 2 stages (5 workgroups per CU), 6 = 3 stages."""
+linear_dma_kernel: TRAMBA_TUNE_GEMM_TILE 0 = the library's choice, 13 = 2 stages (5 workgroups per CU), 14 = 3 stages."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tramba_amd import hip
@@ -13,7 +13,7 @@ for m, n, k in SHAPES:
     b = torch.randn(n, device=dev)
     line, ref = f"M={m:6d} N={n:5d} K={k:5d}:", None
     for act in (0, 2):
-        for form in (0, 13, 6):
+        for form in (0, 13, 14):
             hip.tune_set(hip.TUNE_GEMM_TILE, form)
             fn = lambda: hip.linear_cl(x, w, b, None, act)
             for _ in range(3):

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Weight-gradient TN GEMM (tramba_wgrad_cl) on the shapes of a batch-8 Tramba-V training step: time per call (TN kernel +
-slab sum) and TFLOP/s, per staging form (TRAMBA_TUNE_GEMM_TILE: 0 = LDS-DMA, 3 stages, ~256 workgroups (the library's choice); 9 =
-4 stages; 8 = register-staged, one tile in flight; 10 / 11 / 12 = 384 / 512 / 768 workgroups wanted).  usage: bench_wgrad.py [lib path ...]  (other libraries: child processes)"""
+slab sum) and TFLOP/s (LDS-DMA, 3 stages, ~256 workgroups; the retired forms' numbers are in profiles/).  usage: bench_wgrad.py
+[lib path ...]  (other libraries: child processes)"""
 import os
 import subprocess
 import sys
@@ -23,13 +23,12 @@ def child(path):
     if path != "product":
         hip.LIB_PATH = path
     dev = torch.device("cuda")
-    tot = {0: 0.0, 9: 0.0, 8: 0.0, 10: 0.0, 11: 0.0, 12: 0.0}
+    tot = {0: 0.0}
     for (m, n, k) in SHAPES:
         gy = torch.randn(m, n, device=dev).bfloat16()
         x = torch.randn(m, k, device=dev).bfloat16()
         line, ref = f"  M={m:6d} N={n:5d} K={k:5d}:", None
-        for form in (0, 9, 8, 10, 11, 12):
-            hip.tune_set(hip.TUNE_GEMM_TILE, form)
+        for form in tot:
             for _ in range(3):
                 gw, gb = hip.wgrad_cl(gy, x, True)
             torch.cuda.synchronize()
@@ -50,9 +49,8 @@ def child(path):
             del graph, keep
             tot[form] += us
             ref = (gw, gb) if ref is None else ref
-            same = form >= 10 or (torch.equal(gw, ref[0]) and torch.equal(gb, ref[1]))   # (another split: another order)
+            same = torch.equal(gw, ref[0]) and torch.equal(gb, ref[1])
             line += f"  f{form}: {us:5.1f} us {2.0 * m * n * k / us / 1e6:5.0f} TF{'' if same else ' DIFFERS'}"
-        hip.tune_set(hip.TUNE_GEMM_TILE, 0)
         print(line, flush=True)
     print("  sums: " + "  ".join(f"form {f}: {t:.1f} us" for f, t in tot.items()), flush=True)
 

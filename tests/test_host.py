@@ -38,6 +38,25 @@ def test_bad_arguments_are_rejected_not_fatal():
         hip.layernorm_cl(torch.zeros(2, 8), torch.ones(8), torch.zeros(8))  # CPU tensor: no fallback
 
 
+def test_retired_gemm_forms_are_refused_and_sizes_ignore_the_knob():
+    from tramba_amd import hip
+    lib = hip.lib()
+    shapes = [(36864, 512, 128, 1, 1), (73728, 512, 2048, 1, 1), (1152, 1024, 4096, 1, 1), (9216, 192, 64, 4, 2)]
+    sizes = [lib.tramba_wgrad_workspace(*s) for s in shapes]
+    try:
+        for v in (1, 2, 3, 4, 5, 6, 8, 9, 10, 11, 12, 15, 20, -1):
+            assert lib.tramba_tune_set(hip.TUNE_GEMM_TILE, v) == -1, v      # TRAMBA_ERR_ARG
+            assert b"TRAMBA_TUNE_GEMM_TILE" in lib.tramba_last_error() and lib.tramba_tune_get(hip.TUNE_GEMM_TILE) == 0
+        for v in (0, 1, 2):
+            assert lib.tramba_tune_set(5, v) == -1 and b"retired" in lib.tramba_last_error()
+        for v in (0, 7, 13, 14, 16, 17, 18, 19):
+            hip.tune_set(hip.TUNE_GEMM_TILE, v)
+            assert lib.tramba_tune_get(hip.TUNE_GEMM_TILE) == v
+            assert [lib.tramba_wgrad_workspace(*s) for s in shapes] == sizes, v
+    finally:
+        hip.tune_set(hip.TUNE_GEMM_TILE, 0)
+
+
 @pytest.mark.parametrize("fam", ["raster", "line", "helix", "window", "dilation"])
 @pytest.mark.parametrize("h", [12, 24, 48, 96, 16, 32, 64, 192])
 def test_native_tables_equal_oracle(fam, h):

@@ -146,24 +146,21 @@ struct ConvGeom {
 // (n = 8g + 4(lane >> 5) + 0..3).  Dropping it into the fp32 staging tile is four 16-byte LDS writes per lane instead of
 // sixteen 4-byte ones, and with a row stride of BN + 4 floats the 16 lanes of a write pass hit 16 different bank groups
 // (the plain orientation wrote 2-way conflicting 4-byte columns: a quarter of the tall GEMMs' LDS time).
-// Wave layouts of a 256-thread block: NWM = 2 -> 2 x 2 waves (each BM/2 x BN/2); NWM = 3 -> 3 x 1 compute waves (each
-// BM/3 x BN), the fourth wave only stages operands and streams the epilogue (the 96x64 tile: M = 2304 is 24 x 96, so the
-// 15-block stage's 512-wide GEMMs make 192 workgroups = ONE round on 256 CUs, where 64x64 tiles make 288 = two).
-template <int BM, int BN, int NWM>
+// Wave layout of the 256 multiplying threads of a block: 2 x 2 waves, each BM/2 x BN/2.
+template <int BM, int BN>
 struct WaveLayout {
-    static constexpr int NWN = NWM == 2 ? 2 : 1;
-    static constexpr int WM = BM / NWM, WN = BN / NWN, TM = WM / 32, TN = WN / 32;
+    static constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
     static_assert(WM % 32 == 0 && WN % 32 == 0, "wave tiles are whole 32x32 MFMA tiles");
 };
 
-template <int BM, int BN, int NWM = 2, typename ACC>
+template <int BM, int BN, typename ACC>
 __device__ __forceinline__ void acc_to_lds(ACC &acc, float *ep)   // ACC = acc16_t[TM][TN] of the layout
 {
-    using WL = WaveLayout<BM, BN, NWM>;
+    using WL = WaveLayout<BM, BN>;
     constexpr int TM = WL::TM, TN = WL::TN, WM = WL::WM, WN = WL::WN, LDE = BN + 4;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (wave >= NWM * WL::NWN) return;       // loader waves (the 4th of the 3 x 1 layout, waves 4-7 of a 512-thread block) hold no accumulators
-    const int wm = wave / WL::NWN, wn = wave % WL::NWN;
+    if (wave >= 4) return;                   // loader waves (waves 4-7 of a 512-thread block) hold no accumulators
+    const int wm = wave / 2, wn = wave % 2;
     const int r32 = lane & 31, hi = lane >> 5;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -177,7 +174,7 @@ __device__ __forceinline__ void acc_to_lds(ACC &acc, float *ep)   // ACC = acc16
 }
 
 // Epilogue through LDS, block-wide (shared by the tile kernels): see the comment inside.
-template <typename T, typename TO, int BM, int BN, int NWM = 2, int NT = 256, typename ACC>
+template <typename T, typename TO, int BM, int BN, int NT = 256, typename ACC>
 __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
                                               const float *__restrict__ bias, const T *__restrict__ res,
                                               TO *__restrict__ y, long M, int N, int act, long m0, int n0,
@@ -187,7 +184,7 @@ __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
 {
     // y_pre (training, linear_dma_kernel<.., DUAL>): the value BEFORE the activation (acc + bias) also leaves, to a second
     // tensor -- the pre-activation the backward of a GELU needs, without a separate activation launch re-reading it.
-    // colsum / rowstat: LayerNorm of the INPUT rows folded into the GEMM (linear_lean_kernel<.., LNIN>): the accumulator
+    // colsum / rowstat: LayerNorm of the INPUT rows folded into the GEMM (linear_dma_kernel / linear_pc_kernel<.., LNIN>): the accumulator
     // holds x . W' with W' = W * gamma; the normalised product is rstd_m * (acc - mean_m * colsum_n), and beta . W rides
     // in `bias`.  rowstat[row] = (mean, rstd) of the block's rows, in LDS behind the staging tile.
     const int tid = threadIdx.x;
@@ -196,7 +193,7 @@ __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
     // 32-column epilogue wrote 64-byte half lines with 8-byte stores: ~1 TB/s on the output-bound layers)
     constexpr int LDE = BN + 4;
     float *ep = reinterpret_cast<float *>(lds);
-    acc_to_lds<BM, BN, NWM>(acc, ep);
+    acc_to_lds<BM, BN>(acc, ep);
     __syncthreads();
     constexpr int CPL = 8;                 // columns per lane: 16 bytes of a 16-bit output row
     constexpr int LPRW = BN / CPL;         // lanes per row
@@ -435,8 +432,8 @@ __global__ __launch_bounds__(256) void linear_tiled_kernel(const T *__restrict__
 // (B, 384, 384, 128) normalised map is ever written (2 x 151 MB at batch 4) or read back.
 // LayerNorm of the INPUT rows folded into a GEMM (LayerNorm2d -> Linear2d pairs: VSSBlock norm -> in_proj, norm2 -> fc1,
 // vmamba.py:384-396): y = act(LN(x) W^T + b) = act(rstd * (x W'^T - mean * colsum) + t), W' = W * gamma (folded once per
-// weight version), colsum_n = sum_k W'_nk, t = W beta + b.  The block derives mean / rstd of its own 64 rows from the A tiles it stages anyway (sums taken from
-// the staging registers, see lstore); the normalised map is never written or re-read, and the LayerNorm launch disappears.
+// weight version), colsum_n = sum_k W'_nk, t = W beta + b.  The block derives mean / rstd of its own 64 rows from the A tiles it stages anyway (read back
+// from the staged tile, or summed from the MFMA fragments); the normalised map is never written or re-read, and the LayerNorm launch disappears.
 struct LnIn {
     const float *colsum;
     float eps;
@@ -553,17 +550,16 @@ template <> __device__ __forceinline__ float dot2_self<__half>(unsigned v, float
 template <> __device__ __forceinline__ float dot2_ones<float>(unsigned, float acc) { return acc; }
 template <> __device__ __forceinline__ float dot2_self<float>(unsigned, float acc) { return acc; }
 
-template <typename T, typename TO, int BM, int BN, int PF, bool LNHEAD = false, int NWM = 2, bool LNIN = false>
+template <typename T, typename TO, int BM, int BN, int PF, bool LNHEAD = false>
 __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ x, const T *__restrict__ w,
                                                          const float *__restrict__ bias,
                                                          const T *__restrict__ res, TO *__restrict__ y, long M,
                                                          int N, int K, int act, const T *__restrict__ x2, int K1,
-                                                         LnHead hd = LnHead{}, LnIn li = LnIn{nullptr, 0.f})
+                                                         LnHead hd = LnHead{})
 {
     // x2 != nullptr: A = [x (M, K1) | x2 (M, K - K1)], both halves whole K steps (no concatenation in memory)
-    using WL = WaveLayout<BM, BN, NWM>;
+    using WL = WaveLayout<BM, BN>;
     constexpr int TM = WL::TM, TN = WL::TN;
-    static_assert(!LNHEAD || NWM == 2, "the fused head epilogue is written for the 2 x 2 layout");
     constexpr int A_PER_T = BM * (kBK / 8) / 256, B_PER_T = BN * (kBK / 8) / 256;
     constexpr int TILE_BYTES = (BM + BN) * kBK * 2;
     constexpr int EPI_BYTES = BM * (BN + 4) * 4;
@@ -571,12 +567,10 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
     constexpr int LDS_BYTES = 2 * TILE_BYTES > EPI_BYTES ? 2 * TILE_BYTES : EPI_BYTES;
     constexpr int NS = PF + 1;
     static_assert(NS % 2 == 0, "the LDS buffer parity must be a compile-time constant");
-    static_assert(!LNIN || (BM == 64 && NWM == 2 && !LNHEAD), "the input-LayerNorm form is written for 64-row tiles");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES + (LNIN ? BM * 8 : 0)];
+    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const bool compute = wave < NWM * WL::NWN;                     // (3 x 1 layout: the fourth wave only moves data)
-    const int wm = compute ? wave / WL::NWN : 0, wn = wave % WL::NWN;
+    const int wm = wave < 4 ? wave / 2 : 0, wn = wave % 2;   // (wave < 4 always holds; the select keeps the measured instruction stream)
     const int r32 = lane & 31, hi = lane >> 5;
     long m0;
     int n0;
@@ -648,30 +642,12 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
 #pragma unroll
         for (int i = 0; i < B_PER_T; ++i) st.b[i] = __builtin_amdgcn_raw_buffer_load_b128(rb, bg[i], so, 0);
     };
-    // LNIN: sum and sum of squares of the A rows, taken from the staging registers on their way to LDS -- thread t stages
-    // chunk t & 7 of rows (t >> 3) + 32 i at every K step, so the row statistics cost no load of their own (a prologue
-    // that re-read the block's rows moved 1.5x the operand bytes and two dependent round trips: +4..6 us per launch).
-    // v_dot2c_f32_bf16 / _f16: two elements per instruction straight from the packed dword, exact products, fp32 sums.
-    float rs1[A_PER_T], rs2[A_PER_T];
-#pragma unroll
-    for (int i = 0; i < A_PER_T; ++i) rs1[i] = rs2[i] = 0.f;
-    auto lstore = [&](int par, const Stage &st, bool real = true) {
+    auto lstore = [&](int par, const Stage &st) {
         unsigned char *base = lds + par * TILE_BYTES;
 #pragma unroll
         for (int i = 0; i < A_PER_T; ++i) *reinterpret_cast<v4u_t *>(base + al[i]) = st.a[i];
 #pragma unroll
         for (int i = 0; i < B_PER_T; ++i) *reinterpret_cast<v4u_t *>(base + bl[i]) = st.b[i];
-        if constexpr (LNIN) {
-            if (real) {   // (block-uniform) a tile past the end of K holds the next rows' elements: not part of the statistics
-#pragma unroll
-                for (int i = 0; i < A_PER_T; ++i)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        rs1[i] = dot2_ones<T>(st.a[i][e], rs1[i]);
-                        rs2[i] = dot2_self<T>(st.a[i][e], rs2[i]);
-                    }
-            }
-        }
     };
 
     Stage pipe[NS];
@@ -686,7 +662,6 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
         const unsigned char *base = lds + par * TILE_BYTES;
 #pragma unroll
         for (int kk = 0; kk < kBK / 16; ++kk) {
-            if (NWM != 2 && !compute) break;   // wave-uniform
             frag8_t a[TM], b[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const frag8_t *>(base + (ard[i] ^ (unsigned)(kk * 32)));
@@ -697,7 +672,7 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = Mfma<T>::run(b[j], a[i], acc[i][j]);   // swapped: see acc_to_lds
         }
-        lstore(par ^ 1, store_from, kt + 1 < nk);
+        lstore(par ^ 1, store_from);
         __syncthreads();
     };
     constexpr int UNR = 4 * NS;   // hipcc drains vmcnt at the top of every loop trip: long trips
@@ -718,24 +693,8 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
     if constexpr (LNHEAD) {
         static_assert(BN == 128, "one tile = whole 128-channel groups");
         tile_epilogue_ln_head<T, BM>(acc, lds, hd, M, m0, n0);
-    } else if constexpr (LNIN) {
-        float2 *rowstat = reinterpret_cast<float2 *>(lds + LDS_BYTES);   // read by the epilogue behind its own barrier
-#pragma unroll
-        for (int i = 0; i < A_PER_T; ++i) {
-            float s1 = rs1[i], s2 = rs2[i];
-#pragma unroll
-            for (int m = 1; m < 8; m <<= 1) {      // the 8 lanes that stage one row
-                s1 += __shfl_xor(s1, m, 64);
-                s2 += __shfl_xor(s2, m, 64);
-            }
-            const float mean = s1 / (float)K;
-            const float var = fmaxf(s2 / (float)K - mean * mean, 0.f);
-            if ((tid & 7) == 0) rowstat[(tid >> 3) + 32 * i] = make_float2(mean, rsqrtf(var + li.eps));
-        }
-        tile_epilogue<T, TO, BM, BN, NWM>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
-                                          reinterpret_cast<const float2 *>(lds + LDS_BYTES));
     } else {
-        tile_epilogue<T, TO, BM, BN, NWM>(acc, lds, bias, res, y, M, N, act, m0, n0);
+        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0);
     }
 }
 
@@ -943,10 +902,10 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
             const float var = fmaxf(s2 / (float)K - mean * mean, 0.f);
             if ((tid & 7) == 0) rowstat[(tid >> 3) + 32 * i] = make_float2(mean, rsqrtf(var + li.eps));
         }
-        tile_epilogue<T, TO, BM, BN, 2>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
-                                        reinterpret_cast<const float2 *>(lds + LDS_BYTES));
+        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
+                                     reinterpret_cast<const float2 *>(lds + LDS_BYTES));
     } else {
-        tile_epilogue<T, TO, BM, BN, 2>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
+        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
     }
 #endif
 }
@@ -1139,175 +1098,14 @@ __global__ __launch_bounds__(512) void linear_pc_kernel(const T *__restrict__ x,
                 if ((lt & 7) == 0) rowstat[(lt >> 3) + 32 * i] = make_float2(mean, rsqrtf(var + li.eps));
             }
         }
-        tile_epilogue<T, TO, BM, BN, 2, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
-                                             reinterpret_cast<const float2 *>(lds + LDS_BYTES));
+        tile_epilogue<T, TO, BM, BN, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
+                                          reinterpret_cast<const float2 *>(lds + LDS_BYTES));
     } else {
-        tile_epilogue<T, TO, BM, BN, 2, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
+        tile_epilogue<T, TO, BM, BN, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
     }
 #endif
 }
 #undef TRAMBA_DSR128_
-
-// The same staging on a 96 x 64 tile (r03) -- A MEASUREMENT FORM (TRAMBA_TUNE_GEMM_TILE 15), never the library's choice: 3 compute
-// waves of 32 rows x 64 columns each, the fourth wave only fetches and streams the epilogue (WaveLayout NWM = 3).  The idea: if
-// the K loop ran at the CU's L2 -> LDS fill rate (as the weight-gradient GEMM's does), what would count is bytes filled per
-// output row and K step -- 20 KB for 96 rows against 16 KB for 64 -- and the rounds of the chip: M = 2304 is 24 x 96, so the
-// 512-wide GEMMs of the 15-block stage make 192 workgroups = ONE round on 256 CUs where 64 x 64 tiles make 288 = two.
-// Measured (scripts/bench_gemm_tile96.py, profiles/r03h_gemm_tile96.txt): 17.6 against 13.2 us at M = 2304, N = 512, K = 2048,
-// slower on 17 of 21 shapes -- with one workgroup per CU and one wave per SIMD a K step is a serial chain (wait, barrier,
-// 12 LDS reads, 8 MFMAs) that nothing overlaps; the 64 x 64 form keeps 3 workgroups per CU in flight and they hide each other.
-//   * a stage = A 96 x 64 + B 64 x 64 16-bit = 20 KB = twenty 1 KB pieces (8 rows x 128 B); every wave fetches five: wave w the
-//     pieces 5w .. 5w + 4 (A pieces first, then B), so the vmcnt waits count in fives;
-//   * compute waves: 12 ds_read_b128 (A slice, two B slices per 16-deep k slice) and 8 MFMAs per K step.
-#define TRAMBA_DSR128I_(OUT, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(OUT) : "v"(ADDR), "i"(OFF) : "memory")
-
-template <typename T, typename TO, int NSTG, bool DUAL = false>
-__global__ __launch_bounds__(256) void linear_dma96_kernel(const T *__restrict__ x, const T *__restrict__ w,
-                                                          const float *__restrict__ bias, const T *__restrict__ res,
-                                                          TO *__restrict__ y, long M, int N, int K, int act,
-                                                          TO *__restrict__ y_pre = nullptr)
-{
-#if defined(__HIP_DEVICE_COMPILE__)   // (vector-register asm in a kernel template: see ss2d_scan_dma_kernel)
-    constexpr int BM = 96, BN = 64;
-    constexpr int A_BYTES = BM * kBK * 2;                    // 12 KB
-    constexpr int TILE_BYTES = (BM + BN) * kBK * 2;          // 20 KB
-    constexpr int EPI_BYTES = BM * (BN + 4) * 4;
-    constexpr int LDS_BYTES = NSTG * TILE_BYTES > EPI_BYTES ? NSTG * TILE_BYTES : EPI_BYTES;
-    static_assert(NSTG == 2 || NSTG == 3, "stage offsets must fit the 16-bit offset field of ds_read");
-    __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES];
-    typedef __attribute__((address_space(3))) void lds_void;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r32 = lane & 31, hi = lane >> 5;
-    long m0;
-    int n0;
-    {   // XCD-aware tile order (see linear_tiled_kernel)
-        const unsigned nblk = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-        const unsigned q = nblk >> 3, r = nblk & 7, xcd = lin & 7, slot = lin >> 3;
-        const unsigned t = xcd * q + (xcd < r ? xcd : r) + slot;
-        m0 = (long)(t / gridDim.x) * BM;
-        n0 = (int)(t % gridDim.x) * BN;
-    }
-    const int nk = K / kBK;
-    const unsigned rowb = (unsigned)K * 2u;
-    const long mrows = M - m0 < BM ? M - m0 : BM;
-    const int nrows = N - n0 < BN ? N - n0 : BN;
-    const __amdgpu_buffer_rsrc_t rsa = make_rsrc(x + m0 * K, (unsigned)mrows * rowb);
-    const __amdgpu_buffer_rsrc_t rsb = make_rsrc(w + (long)n0 * K, (unsigned)nrows * rowb);
-    // piece p = 5 wave + j: A rows 8p .. 8p + 7 for p < 12, B rows 8 (p - 12) .. after that
-    unsigned voff[5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int p = 5 * wave + j;
-        const int row = (p < 12 ? p : p - 12) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        voff[j] = (unsigned)row * rowb + (unsigned)c * 16u;
-    }
-    unsigned char *mine = lds + 5 * wave * 1024;             // my five pieces inside a stage (the B region follows A's 12 KB)
-    auto issue = [&](int kt, int stg) {
-        const unsigned so = (unsigned)kt * (kBK * 2);
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            if (5 * wave + j < 12)                           // (wave-uniform)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16, voff[j], so,
-                                                         0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsb, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16, voff[j], so,
-                                                         0, 0);
-        }
-    };
-    const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds;
-    const bool computes = wave < 3;
-    unsigned aad[4], bad0[4], bad1[4];
-    {
-        const int ra_ = (computes ? wave : 0) * 32 + r32, rb0_ = r32, rb1_ = 32 + r32;
-        const unsigned a0 = lbase + (unsigned)(ra_ * 128 + ((hi ^ ((ra_ >> 1) & 7)) * 16));
-        const unsigned b0 = lbase + (unsigned)(A_BYTES + rb0_ * 128 + ((hi ^ ((rb0_ >> 1) & 7)) * 16));
-        const unsigned b1 = lbase + (unsigned)(A_BYTES + rb1_ * 128 + ((hi ^ ((rb1_ >> 1) & 7)) * 16));
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            aad[kk] = a0 ^ (unsigned)(kk * 32);      // (rows are 128-byte aligned: the XOR stays inside the row)
-            bad0[kk] = b0 ^ (unsigned)(kk * 32);
-            bad1[kk] = b1 ^ (unsigned)(kk * 32);
-        }
-    }
-    acc16_t acc[1][2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][0][r] = acc[0][1][r] = 0.f;
-
-    constexpr int DEPTH = NSTG - 1;                  // tiles in flight ahead of the one being multiplied
-#pragma unroll
-    for (int t = 0; t < DEPTH; ++t)
-        if (t < nk) issue(t, t);
-    auto kstep = [&](int kt, auto stg_c) {
-        constexpr int STG = decltype(stg_c)::value;
-        constexpr int S = STG * TILE_BYTES;
-        const int later = nk - 1 - kt;
-        if (later >= DEPTH - 1) {
-            if constexpr (DEPTH == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (DEPTH 2: the last step)
-        }
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + DEPTH < nk) issue(kt + DEPTH, (STG + DEPTH) % NSTG);
-        if (computes) {
-            frag8_t a[4], b0[4], b1[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                TRAMBA_DSR128I_(a[kk], aad[kk], S);
-                TRAMBA_DSR128I_(b0[kk], bad0[kk], S);
-                TRAMBA_DSR128I_(b1[kk], bad1[kk], S);
-            }
-            asm volatile("s_waitcnt lgkmcnt(9)" : "+v"(a[0]), "+v"(b0[0]), "+v"(b1[0]) : : "memory");
-            acc[0][0] = Mfma<T>::run(b0[0], a[0], acc[0][0]);
-            acc[0][1] = Mfma<T>::run(b1[0], a[0], acc[0][1]);
-            asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(a[1]), "+v"(b0[1]), "+v"(b1[1]) : : "memory");
-            acc[0][0] = Mfma<T>::run(b0[1], a[1], acc[0][0]);
-            acc[0][1] = Mfma<T>::run(b1[1], a[1], acc[0][1]);
-            asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(a[2]), "+v"(b0[2]), "+v"(b1[2]) : : "memory");
-            acc[0][0] = Mfma<T>::run(b0[2], a[2], acc[0][0]);
-            acc[0][1] = Mfma<T>::run(b1[2], a[2], acc[0][1]);
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[3]), "+v"(b0[3]), "+v"(b1[3]) : : "memory");
-            acc[0][0] = Mfma<T>::run(b0[3], a[3], acc[0][0]);
-            acc[0][1] = Mfma<T>::run(b1[3], a[3], acc[0][1]);
-        }
-    };
-    int kt0 = 0;
-    for (; kt0 + NSTG <= nk; kt0 += NSTG) {
-        kstep(kt0, std::integral_constant<int, 0>{});
-        kstep(kt0 + 1, std::integral_constant<int, 1>{});
-        if constexpr (NSTG > 2) kstep(kt0 + 2, std::integral_constant<int, 2>{});
-    }
-    if (kt0 < nk) kstep(kt0, std::integral_constant<int, 0>{});
-    if constexpr (NSTG > 2) {
-        if (kt0 + 1 < nk) kstep(kt0 + 1, std::integral_constant<int, 1>{});
-    }
-    __syncthreads();                                       // every wave has read the last tile: the epilogue reuses the LDS
-    tile_epilogue<T, TO, BM, BN, 3>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
-#endif
-}
-#undef TRAMBA_DSR128I_
-
-// Tile / staging choice: see launch_tiled.  tile96(): where a 96x64 tile (3 compute waves + 1 loader wave) lands at or
-// under a whole number of rounds of the 256 CUs and 64x64 tiles land just above it (M = 2304, N = 512: 288 -> 192
-// workgroups); a measurement form since r02 (tramba_tune_set(TRAMBA_TUNE_GEMM_TILE, 4)).
-static bool tile96(long m, int n, int k)
-{
-    if (m < 96) return false;
-    const long t64 = ((m + 63) / 64) * ((n + 63) / 64), t96 = ((m + 95) / 96) * ((n + 63) / 64);
-    // rounds of the chip: time ~ rounds x tile height
-    const long r64 = (t64 + 255) / 256, r96 = (t96 + 255) / 256;
-    return k >= 512 && t64 <= 1024 && r96 * 96 < r64 * 64;
-}
-
-// The 96 x 64 LDS-DMA tile (linear_dma96_kernel) is a measurement form: TRAMBA_TUNE_GEMM_TILE 15 runs it wherever it can.
-static bool tile96_dma(long m, int n, int k, int tile_tune)
-{
-    return tile_tune == 15 && m >= 96 && (m + 95) / 96 <= 65535;
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // r04: WEIGHT-STATIONARY form for the tall short-K layers (the 96 x 96 / 48 x 48 stages: M = 9216 .. 73728 rows, K = 128 / 256).
@@ -1315,7 +1113,7 @@ static bool tile96_dma(long m, int n, int k, int tile_tune)
 // re-fetches its 64 x K slice of W, drops its accumulators into an fp32 LDS tile and re-reads them for the store (r03: 51 VALU
 // instructions per MFMA, 25 us for M = 36864, N = 512, K = 128 against a 9 us HBM floor).  Here a workgroup is PERSISTENT and
 // the weights never move again:
-//   * 4 waves own a PANEL of 128 NCW columns (NCW = 4 / 2 / 1 column blocks of 32 per wave, NCW * K <= 512): every wave loads
+//   * 4 waves own a PANEL of 128 NCW columns (NCW column blocks of 32 per wave, NCW * K <= 512; ws_ncw picks 2 / 1): every wave loads
 //     its NCW x K/16 MFMA B-fragments ONCE into registers (<= 128 VGPRs) and keeps them;
 //   * the workgroup then walks its list of 32-row tiles (tile = g + i * G: neighbouring workgroups stream neighbouring rows);
 //     the 32 x K activation tiles travel L2 -> LDS by `buffer_load ... lds` on a 6- / 4-stage ring (K = 128 / 256), every wave
@@ -1653,22 +1451,16 @@ static int pc_rule(long tiles64, int k, int kind)
     return 3;
 }
 
-// Weight-stationary form (linear_ws_kernel, r04): column blocks per wave (4 / 2 / 1), or 0 = not used.  16-bit in and out, K = 128 /
-// 256, N a whole number of 128 NCW-column panels, tall M.  TRAMBA_TUNE_GEMM_TILE 19 forces it wherever it can run, 0 = the
-// library's rule (scripts/bench_gemm_pc.py, profiles/r04_gemm_ws.txt); every other value keeps it off.
-static int ws_ncw(long m, int n, int k, int tile_tune, bool has_res, int kind)
+// Weight-stationary form (linear_ws_kernel, r04): column blocks per wave, or 0 = it cannot run.  16-bit in and out, K = 128 /
+// 256, N a whole number of 128 NCW-column panels.
+static int ws_ncw(long m, int n, int k)
 {
-    if (tile_tune != 19 && tile_tune != 0) return 0;
     if (k != 128 && k != 256) return 0;
     if ((double)m * n * 2.0 >= 2147483648.0 || (double)(m + 32) * k * 2.0 >= 2147483648.0) return 0;
     int ncw = 256 / k;                         // NCW * K <= 256: ~150 VGPRs = 3 workgroups per CU, half the weight prologue per
                                                // workgroup of the NCW * K = 512 form (measured, profiles/r04_gemm_ws.txt)
-    if (tile_tune == 19 && tramba_tune_get(TRAMBA_TUNE_SCAN_W) == 99) ncw = 512 / k;   // (A/B of the wide panel: scripts only)
-    if (has_res && ncw > 2) ncw = 2;
     while (ncw >= 1 && n % (128 * ncw)) ncw >>= 1;
-    if (ncw < 1) return 0;
-    if (tile_tune == 19) return m >= 64 ? ncw : 0;
-    return ws_rule(m, n, k, kind) ? ncw : 0;
+    return ncw;
 }
 
 template <typename T, int K, bool LNIN, bool DUAL, bool RES>
@@ -1677,10 +1469,10 @@ static void launch_ws(int ncw, const void *x, const void *w, const float *bias, 
 {
     const int npanel = n / (128 * ncw);
     const long t32 = (m + 31) / 32;
-    // persistent workgroups, as many as are resident at once (256 CUs x 3 at K = 128 with NCW <= 2, x 2 otherwise), the tiles of a panel dealt
+    // persistent workgroups, as many as are resident at once (256 CUs x 3 at K = 128, x 2 at K = 256), the tiles of a panel dealt
     // round-robin: every workgroup walks tiles g, g + G, ... -- an even split, whereas a grid sized by whole rounds of tiles
     // (384 workgroups for 1152 tiles) left half of the CUs with one workgroup and the other half with two
-    const long resident = 256L * ((K == 128 && ncw <= 2) ? 3 : 2);     // (by registers and LDS: 51 KB / 67 KB per workgroup)
+    const long resident = 256L * (K == 128 ? 3 : 2);     // (by registers and LDS: 51 KB / 67 KB per workgroup)
     long gt = resident / npanel;
     if (gt > t32) gt = t32;
     if (gt < 1) gt = 1;
@@ -1689,11 +1481,9 @@ static void launch_ws(int ncw, const void *x, const void *w, const float *bias, 
     hipLaunchKernelGGL((linear_ws_kernel<T, K, NCW_, LNIN, DUAL, RES>), grid, block, 0, s, (const T *)x, (const T *)w, bias, \
                        (const T *)res, (T *)y, m, n, act, li, (T *)y_pre, npanel, (int)gt)
     if constexpr (K == 128) {
-        if (ncw == 4) { if constexpr (!RES) { WS_(4); } }
-        else if (ncw == 2) { WS_(2); }
-        else { WS_(1); }
-    } else {
         if (ncw == 2) { WS_(2); } else { WS_(1); }
+    } else {
+        WS_(1);                                // (ws_ncw: NCW * K <= 256)
     }
 #undef WS_
 }
@@ -1711,110 +1501,133 @@ static void launch_ws_k(int ncw, const void *x, const void *w, const float *bias
     }
 }
 
-// Producer / consumer form (linear_pc_kernel, r04): 0 = not used, else its LDS stage count.  TRAMBA_TUNE_GEMM_TILE 16 / 17 force it
-// on 3 / 4 stages wherever the LDS-DMA kernel could run, 18 forbids it; the library's own rule (tune 0) is fitted to
-// scripts/bench_gemm_pc.py (profiles/r04_gemm_pc.txt).
-static int pc_stages(long m, int n, int k, int tile_tune, int kind)
-{
-    if (tile_tune == 16) return 3;
-    if (tile_tune == 17) return 4;
-    if (tile_tune != 0 && tile_tune != 19) return 0;
-    const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
-    return pc_rule(tiles64, k, kind);
-}
-
 // K up to which a grid of >= 1024 tiles runs linear_dma_kernel on 2 LDS stages (5 workgroups per CU instead of 3):
 // scripts/bench_gemm_stages.py, r03 -- -12 % at M = 36864 / 73728, N = 512, K = 128, -3..7 % on the other K <= 256 shapes,
 // +5 % at K = 512
 constexpr int DMA_SHORT_K = 256;
 
-template <typename T, typename TO, bool CONV = false>
-static void launch_tiled(const void *x, const void *w, const float *bias, const void *res, void *y, long m, int n,
-                         int k, int act, hipStream_t s, ConvGeom cg = ConvGeom{0, 0, 0, 0, 0},
-                         const void *x2 = nullptr, int k1 = 0)
+// ---------------------------------------------------------------------------------------------------------------------
+// The form planner of the 16-bit GEMM entries: gemm_plan picks the kernel, launch_gemm launches it.
+enum GemmKind { GEMM_PLAIN = 0, GEMM_LN = 1, GEMM_DUAL = 2, GEMM_TWO_SRC, GEMM_CONV };   // PLAIN / LN / DUAL = `kind` of ws_rule, pc_rule
+enum class GemmForm {
+    WS,                           // linear_ws_kernel
+    PC3, PC4,                     // linear_pc_kernel, 3 / 4 LDS stages
+    DMA2, DMA3, DMA4,             // linear_dma_kernel, 2 / 3 / 4 LDS stages
+    LEAN,                         // linear_lean_kernel 64 x 64 (register-staged: the two-source A operand)
+    TILED128, TILED64, TILED64_PF3   // linear_tiled_kernel (ragged K, implicit-GEMM convolution)
+};
+struct GemmPlan {
+    GemmForm form;
+    int ncw;                      // WS: column blocks per wave
+};
+
+// TRAMBA_TUNE_GEMM_TILE (the only place it is read) forces a form on the plain, LayerNorm-folded and dual-output entries
+// wherever the LDS-DMA kernels can run: 7 = DMA4 (plain entry only: the other two have no 4-stage LDS-DMA kernel and keep their
+// rule), 13 / 14 = DMA2 / DMA3, 16 / 17 = PC3 / PC4, 18 = the rule without the PC and WS forms (the r03 kernels), 19 = WS
+// wherever it can run, else the rule.  0 = the rule.
+static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool same_dtype)
 {
-    const long big = ((m + 127) / 128) * ((n + 127) / 128);
-    // lean kernel: whole 64-deep K steps, and a 64-row operand panel within 32-bit byte offsets
-    const bool lean_ok = k % 64 == 0 && (double)k * 2.0 * 128.0 < 2147483648.0;
-    const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
-    // Plain GEMMs with K % 64 == 0 (every 1x1 convolution of the model): the LDS-DMA staged 64x64 kernel.  Measured back to
-    // back in one process on the model's shapes at batch 4 and 8 (scripts/bench_gemm_tiles.py): 14 % / 9 % less time per
-    // pass than the register-staged 64x64 kernel (2-stage ring, 82 VGPRs), faster on every shape (19.4 -> 13.0 us at
-    // M = 2304, N = 512, K = 2048).  Register-staged forms for comparison, through TRAMBA_TUNE_GEMM_TILE: 1 = 64x64 (the
-    // default until r02; still used for the two-source A operand), 2 = 128x128 (1-2 resident blocks: 1.3-2x slower),
-    // 3 = 128x64, 4 = 96x64 where it saves a round of the chip, 5 = 64x64 on a 4-stage ring.
-    const int tile_tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
-    // (4 stages = 3 tiles in flight where at most one block lands on a CU and K is long: nothing else hides the load latency
-    //  there -- M = 576, N = 1024, K = 4096: 27 -> 22 us with operands that are not cache-resident; 8 stages = one block per
-    //  CU by LDS, was measured slower on every shape and is not built)
-    const bool dma_deep = tile_tune == 7 || ((tile_tune == 0 || tile_tune == 18 || tile_tune == 19) && tiles64 <= 256 && k >= 1024);
-    if constexpr (!CONV && std::is_same<T, TO>::value) {
-        const int ncw = (lean_ok && !x2) ? ws_ncw(m, n, k, tile_tune, res != nullptr, 0) : 0;
-        if (ncw && (act == TRAMBA_ACT_NONE || act == TRAMBA_ACT_GELU || act == TRAMBA_ACT_SILU)) {
-            launch_ws_k<T, false, false>(ncw, x, w, bias, res, y, m, n, k, act, LnIn{nullptr, 0.f}, nullptr, s);
-            return;
-        }
+    if (kind == GEMM_TWO_SRC) return {GemmForm::LEAN, 0};
+    // whole 64-deep K steps, and a 64-row operand panel within 32-bit byte offsets
+    if (kind == GEMM_CONV || k % 64 != 0 || (double)k * 2.0 * 128.0 >= 2147483648.0) {
+        const long big = ((m + 127) / 128) * ((n + 127) / 128);
+        if (big >= 2048 && k >= 1024) return {GemmForm::TILED128, 0};
+        return {k <= 128 ? GemmForm::TILED64 : GemmForm::TILED64_PF3, 0};   // 1-2 K steps: a 2-stage ring, no padded dummy steps
     }
-    if (!CONV && lean_ok && !x2 && tile96_dma(m, n, k, tile_tune)) {
-        dim3 grid((n + 63) / 64, (unsigned)((m + 95) / 96)), block(256);
-        hipLaunchKernelGGL((linear_dma96_kernel<T, TO, 3>), grid, block, 0, s, (const T *)x, (const T *)w, bias, (const T *)res,
-                           (TO *)y, m, n, k, act);
-    } else if (!CONV && lean_ok && !x2 && (tile_tune == 0 || tile_tune == 6 || tile_tune == 7 || tile_tune == 13 || tile_tune == 14 ||
-                                           tile_tune == 15 || tile_tune == 16 || tile_tune == 17 || tile_tune == 18 || tile_tune == 19)) {
-        dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-        // short K (<= 4 steps) on a grid of many tiles: the launch is prologue + epilogue, and what it needs is workgroups in
-        // flight -- 2 stages = 32 KB of LDS = 5 per CU instead of 3 (TRAMBA_TUNE_GEMM_TILE 13 forces it, 14 forbids it)
-        const bool dma_short = tile_tune == 13 || ((tile_tune == 0 || tile_tune == 18 || tile_tune == 19) && DMA_SHORT_K > 0 && k <= DMA_SHORT_K && tiles64 >= 1024);
-        const int pc = pc_stages(m, n, k, tile_tune, 0);
-        if (pc == 3)
-            hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3>), grid, dim3(512), 0, s, (const T *)x, (const T *)w, bias,
-                               (const T *)res, (TO *)y, m, n, k, act);
-        else if (pc == 4)
-            hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4>), grid, dim3(512), 0, s, (const T *)x, (const T *)w, bias,
-                               (const T *)res, (TO *)y, m, n, k, act);
-        else if (dma_short)
-            hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                               (const T *)res, (TO *)y, m, n, k, act);
-        else if (dma_deep)
-            hipLaunchKernelGGL((linear_dma_kernel<T, TO, 4>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                               (const T *)res, (TO *)y, m, n, k, act);
-        else
-            hipLaunchKernelGGL((linear_dma_kernel<T, TO, 3>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                               (const T *)res, (TO *)y, m, n, k, act);
-    } else if (!CONV && lean_ok && tile_tune == 2) {
-        dim3 grid((n + 127) / 128, (unsigned)((m + 127) / 128)), block(256);
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 128, 128, 1>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                           (const T *)res, (TO *)y, m, n, k, act, (const T *)x2, k1);
-    } else if (!CONV && lean_ok && tile_tune == 3) {
-        dim3 grid((n + 63) / 64, (unsigned)((m + 127) / 128)), block(256);
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 128, 64, 1>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                           (const T *)res, (TO *)y, m, n, k, act, (const T *)x2, k1);
-    } else if (!CONV && lean_ok && tile_tune == 4 && tile96(m, n, k)) {
-        // 96x64 tiles, 3 compute waves + 1 loader wave: the tile count drops under one round of the chip
-        dim3 grid((n + 63) / 64, (unsigned)((m + 95) / 96)), block(256);
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 96, 64, 1, false, 3>), grid, block, 0, s, (const T *)x, (const T *)w,
-                           bias, (const T *)res, (TO *)y, m, n, k, act, (const T *)x2, k1);
-    } else if (!CONV && lean_ok && tile_tune == 5) {
-        // 4 stages (168 VGPRs): long K on a grid of about one block per CU
-        dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 3>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                           (const T *)res, (TO *)y, m, n, k, act, (const T *)x2, k1);
-    } else if (!CONV && lean_ok) {
-        dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 1>), grid, block, 0, s, (const T *)x, (const T *)w, bias,
-                           (const T *)res, (TO *)y, m, n, k, act, (const T *)x2, k1);
-    } else if (!x2 && big >= 2048 && k >= 1024) {
-        dim3 grid((n + 127) / 128, (unsigned)((m + 127) / 128)), block(256);
-        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 128, 128, 2, CONV>), grid, block, 0, s, (const T *)x,
-                           (const T *)w, bias, (const T *)res, (TO *)y, m, n, k, act, cg);
-    } else if (k <= 128) {  // 1-2 K steps: a 2-stage ring, no padded dummy steps
-        dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 64, 64, 1, CONV>), grid, block, 0, s, (const T *)x,
-                           (const T *)w, bias, (const T *)res, (TO *)y, m, n, k, act, cg);
+    int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
+    if (tune == 7 && kind != GEMM_PLAIN) tune = 0;
+    if (tune == 0 || tune == 19) {
+        const bool ws_act = act == TRAMBA_ACT_NONE || act == TRAMBA_ACT_GELU || act == TRAMBA_ACT_SILU;
+        const int ncw = same_dtype && ws_act ? ws_ncw(m, n, k) : 0;
+        if (ncw && (tune == 19 ? m >= 64 : ws_rule(m, n, k, kind))) return {GemmForm::WS, ncw};
+    }
+    switch (tune) {
+    case 7: return {GemmForm::DMA4, 0};
+    case 13: return {GemmForm::DMA2, 0};
+    case 14: return {GemmForm::DMA3, 0};
+    case 16: return {GemmForm::PC3, 0};
+    case 17: return {GemmForm::PC4, 0};
+    }
+    const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
+    const int pc = tune == 18 ? 0 : pc_rule(tiles64, k, kind);
+    if (pc) return {pc == 4 ? GemmForm::PC4 : GemmForm::PC3, 0};
+    // short K (<= 4 steps) on a grid of many tiles: the launch is prologue + epilogue, and what it needs is workgroups in flight
+    if (k <= DMA_SHORT_K && tiles64 >= 1024) return {GemmForm::DMA2, 0};
+    // 4 stages = 3 tiles in flight where at most one block lands on a CU and K is long: nothing else hides the load latency
+    // there -- M = 576, N = 1024, K = 4096: 27 -> 22 us with operands that are not cache-resident; 8 stages = one block per
+    // CU by LDS, was measured slower on every shape and is not built
+    if (kind == GEMM_PLAIN && tiles64 <= 256 && k >= 1024) return {GemmForm::DMA4, 0};
+    return {GemmForm::DMA3, 0};
+}
+
+struct GemmArgs {
+    const void *x, *w;
+    const float *bias;
+    const void *res;
+    void *y;
+    long m;
+    int n, k, act;
+    LnIn li{nullptr, 0.f};        // LayerNorm-folded entry
+    void *y_pre = nullptr;        // dual-output entry: the pre-activation
+    const void *x2 = nullptr;     // two-source entry: A = [x (m, k1) | x2 (m, k - k1)]
+    int k1 = 0;
+    ConvGeom cg{0, 0, 0, 0, 0};   // implicit-GEMM convolution
+};
+
+template <typename T, typename TO, bool LNIN = false, bool DUAL = false, bool CONV = false>
+static void launch_gemm(const GemmPlan &p, const GemmArgs &a, hipStream_t s)
+{
+    const T *x = (const T *)a.x, *w = (const T *)a.w, *res = (const T *)a.res;
+    TO *y = (TO *)a.y, *y_pre = (TO *)a.y_pre;
+    const long m = a.m;
+    const int n = a.n, k = a.k, act = a.act;
+    const dim3 g64((n + 63) / 64, (unsigned)((m + 63) / 64)), g128((n + 127) / 128, (unsigned)((m + 127) / 128));
+    switch (p.form) {
+    case GemmForm::WS:
+        launch_ws_k<T, LNIN, DUAL>(p.ncw, a.x, a.w, a.bias, a.res, a.y, m, n, k, act, a.li, a.y_pre, s);
+        break;
+    case GemmForm::PC3:
+        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        break;
+    case GemmForm::PC4:
+        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        break;
+    case GemmForm::DMA2:
+        hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2, LNIN, DUAL>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        break;
+    case GemmForm::DMA3:
+        hipLaunchKernelGGL((linear_dma_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        break;
+    case GemmForm::DMA4:   // (gemm_plan: plain entry only)
+        if constexpr (!LNIN && !DUAL)
+            hipLaunchKernelGGL((linear_dma_kernel<T, TO, 4>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        break;
+    case GemmForm::LEAN:
+        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 1>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act,
+                           (const T *)a.x2, a.k1);
+        break;
+    case GemmForm::TILED128:
+        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 128, 128, 2, CONV>), g128, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.cg);
+        break;
+    case GemmForm::TILED64:
+        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 64, 64, 1, CONV>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.cg);
+        break;
+    case GemmForm::TILED64_PF3:
+        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 64, 64, 3, CONV>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.cg);
+        break;
+    }
+}
+
+// 16-bit operands of `dtype`, output of `dtype` or f32
+template <bool LNIN = false>
+static void launch_gemm16(const GemmPlan &p, const GemmArgs &a, int dtype, int out_dtype, hipStream_t s)
+{
+    if (dtype == TRAMBA_BF16) {
+        if (out_dtype == TRAMBA_F32) launch_gemm<__hip_bfloat16, float, LNIN>(p, a, s);
+        else launch_gemm<__hip_bfloat16, __hip_bfloat16, LNIN>(p, a, s);
     } else {
-        dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-        hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 64, 64, 3, CONV>), grid, block, 0, s, (const T *)x,
-                           (const T *)w, bias, (const T *)res, (TO *)y, m, n, k, act, cg);
+        if (out_dtype == TRAMBA_F32) launch_gemm<__half, float, LNIN>(p, a, s);
+        else launch_gemm<__half, __half, LNIN>(p, a, s);
     }
 }
 
@@ -1885,13 +1698,8 @@ extern "C" int tramba_linear_cl(const void *x, const void *w, const float *bias,
     const bool tiled = vec && dtype != TRAMBA_F32 && aligned16(y) && (residual == nullptr || aligned16(residual)) &&
                        (m + 63) / 64 <= 65535;
     if (tiled) {
-        if (dtype == TRAMBA_BF16) {
-            if (out_dtype == TRAMBA_F32) launch_tiled<__hip_bfloat16, float>(x, w, bias, residual, y, m, n, k, act, s);
-            else launch_tiled<__hip_bfloat16, __hip_bfloat16>(x, w, bias, residual, y, m, n, k, act, s);
-        } else {
-            if (out_dtype == TRAMBA_F32) launch_tiled<__half, float>(x, w, bias, residual, y, m, n, k, act, s);
-            else launch_tiled<__half, __half>(x, w, bias, residual, y, m, n, k, act, s);
-        }
+        launch_gemm16(gemm_plan(GEMM_PLAIN, m, n, k, act, out_dtype == dtype), GemmArgs{x, w, bias, residual, y, m, n, k, act},
+                      dtype, out_dtype, s);
         TRAMBA_LAUNCH_CHECK();
         return TRAMBA_OK;
     }
@@ -1936,46 +1744,9 @@ extern "C" int tramba_linear_ln_cl(const void *x, const void *w_folded, const fl
                  "linear_ln_cl: tensors must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(TRAMBA_PROF_GEMM, s, 2.0 * (double)m * n * k);
-    const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
-    const int tile_tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
-    const bool deep = tile_tune == 5;                    // 4-stage register ring: measurement only (see launch_tiled)
-    const bool dma = tile_tune == 0 || tile_tune == 6 || tile_tune == 15 || tile_tune >= 16;   // the LDS-DMA staged kernel (default)
-    const int pc = pc_stages(m, n, k, tile_tune, 1);
-    dim3 grid((n + 63) / 64, (unsigned)((m + 63) / 64)), block(256);
-    const LnIn li{colsum, eps};
-    const bool dma_short = dma && (tile_tune == 0 || tile_tune >= 18) && k <= DMA_SHORT_K && ((m + 63) / 64) * ((n + 63) / 64) >= 1024;   // (launch_tiled)
-#define LNIN_(T, TO)                                                                                                     \
-    if (pc == 3)                                                                                                         \
-        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, true>), grid, dim3(512), 0, s, (const T *)x, (const T *)w_folded, bias, \
-                           (const T *)residual, (TO *)y, m, n, k, act, li);                                              \
-    else if (pc == 4)                                                                                                    \
-        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, true>), grid, dim3(512), 0, s, (const T *)x, (const T *)w_folded, bias, \
-                           (const T *)residual, (TO *)y, m, n, k, act, li);                                              \
-    else if (dma_short)                                                                                                       \
-        hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2, true>), grid, block, 0, s, (const T *)x, (const T *)w_folded, bias, \
-                           (const T *)residual, (TO *)y, m, n, k, act, li);                                              \
-    else if (dma)                                                                                                        \
-        hipLaunchKernelGGL((linear_dma_kernel<T, TO, 3, true>), grid, block, 0, s, (const T *)x, (const T *)w_folded, bias, \
-                           (const T *)residual, (TO *)y, m, n, k, act, li);                                              \
-    else if (deep)                                                                                                            \
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 3, false, 2, true>), grid, block, 0, s, (const T *)x,       \
-                           (const T *)w_folded, bias, (const T *)residual, (TO *)y, m, n, k, act, (const T *)nullptr, 0,  \
-                           LnHead{}, li);                                                                                \
-    else                                                                                                                 \
-        hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 1, false, 2, true>), grid, block, 0, s, (const T *)x,       \
-                           (const T *)w_folded, bias, (const T *)residual, (TO *)y, m, n, k, act, (const T *)nullptr, 0,  \
-                           LnHead{}, li)
-    const int ncw = out_dtype == dtype && (act == TRAMBA_ACT_NONE || act == TRAMBA_ACT_GELU || act == TRAMBA_ACT_SILU)
-                        ? ws_ncw(m, n, k, tile_tune, residual != nullptr, 1) : 0;
-    if (ncw) {
-        if (dtype == TRAMBA_BF16) launch_ws_k<__hip_bfloat16, true, false>(ncw, x, w_folded, bias, residual, y, m, n, k, act, li, nullptr, s);
-        else launch_ws_k<__half, true, false>(ncw, x, w_folded, bias, residual, y, m, n, k, act, li, nullptr, s);
-    } else if (dtype == TRAMBA_BF16) {
-        if (out_dtype == TRAMBA_F32) { LNIN_(__hip_bfloat16, float); } else { LNIN_(__hip_bfloat16, __hip_bfloat16); }
-    } else {
-        if (out_dtype == TRAMBA_F32) { LNIN_(__half, float); } else { LNIN_(__half, __half); }
-    }
-#undef LNIN_
+    GemmArgs a{x, w_folded, bias, residual, y, m, n, k, act};
+    a.li = LnIn{colsum, eps};
+    launch_gemm16<true>(gemm_plan(GEMM_LN, m, n, k, act, out_dtype == dtype), a, dtype, out_dtype, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -1994,14 +1765,10 @@ extern "C" int tramba_linear2_cl(const void *x1, const void *x2, int k1, const v
     TRAMBA_CHECK((m + 63) / 64 <= 65535 && (double)k * 2.0 * 128.0 < 2147483648.0, "linear2_cl: shape exceeds this build's limits");
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(TRAMBA_PROF_GEMM, s, 2.0 * (double)m * n * k);
-    const ConvGeom nocg{0, 0, 0, 0, 0};
-    if (dtype == TRAMBA_BF16) {
-        if (out_dtype == TRAMBA_F32) launch_tiled<__hip_bfloat16, float>(x1, w, bias, residual, y, m, n, k, act, s, nocg, x2, k1);
-        else launch_tiled<__hip_bfloat16, __hip_bfloat16>(x1, w, bias, residual, y, m, n, k, act, s, nocg, x2, k1);
-    } else {
-        if (out_dtype == TRAMBA_F32) launch_tiled<__half, float>(x1, w, bias, residual, y, m, n, k, act, s, nocg, x2, k1);
-        else launch_tiled<__half, __half>(x1, w, bias, residual, y, m, n, k, act, s, nocg, x2, k1);
-    }
+    GemmArgs a{x1, w, bias, residual, y, m, n, k, act};
+    a.x2 = x2;
+    a.k1 = k1;
+    launch_gemm16(gemm_plan(GEMM_TWO_SRC, m, n, k, act, out_dtype == dtype), a, dtype, out_dtype, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -2047,10 +1814,11 @@ extern "C" int tramba_conv3x3s2_cl(const void *x, const void *w, const float *bi
     const long m = (long)batch * cg.hout * cg.wout;
     TRAMBA_CHECK((m + 63) / 64 <= 65535, "conv3x3s2_cl: too many output pixels");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == TRAMBA_BF16)
-        launch_tiled<__hip_bfloat16, __hip_bfloat16, true>(x, w, bias, nullptr, y, m, cout, 9 * cin, TRAMBA_ACT_NONE, s, cg);
-    else
-        launch_tiled<__half, __half, true>(x, w, bias, nullptr, y, m, cout, 9 * cin, TRAMBA_ACT_NONE, s, cg);
+    const GemmPlan p = gemm_plan(GEMM_CONV, m, cout, 9 * cin, TRAMBA_ACT_NONE, true);
+    GemmArgs a{x, w, bias, nullptr, y, m, cout, 9 * cin, TRAMBA_ACT_NONE};
+    a.cg = cg;
+    if (dtype == TRAMBA_BF16) launch_gemm<__hip_bfloat16, __hip_bfloat16, false, false, true>(p, a, s);
+    else launch_gemm<__half, __half, false, false, true>(p, a, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -2067,34 +1835,11 @@ extern "C" int tramba_linear_dual_cl(const void *x, const void *w, const float *
     TRAMBA_CHECK(aligned16(x) && aligned16(w) && aligned16(y_pre) && aligned16(y_act), "linear_dual_cl: 16-byte alignment");
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(TRAMBA_PROF_GEMM, s, 2.0 * (double)m * n * k);
-    const bool dma96 = tile96_dma(m, n, k, tramba_tune_get(TRAMBA_TUNE_GEMM_TILE));
-    dim3 grid((n + 63) / 64, (unsigned)(dma96 ? (m + 95) / 96 : (m + 63) / 64)), block(256);
-    const int tune_ = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
-    const bool dma_short = (tune_ == 0 || tune_ >= 18) && k <= DMA_SHORT_K && ((m + 63) / 64) * ((n + 63) / 64) >= 1024;   // (launch_tiled)
-    const int pc = pc_stages(m, n, k, tune_, 2);
-#define DUAL_(T, S_)                                                                                                    \
-    hipLaunchKernelGGL((linear_dma_kernel<T, T, S_, false, true>), grid, block, 0, s, (const T *)x, (const T *)w, bias,   \
-                       (const T *)nullptr, (T *)y_act, m, n, k, act, LnIn{nullptr, 0.f}, (T *)y_pre)
-#define DUAL96_(T)                                                                                                      \
-    hipLaunchKernelGGL((linear_dma96_kernel<T, T, 3, true>), grid, block, 0, s, (const T *)x, (const T *)w, bias,         \
-                       (const T *)nullptr, (T *)y_act, m, n, k, act, (T *)y_pre)
-#define DUALPC_(T, S_)                                                                                                  \
-    hipLaunchKernelGGL((linear_pc_kernel<T, T, S_, false, true>), grid, dim3(512), 0, s, (const T *)x, (const T *)w, bias, \
-                       (const T *)nullptr, (T *)y_act, m, n, k, act, LnIn{nullptr, 0.f}, (T *)y_pre)
-    const int ncw = ws_ncw(m, n, k, tune_, false, 2);
-    if (ncw) {
-        if (dtype == TRAMBA_BF16) launch_ws_k<__hip_bfloat16, false, true>(ncw, x, w, bias, nullptr, y_act, m, n, k, act, LnIn{nullptr, 0.f}, y_pre, s);
-        else launch_ws_k<__half, false, true>(ncw, x, w, bias, nullptr, y_act, m, n, k, act, LnIn{nullptr, 0.f}, y_pre, s);
-    } else if (dtype == TRAMBA_BF16) {
-        if (dma96) DUAL96_(__hip_bfloat16); else if (pc == 3) DUALPC_(__hip_bfloat16, 3); else if (pc == 4) DUALPC_(__hip_bfloat16, 4);
-        else if (dma_short) DUAL_(__hip_bfloat16, 2); else DUAL_(__hip_bfloat16, 3);
-    } else {
-        if (dma96) DUAL96_(__half); else if (pc == 3) DUALPC_(__half, 3); else if (pc == 4) DUALPC_(__half, 4);
-        else if (dma_short) DUAL_(__half, 2); else DUAL_(__half, 3);
-    }
-#undef DUALPC_
-#undef DUAL_
-#undef DUAL96_
+    const GemmPlan p = gemm_plan(GEMM_DUAL, m, n, k, act, true);
+    GemmArgs a{x, w, bias, nullptr, y_act, m, n, k, act};
+    a.y_pre = y_pre;
+    if (dtype == TRAMBA_BF16) launch_gemm<__hip_bfloat16, __hip_bfloat16, false, true>(p, a, s);
+    else launch_gemm<__half, __half, false, true>(p, a, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -113,12 +113,17 @@ extern "C" int tramba_device_error(void)
 // 5: the step's ends and batched launches (sod_loss_*, adam_step, multi_sum / multi_sum_strided, wgrad_parts_cl,
 //    dw_pack_multi / dw_unpack_grad_multi, shuffle_norm_head_bwd_cl)
 // 6: tramba_device_error, TRAMBA_TUNE_MAILBOX_SKIP (r04)
+// 7: tramba_dwconv_wgrad_parts takes C; TRAMBA_TUNE_DW_FORM / TRAMBA_TUNE_DW_ROWS (r04)
 extern "C" int tramba_abi_version(void) { return 7; }
 
 static int g_tune[TRAMBA_TUNE_COUNT] = {0};
 extern "C" int tramba_tune_set(int knob, int value)
 {
     TRAMBA_CHECK(knob >= 0 && knob < TRAMBA_TUNE_COUNT, "tune knob %d out of range", knob);
+    // retired measurement forms: refused, so that an old script fails instead of timing the default (their source is in history)
+    TRAMBA_CHECK(knob != 5, "tune knob 5 (the weight-gradient form) is retired");
+    TRAMBA_CHECK(knob != TRAMBA_TUNE_GEMM_TILE || value == 0 || value == 7 || value == 13 || value == 14 || (value >= 16 && value <= 19),
+                 "TRAMBA_TUNE_GEMM_TILE %d is retired or unknown (kept: 0, 7, 13, 14, 16-19)", value);
     g_tune[knob] = value;
     return TRAMBA_OK;
 }

@@ -9,9 +9,8 @@
 //    An MFMA fragment wants 8 consecutive k (= tokens) of one channel, the tensors are channel-contiguous: the 32-token
 //    tiles are staged in LDS as they lie in memory ([token][channel], coalesced 16-byte rows) and read back TRANSPOSED
 //    with ds_read_b64_tr_b16 (4 tokens x 16 channels per 16-lane group) -- no transposed copy of an activation is ever
-//    written.  Row stride 320 B (= 16 banks past a multiple of 64): the four token rows and the two channel halves a
-//    32-lane group touches fall on disjoint banks.
-//    The bias gradient (column sums of gy) rides along: the threads that stage gy add what they load.
+//    written.
+//    The bias gradient (column sums of gy) rides along, read back from the staged gy tiles.
 //    `groups` / `nbatch` + strides let one launch serve the per-direction contractions of the SS2D backward, whose
 //    operands are (B, K, L, C) tensors: group g, batch b, token t sits at base + b*bs + g*gs + t*ld.
 // 2. rows_gemm: y[z][t][0..N) = x[z][t][:] . w[z % groups][n][:], N <= 64, fp32 rows written with a row stride -- the
@@ -48,7 +47,6 @@ template <> __device__ __forceinline__ acc16 mfma16<__half>(frag8s a, frag8s b, 
 
 constexpr int kWgTok = 32;            // tokens per step
 constexpr int kWgTile = 128;          // output tile edge (channels of gy / channels of x)
-constexpr int kWgRow = 320;           // LDS bytes per staged token row (256 data + 64 pad)
 
 struct WgradArgs {
     const void *gy, *x;
@@ -60,149 +58,9 @@ struct WgradArgs {
     int want_bias;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs a)
-{
-    __shared__ __attribute__((aligned(16))) unsigned char lds[2][2][kWgTok * kWgRow];   // [buffer][gy | x]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wn = wv >> 1, wk = wv & 1;                      // wave tile: 64 (n) x 64 (k)
-    // XCD-aware work order (xcd_work_item, common.h): the tiles of ONE token chunk re-read the same gy / x rows -- K / 128
-    // and N / 128 times.  In launch order consecutive workgroups land on different XCDs, so every chunk was fetched by all
-    // eight L2s and re-read through the fabric (the big layers moved ~150 MB per launch at ~5.4 TB/s: that, not the matrix
-    // cores, set their 350 TFLOP/s).  Remapped, an XCD walks k tile -> n tile -> chunk: a chunk's tiles run side by side on
-    // one XCD and its operand rows (<= 2.5 MB) are served by that XCD's L2.
-    unsigned bx_, by_, bz_;
-    xcd_work_item(bx_, by_, bz_);
-    const int bx = (int)bx_, by = (int)by_, bz = (int)bz_;
-    const int n0 = by * kWgTile, k0 = bx * kWgTile;
-    const int per = a.nbatch * a.nsplit;
-    const int g = bz / per, zz = bz % per;
-    const int b = zz / a.nsplit, sp = zz % a.nsplit;
-    const int t0 = sp * a.mchunk;
-    const int t1 = t0 + a.mchunk < a.M ? t0 + a.mchunk : a.M;
-    const T *gyb = (const T *)a.gy + (long)b * a.gy_bs + (long)g * a.gy_gs;
-    const T *xb = (const T *)a.x + (long)b * a.x_bs + (long)g * a.x_gs;
-    // descriptors over the whole (group, batch) operand: row t at t*ld elements
-    const __amdgpu_buffer_rsrc_t rg = make_rsrc(gyb, (unsigned)(((long)(a.M - 1) * a.gy_ld + a.N) * (long)sizeof(T)));
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(xb, (unsigned)(((long)(a.M - 1) * a.x_ld + a.K) * (long)sizeof(T)));
-
-    // staging: a 32 x 128 tile = 512 chunks of 16 bytes; thread t moves chunks t and t + 256: token tid/16 (+16),
-    // channels 8*(tid%16) .. +7
-    const int stok = tid >> 4, sch = (tid & 15) * 8;
-    const bool gcol = n0 + sch < a.N, xcol = k0 + sch < a.K;     // N, K are multiples of 8: a chunk is in or out whole
-    auto goff = [&](int tok, bool col, int c0, int ld) -> unsigned {
-        return (col && tok < t1) ? (unsigned)(((long)tok * ld + c0) * (long)sizeof(T)) : kOutOfRange;
-    };
-    v4u32 rgy[2], rxx[2];
-    auto fetch = [&](int ts) {   // ts = first token of the step
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int tok = ts + stok + 16 * i;
-            rgy[i] = __builtin_amdgcn_raw_buffer_load_b128(rg, goff(tok, gcol, n0 + sch, a.gy_ld), 0, 0);
-            rxx[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, goff(tok, xcol, k0 + sch, a.x_ld), 0, 0);
-        }
-    };
-    float bsum[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bsum[j] = 0.f;
-    const bool do_bias = (a.want_bias & 1) && bx == 0;
-    auto stash = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int off = (stok + 16 * i) * kWgRow + sch * 2;
-            *reinterpret_cast<v4u32 *>(&lds[buf][0][off]) = rgy[i];
-            *reinterpret_cast<v4u32 *>(&lds[buf][1][off]) = rxx[i];
-            if (do_bias) {
-                const Pack<T, 8> pk = __builtin_bit_cast(Pack<T, 8>, rgy[i]);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) bsum[j] += Cvt<T>::to_f(pk.v[j]);
-            }
-        }
-    };
-
-    // transposed fragment reads.  16-lane group gq = lane>>4: channels 16*(gq&1) .. +15 of a 32-channel block, tokens
-    // 8*(gq>>1) + 4u .. +3; lane 4q+p of the group supplies the address of token row q, channels 4p .. 4p+3 and receives
-    // channel (lane&15), the 4 tokens
-    const int li = lane & 15, q = li >> 2, p = li & 3, gq = lane >> 4;
-    const unsigned trbase = (unsigned)((8 * (gq >> 1) + q) * kWgRow + (16 * (gq & 1) + 4 * p) * 2);
-    auto frag = [&](const unsigned char *tile, int ks, int cblk) -> frag8s {   // cblk: first channel of the 32-block
-        const unsigned char *pa = tile + trbase + ks * 16 * kWgRow + cblk * 2;
-        const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3))) *)(pa));
-        const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3))) *)(pa + 4 * kWgRow));
-        frag8s f;
-        f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3];
-        f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-        return f;
-    };
-
-    acc16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nstep = (t1 - t0 + kWgTok - 1) / kWgTok;
-    if (nstep > 0) {
-        fetch(t0);
-        stash(0);
-    }
-    __syncthreads();
-    for (int s = 0; s < nstep; ++s) {
-        const int buf = s & 1;
-        if (s + 1 < nstep) fetch(t0 + (s + 1) * kWgTok);      // block-uniform
-#pragma unroll
-        for (int ks = 0; ks < kWgTok / 16; ++ks) {
-            frag8s fa[2], fb[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) fa[i] = frag(&lds[buf][0][0], ks, wn * 64 + i * 32);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fb[j] = frag(&lds[buf][1][0], ks, wk * 64 + j * 32);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = mfma16<T>(fa[i], fb[j], acc[i][j]);
-        }
-        if (s + 1 < nstep) stash(buf ^ 1);
-        __syncthreads();
-    }
-
-    // ---- partial slab of this (group, batch, split)
-    float *slab = a.part + ((long)g * per + zz) * ((long)a.N * a.K + a.N);
-    const int col_l = lane & 31, rh = 4 * (lane >> 5);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int kc = k0 + wk * 64 + j * 32 + col_l;
-            if (kc < a.K) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int n = n0 + wn * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + rh;
-                    if (n < a.N) slab[(long)n * a.K + kc] = acc[i][j][r];
-                }
-            }
-        }
-    if (do_bias) {   // column sums of gy: 16 token rows of threads per channel chunk, through LDS
-        float *red = reinterpret_cast<float *>(&lds[0][0][0]);   // (16, 128) floats = 8 KB; the tile loop has ended
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[stok * kWgTile + sch + j] = bsum[j];
-        __syncthreads();
-        if (tid < kWgTile && n0 + tid < a.N) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sacc += red[r * kWgTile + tid];
-            slab[(long)a.N * a.K + n0 + tid] = sacc;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// The same TN GEMM with its token tiles staged by LDS-DMA (r03).  wgrad_tn_kernel above keeps ONE 32-token tile in flight
-// (registers -> ds_write -> barrier): every shape of a training step, 1 152 to 73 728 tokens, 0.5 to 9.7 GFLOP, took
+// The TN GEMM with its token tiles staged by LDS-DMA (r03).  The register-staged kernel before it kept ONE 32-token tile in
+// flight (registers -> ds_write -> barrier): every shape of a training step, 1 152 to 73 728 tokens, 0.5 to 9.7 GFLOP, took
 // 22-37 us = 16 K steps x ~1.5 us of memory latency, with 8 MFMAs per wave and step in between (scripts/bench_wgrad.py; an
 // XCD-aware tile order changed nothing: the launches wait on latency, not on bandwidth).  Here NSTG - 1 tiles are in flight
 // per workgroup and no VGPR is spent on staging:
@@ -210,12 +68,12 @@ __global__ __launch_bounds__(256) void wgrad_tn_kernel(WgradArgs a)
 //     4 token rows (lane i -> row i / 16, 16-byte chunk position i % 16); waves 0-1 fetch gy, waves 2-3 fetch x, four
 //     pieces per wave and step;
 //   * the transposed fragment reads (ds_read_b64_tr_b16: a 16-lane group reads 4 token rows x 32 B) want those 4 rows on
-//     different banks, which the 320-byte rows of the register-staged kernel gave: here the 16-byte chunk c of token row t
+//     different banks, which the 320-byte padded rows of the register-staged kernel gave: here the 16-byte chunk c of token row t
 //     sits at chunk position c ^ 4 (t & 3), applied on the GLOBAL side of the DMA (lane i fetches chunk (i % 16) ^ 4 (i / 16))
 //     and undone in the per-lane read address -- the 8 (row, channel-half) pieces of a 32-lane group cover all 64 banks;
 //   * step:  s_waitcnt vmcnt(4 (NSTG - 2)) (my pieces of this tile have landed; hand-counted: hipcc does not see what an
 //            LDS-DMA writes), s_barrier, DMA of tile + NSTG - 1 into the stage just vacated, 16 hand-written
-//            ds_read_b64_tr_b16 behind counted lgkmcnt waits, 8 MFMAs;
+//            ds_read_b64_tr_b16 behind ONE lgkmcnt(0) wait (see kstep), 8 MFMAs;
 //   * token rows past the chunk and channel chunks past N / K arrive as zeros through the descriptor's range check.
 // Same slabs, same bias column sums (read back from the staged gy tile by the k-tile-0 workgroups), same fixed-order sum.
 #define TRAMBA_TR64_(OUT, ADDR, OFF) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #OFF : "=v"(OUT) : "v"(ADDR) : "memory")
@@ -282,7 +140,6 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(WgradArgs a)
     // bias column sums (k-tile 0 only): thread t re-reads chunk positions t % 16 of rows t / 16 and t / 16 + 16 of the gy
     // tile -- both rows hold the same channel chunk there, (t % 16) ^ 4 ((t / 16) & 3)
     const bool do_bias = (a.want_bias & 1) && bx == 0;
-    const bool counted = (a.want_bias & 256) != 0;    // (TRAMBA_TUNE_WGRAD_FORM 2: the r03 counted waits, for measurements only)
     const unsigned ba = lbase + (unsigned)((tid >> 4) * 256 + (tid & 15) * 16);
     float bsum[8];
 #pragma unroll
@@ -351,39 +208,24 @@ __global__ __launch_bounds__(256) void wgrad_dma_kernel(WgradArgs a)
         // a workgroup of another LDS-heavy kernel beside it (the projections' ds_read_b128 traffic, the fused scans') the MFMAs
         // now and then consumed a ds_read_b64_tr_b16 destination that had not been written yet: weight gradients that differ from
         // run to run in a few elements, NaN about one training step in a hundred -- found when the guide branches' backward first ran on
-        // a second stream (scripts/dev/debug_wgrad_concurrent.py: 16-28 of 180 launches differ beside linear_pc / linear_ws /
-        // scan_dma, 0 with this wait; the counted waits below then never wait).  Costs nothing measurable (scripts/bench_wgrad.py).
-        if (!counted) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        // a second stream (16-28 of 180 launches differed beside linear_pc / linear_ws / scan_dma, 0 with this wait;
+        // test_wgrad_is_bitwise_stable_beside_another_stream).  Costs nothing measurable (scripts/bench_wgrad.py).  Every
+        // destination is named so that no MFMA moves above the wait.
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(fg[0][0][0]), "+v"(fg[0][0][1]), "+v"(fx[0][0][0]), "+v"(fx[0][0][1]), "+v"(fg[1][0][0]), "+v"(fg[1][0][1]),
+                       "+v"(fx[1][0][0]), "+v"(fx[1][0][1]), "+v"(fg[0][1][0]), "+v"(fg[0][1][1]), "+v"(fx[0][1][0]), "+v"(fx[0][1][1]),
+                       "+v"(fg[1][1][0]), "+v"(fg[1][1][1]), "+v"(fx[1][1][0]), "+v"(fx[1][1][1])
+                     :
+                     : "memory");
         auto mk = [](v2u32 lo, v2u32 hi) -> frag8s {
             const v4u32 v = {lo.x, lo.y, hi.x, hi.y};
             return __builtin_bit_cast(frag8s, v);
         };
-        // counted waits (the reads return in order): slice 0 of block 0 needs the first 4 reads, block 1 four more, ...
-        if (do_bias) {
-            asm volatile("s_waitcnt lgkmcnt(14)" : "+v"(fg[0][0][0]), "+v"(fg[0][0][1]), "+v"(fx[0][0][0]), "+v"(fx[0][0][1]) : : "memory");
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(12)" : "+v"(fg[0][0][0]), "+v"(fg[0][0][1]), "+v"(fx[0][0][0]), "+v"(fx[0][0][1]) : : "memory");
-        }
         acc[0][0] = mfma16<T>(mk(fg[0][0][0], fg[0][0][1]), mk(fx[0][0][0], fx[0][0][1]), acc[0][0]);
-        if (do_bias) {
-            asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(fg[1][0][0]), "+v"(fg[1][0][1]), "+v"(fx[1][0][0]), "+v"(fx[1][0][1]) : : "memory");
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(fg[1][0][0]), "+v"(fg[1][0][1]), "+v"(fx[1][0][0]), "+v"(fx[1][0][1]) : : "memory");
-        }
         acc[1][0] = mfma16<T>(mk(fg[1][0][0], fg[1][0][1]), mk(fx[0][0][0], fx[0][0][1]), acc[1][0]);
         acc[0][1] = mfma16<T>(mk(fg[0][0][0], fg[0][0][1]), mk(fx[1][0][0], fx[1][0][1]), acc[0][1]);
         acc[1][1] = mfma16<T>(mk(fg[1][0][0], fg[1][0][1]), mk(fx[1][0][0], fx[1][0][1]), acc[1][1]);
-        if (do_bias) {
-            asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(fg[0][1][0]), "+v"(fg[0][1][1]), "+v"(fx[0][1][0]), "+v"(fx[0][1][1]) : : "memory");
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fg[0][1][0]), "+v"(fg[0][1][1]), "+v"(fx[0][1][0]), "+v"(fx[0][1][1]) : : "memory");
-        }
         acc[0][0] = mfma16<T>(mk(fg[0][1][0], fg[0][1][1]), mk(fx[0][1][0], fx[0][1][1]), acc[0][0]);
-        if (do_bias) {
-            asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fg[1][1][0]), "+v"(fg[1][1][1]), "+v"(fx[1][1][0]), "+v"(fx[1][1][1]) : : "memory");
-        } else {
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fg[1][1][0]), "+v"(fg[1][1][1]), "+v"(fx[1][1][0]), "+v"(fx[1][1][1]) : : "memory");
-        }
         acc[1][0] = mfma16<T>(mk(fg[1][1][0], fg[1][1][1]), mk(fx[0][1][0], fx[0][1][1]), acc[1][0]);
         acc[0][1] = mfma16<T>(mk(fg[0][1][0], fg[0][1][1]), mk(fx[1][1][0], fx[1][1][1]), acc[0][1]);
         acc[1][1] = mfma16<T>(mk(fg[1][1][0], fg[1][1][1]), mk(fx[1][1][0], fx[1][1][1]), acc[1][1]);
@@ -735,9 +577,7 @@ static void wgrad_plan(long m, int n, int k, int groups, int nbatch, int &nsplit
     // only share that rate, while every extra split costs another 4 N K bytes of partial sums written and read back
     // (scripts/bench_wgrad.py, r03: 256 wanted workgroups beat 384 / 512 / 768 on 14 of 16 shapes, -8 % over the step's set).
     const long tiles = (long)((n + kWgTile - 1) / kWgTile) * ((k + kWgTile - 1) / kWgTile) * groups * nbatch;
-    const int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);   // 10 / 11 / 12: 384 / 512 / 768 workgroups wanted (measurements)
-    const long target = tune == 10 ? 384 : (tune == 11 ? 512 : (tune == 12 ? 768 : 256));
-    long want = (target + tiles - 1) / tiles;
+    long want = (256 + tiles - 1) / tiles;   // 256 workgroups wanted
     const long maxsplit = m / 512 > 1 ? m / 512 : 1;
     if (want > maxsplit) want = maxsplit;
     if (want < 1) want = 1;
@@ -781,21 +621,11 @@ static int wgrad_launch(const void *gy, const void *x, float *out, void *workspa
     a.gy = gy; a.x = x; a.part = direct ? out : (float *)workspace;
     a.gy_bs = gy_bs; a.gy_gs = gy_gs; a.x_bs = x_bs; a.x_gs = x_gs; a.gy_ld = gy_ld; a.x_ld = x_ld;
     a.M = (int)m; a.N = n; a.K = k; a.nbatch = nbatch; a.nsplit = nsplit; a.mchunk = mchunk; a.want_bias = want_bias ? 1 : 0;
-    if (tramba_tune_get(TRAMBA_TUNE_WGRAD_FORM) == 2) a.want_bias |= 256;
     dim3 grid((k + kWgTile - 1) / kWgTile, (n + kWgTile - 1) / kWgTile, groups * nbatch * nsplit), block(256);
-    // LDS-DMA staged tiles (the default) need 32-bit byte offsets inside one (group, batch) operand -- checked above -- and
-    // rows of whole 16-byte chunks; TRAMBA_TUNE_GEMM_TILE 8 / 9 select the register-staged form / 4 stages for measurements
-    const int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
-    if (tune == 8 || tramba_tune_get(TRAMBA_TUNE_WGRAD_FORM) == 1) {
-        if (dtype == TRAMBA_BF16) hipLaunchKernelGGL((wgrad_tn_kernel<__hip_bfloat16>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wgrad_tn_kernel<__half>), grid, block, 0, s, a);
-    } else if (tune == 9) {
-        if (dtype == TRAMBA_BF16) hipLaunchKernelGGL((wgrad_dma_kernel<__hip_bfloat16, 4>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<__half, 4>), grid, block, 0, s, a);
-    } else {   // 3 stages of 16 KB: three workgroups per CU (measured 3-5 % ahead of 4 stages / two workgroups)
-        if (dtype == TRAMBA_BF16) hipLaunchKernelGGL((wgrad_dma_kernel<__hip_bfloat16, 3>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((wgrad_dma_kernel<__half, 3>), grid, block, 0, s, a);
-    }
+    // LDS-DMA staged tiles need 32-bit byte offsets inside one (group, batch) operand -- checked above -- and rows of whole
+    // 16-byte chunks.  3 stages of 16 KB: three workgroups per CU (measured 3-5 % ahead of 4 stages / two workgroups)
+    if (dtype == TRAMBA_BF16) hipLaunchKernelGGL((wgrad_dma_kernel<__hip_bfloat16, 3>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((wgrad_dma_kernel<__half, 3>), grid, block, 0, s, a);
     TRAMBA_LAUNCH_CHECK();
     if (nslab_out) {
         *nslab_out = direct ? 0 : nbatch * nsplit;
