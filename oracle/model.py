@@ -5,7 +5,8 @@ it shares no class with the product's nn.Module tree; it accepts the reference's
 ``state_dict()`` as well as the product's (same 679 names for Tramba-V).
 
 Every function cites the reference code it restates.  Eval-mode semantics (DropPath and
-Dropout are identities; BatchNorm uses running statistics).
+Dropout are identities; BatchNorm uses running statistics), except that the residual blocks
+take injected per-sample DropPath masks for the training-path tests.
 """
 import torch
 import torch.nn.functional as F
@@ -56,10 +57,18 @@ def mlp(p: SD, x):
     return _lin(p.sub("fc2"), F.gelu(_lin(p.sub("fc1"), x)))
 
 
-def vss_block(p: SD, x):
-    """vmamba.py:384-396 (pre-norm)."""
-    x = x + ss2d(p.sub("op"), _ln(p.sub("norm"), x), "raster")
-    return x + mlp(p.sub("mlp"), _ln(p.sub("norm2"), x))
+def _drop(y, m):
+    """a residual branch under stochastic depth: y * m[sample] (m (B): keep / keep_prob per image, timm's DropPath)"""
+    return y * m.to(y.dtype).view((-1,) + (1,) * (y.dim() - 1))
+
+
+def vss_block(p: SD, x, masks=None):
+    """vmamba.py:384-396 (pre-norm).  masks: None (eval mode) or the (B) DropPath masks of the two branches."""
+    if masks is None:
+        x = x + ss2d(p.sub("op"), _ln(p.sub("norm"), x), "raster")
+        return x + mlp(p.sub("mlp"), _ln(p.sub("norm2"), x))
+    x = x + _drop(ss2d(p.sub("op"), _ln(p.sub("norm"), x), "raster"), masks[0])
+    return x + _drop(mlp(p.sub("mlp"), _ln(p.sub("norm2"), x)), masks[1])
 
 
 def vssm_encoder(p: SD, x, depths=(2, 2, 15, 2)):
@@ -91,10 +100,13 @@ def dwms_mlp(p: SD, x):
     return _lin(p.sub("fc2"), F.gelu(acc))
 
 
-def multiscale_decoder_block(p: SD, x):
-    """vmamba.py:700-704 (Helix-SS2D K=8 + DWMSMlp)."""
-    x = x + ss2d(p.sub("op"), _ln(p.sub("norm1"), x), "helix")
-    return x + dwms_mlp(p.sub("mlp"), _ln(p.sub("norm2"), x))
+def multiscale_decoder_block(p: SD, x, masks=None):
+    """vmamba.py:700-704 (Helix-SS2D K=8 + DWMSMlp).  masks: as vss_block."""
+    if masks is None:
+        x = x + ss2d(p.sub("op"), _ln(p.sub("norm1"), x), "helix")
+        return x + dwms_mlp(p.sub("mlp"), _ln(p.sub("norm2"), x))
+    x = x + _drop(ss2d(p.sub("op"), _ln(p.sub("norm1"), x), "helix"), masks[0])
+    return x + _drop(dwms_mlp(p.sub("mlp"), _ln(p.sub("norm2"), x)), masks[1])
 
 
 def _expand_shuffle_norm(p: SD, x, scale):

@@ -324,3 +324,32 @@ def test_adam_restatement_equals_torch_optim_adam(wd):
             assert torch.allclose(p.detach(), want_p[i], rtol=1e-12, atol=1e-14)
             assert torch.allclose(st["exp_avg"], want_m[i], rtol=1e-12, atol=1e-14)
             assert torch.allclose(st["exp_avg_sq"], want_v[i], rtol=1e-12, atol=1e-16)
+
+
+# --------------------------------------------------------------------------- per-sample DropPath masks
+MASKED_BLOCKS = {"vssblock": om.vss_block, "helixblock": om.multiscale_decoder_block}
+
+
+@pytest.mark.parametrize("tag", list(MASKED_BLOCKS))
+def test_block_masks_of_ones_and_zeros(golden_meta, tag):
+    """masks of ones give the eval-mode block bit for bit; masks of zeros make the block the identity"""
+    fn = MASKED_BLOCKS[tag]
+    p = om.SD(block_state(golden_meta, tag))
+    x = torch.randn(3, 16, 12, 12, generator=torch.Generator().manual_seed(1))
+    ones, zeros = torch.ones(3), torch.zeros(3)
+    assert torch.equal(fn(p, x, masks=(ones, ones)), fn(p, x))
+    assert torch.equal(fn(p, x, masks=(zeros, zeros)), x)
+
+
+@pytest.mark.parametrize("tag", list(MASKED_BLOCKS))
+def test_block_mask_acts_per_image(golden_meta, tag):
+    """an image's output under its mask values does not depend on the other images' masks, and does depend on its own"""
+    fn = MASKED_BLOCKS[tag]
+    p = om.SD(block_state(golden_meta, tag))
+    x = torch.randn(3, 16, 12, 12, generator=torch.Generator().manual_seed(2))
+    a = fn(p, x, masks=(torch.tensor([1.25, 0.0, 2.0]), torch.tensor([0.5, 2.0, 0.0])))
+    b = fn(p, x, masks=(torch.tensor([1.25, 2.0, 0.5]), torch.tensor([0.5, 0.0, 1.25])))
+    assert torch.equal(a[0], b[0])
+    assert not torch.allclose(a[1], b[1]) and not torch.allclose(a[2], b[2])
+    alone = fn(p, x[:1], masks=(torch.tensor([1.25]), torch.tensor([0.5])))
+    np.testing.assert_allclose(alone[0].numpy(), a[0].numpy(), rtol=1e-6, atol=1e-6)
