@@ -499,6 +499,37 @@ int tramba_frames_to_input(const unsigned char *frames, const int *table, float 
 int tramba_logits_to_u8(const void *logits, unsigned char *out, int batch, int in_h, int in_w, int h, int w, int dtype,
                         void *stream);
 
+/* ------------------------------------------------------------------ training: uint8 pairs in, train batches out */
+/* The train transform of the loader (data.get_transform(S, 'train'): static resize, scale-crop, mirror, rotation, the three
+ * enhancers, to_tensors) on the device, bit for bit, for draws made on the host (tramba_amd/augment.py).  Tables (HOST int32
+ * arrays, fp64 with contraction off; the caller uploads them once and caches them):
+ *   tramba_augment_source_table: one source size (h, w) -> (size, size): {kx, ky, 0, 0}, the tramba_resize_table words of
+ *     the bilinear image resize, then Pillow's nearest indices of the mask, x[size] then y[size] (-1: fill 0);
+ *   tramba_augment_size_table: one output side: the normalisation table [3][256] f32, u / 255 [256] f32, SMOOTH / 13 [9] f32
+ *     (words 1024..), {lo, hi} at word 1040, then at 1042 the word offset of the bicubic axis table (bounds[R][2],
+ *     weights[R][taps]) of every R in lo .. hi (0 for R == size, Pillow's copy); taps: tramba_augment_scale_taps;
+ *   tramba_augment_rotation: Image.rotate(degrees, expand=True) + centre crop as 6 16.16 words A0..A5 (source pixel of
+ *     output (x, y) = ((A0 x + A1 y + A2) >> 16, (A3 x + A4 y + A5) >> 16); out of range: 0).
+ * tramba_augment_batch: packed (device, packed_bytes): batch descriptors of TRAMBA_AUG_DESC_WORDS int64 words (layout:
+ * csrc/augment.hip), then the u8 images (h, w, 3) and masks (h, w) at the byte offsets they name; desc_host: a host copy of
+ * the descriptors, checked before any launch (sizes 1 .. TRAMBA_FRAME_MAX_DIM, 3 <= size <= TRAMBA_FRAME_MAX_OUT, offsets
+ * inside the buffer, draws in range).  image (batch, 3, size, size) f32, label (batch, 1, size, size) f32.  Four launches on
+ * `stream`, no allocation, no synchronisation; each sample's result is independent of the batch it is in. */
+#define TRAMBA_AUG_DESC_WORDS 32
+#define TRAMBA_AUG_CONTRAST 0
+#define TRAMBA_AUG_BRIGHTNESS 1
+#define TRAMBA_AUG_SHARPNESS 2
+size_t tramba_augment_source_table_words(int h, int w, int size);
+int tramba_augment_source_table(int h, int w, int size, int *table, size_t words);
+size_t tramba_augment_size_table_words(int size);
+int tramba_augment_size_table(int size, const double *mean, const double *std, int *table, size_t words);
+int tramba_augment_scale_taps(int size, int r);
+int tramba_augment_rotation(int size, int degrees, int *coef);
+size_t tramba_augment_workspace(int batch, int size);
+int tramba_augment_batch(const unsigned char *packed, const int64_t *desc_host, size_t packed_bytes, const int *size_table,
+                         float *image, float *label, void *workspace, size_t workspace_bytes, int batch, int size,
+                         void *stream);
+
 /* ------------------------------------------------------------------ loss and optimizer of the training step */
 /* The deep-supervision loss (train.py:76-85; utils/loss.py:6-11) of ONE output: logits (planes, h, w) f32 bilinearly resized
  * (F.interpolate(mode="bilinear"), align_corners=False; identity when the sizes agree) to the label (planes, hout, wout) f32,

@@ -16,6 +16,7 @@
 //   as torch's upsample_bilinear2d kernel computes it (source index, two-level lambda blend, with the FMAs its build
 //   contracts to); each thread stores 16 consecutive output bytes with one 16-byte store.
 #include "common.h"
+#include "resample.h"
 
 #include <math.h>
 
@@ -27,19 +28,32 @@ constexpr int kFrThreads = 256;
 constexpr int kFrMaxAcc = 8;              // vertical sums per thread: band * 3 * slab <= kFrThreads * kFrMaxAcc
 constexpr int kFrLdsBytes = 32768;        // horizontally resampled rows staged per chunk
 constexpr int kFrWantBlocks = 512;        // a band size that gives at least this many workgroups where it can
-constexpr int kPrecBits = 22;             // Pillow's fixed-point precision for 8-bit images
 constexpr int kU8Threads = 256, kU8Bytes = 16;
 
 // ---------------------------------------------------------------------------------------------- coefficient tables
 // Word layout of a table (int32): xb[out_w][2] = {first input column, taps}, xk[out_w][kx] fixed-point weights, then
 // yb[out_h][2], yk[out_h][ky], then lut[3][256] (f32 bits).  An axis whose size does not change gets one tap of weight
 // 2^22 (acc >> 22 = px exactly: the pass is a copy, as Pillow skips it).
-static int axis_taps(int in, int out)
+static double filter_support(int filter) { return filter == kFilterBicubic ? 2.0 : 1.0; }
+
+// Pillow's bilinear (triangle) and bicubic (a = -0.5) kernels
+static double filter_weight(int filter, double x)
+{
+#pragma clang fp contract(off)
+    if (x < 0.0) x = -x;
+    if (filter != kFilterBicubic) return x < 1.0 ? 1.0 - x : 0.0;
+    const double a = -0.5;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+int resample_taps(int in, int out, int filter)
 {
     if (in == out) return 1;
     const double scale = (double)in / out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    return (int)ceil(fs) * 2 + 1;
+    return (int)ceil(filter_support(filter) * fs) * 2 + 1;
 }
 
 struct ResizeLayout {
@@ -50,8 +64,8 @@ struct ResizeLayout {
 static ResizeLayout resize_layout(int in_h, int in_w, int out_h, int out_w)
 {
     ResizeLayout L;
-    L.kx = axis_taps(in_w, out_w);
-    L.ky = axis_taps(in_h, out_h);
+    L.kx = resample_taps(in_w, out_w, kFilterBilinear);
+    L.ky = resample_taps(in_h, out_h, kFilterBilinear);
     L.xb = 0;
     L.xk = L.xb + 2 * (size_t)out_w;
     L.yb = L.xk + (size_t)out_w * L.kx;
@@ -61,15 +75,15 @@ static ResizeLayout resize_layout(int in_h, int in_w, int out_h, int out_w)
     return L;
 }
 
-static bool frame_sizes_ok(int in_h, int in_w, int out_h, int out_w)
+bool frame_sizes_ok(int in_h, int in_w, int out_h, int out_w)
 {
     return in_h >= 1 && in_w >= 1 && in_h <= TRAMBA_FRAME_MAX_DIM && in_w <= TRAMBA_FRAME_MAX_DIM && out_h >= 1 &&
            out_w >= 1 && out_h <= TRAMBA_FRAME_MAX_OUT && out_w <= TRAMBA_FRAME_MAX_OUT;
 }
 
-// One axis, Pillow's bilinear rule for 8-bit images.  No contraction: `center - support` and the other sums must round
-// as separate fp64 operations.
-static bool resize_axis(int in, int out, int ksize, int *bounds, int *coef)
+// One axis, Pillow's rule for 8-bit images (precompute_coeffs + normalize_coeffs_8bpc).  No contraction: `center - support`
+// and the other sums must round as separate fp64 operations.
+bool resample_axis(int in, int out, int filter, int ksize, int *bounds, int *coef)
 {
 #pragma clang fp contract(off)
     if (in == out) {
@@ -82,7 +96,7 @@ static bool resize_axis(int in, int out, int ksize, int *bounds, int *coef)
     }
     const double scale = (double)in / out;
     const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs;                 // the triangle's support (1) times the filter scale
+    const double support = filter_support(filter) * fs;
     const double ss = 1.0 / fs;
     std::vector<double> w(ksize);
     for (int i = 0; i < out; ++i) {
@@ -95,21 +109,22 @@ static bool resize_axis(int in, int out, int ksize, int *bounds, int *coef)
         if (n < 1 || n > ksize) return false;
         double ww = 0.0;
         for (int j = 0; j < n; ++j) {
-            const double x = fabs(((double)(j + xmin) - center + 0.5) * ss);
-            w[j] = x < 1.0 ? 1.0 - x : 0.0;
+            w[j] = filter_weight(filter, ((double)(j + xmin) - center + 0.5) * ss);
             ww += w[j];
         }
         for (int j = 0; j < n; ++j)
             if (ww != 0.0) w[j] /= ww;
-        for (int j = 0; j < ksize; ++j)
-            coef[(size_t)i * ksize + j] = j < n ? (int)(0.5 + w[j] * (double)(1 << kPrecBits)) : 0;
+        for (int j = 0; j < ksize; ++j) {
+            const double v = j < n ? w[j] * (double)(1 << kPrecBits) : 0.0;
+            coef[(size_t)i * ksize + j] = j >= n ? 0 : (v < 0.0 ? (int)(-0.5 + v) : (int)(0.5 + v));
+        }
         bounds[2 * i] = xmin;
         bounds[2 * i + 1] = n;
     }
     return true;
 }
 
-static void normalise_lut(const double *mean, const double *std, float *lut)
+void normalise_lut(const double *mean, const double *std, float *lut)
 {
 #pragma clang fp contract(off)
     for (int c = 0; c < 3; ++c)
@@ -292,8 +307,8 @@ extern "C" int tramba_resize_table(int in_h, int in_w, int out_h, int out_w, con
     const ResizeLayout L = resize_layout(in_h, in_w, out_h, out_w);
     TRAMBA_CHECK(words >= L.words, "resize_table: %zu words given, %zu needed", words, L.words);
     for (int c = 0; c < 3; ++c) TRAMBA_CHECK(std[c] != 0.0, "resize_table: std[%d] is zero", c);
-    TRAMBA_CHECK(resize_axis(in_w, out_w, L.kx, table + L.xb, table + L.xk) &&
-                 resize_axis(in_h, out_h, L.ky, table + L.yb, table + L.yk), "resize_table: tap count out of range");
+    TRAMBA_CHECK(resample_axis(in_w, out_w, kFilterBilinear, L.kx, table + L.xb, table + L.xk) &&
+                 resample_axis(in_h, out_h, kFilterBilinear, L.ky, table + L.yb, table + L.yk), "resize_table: tap count out of range");
     normalise_lut(mean, std, reinterpret_cast<float *>(table + L.lut));
     return TRAMBA_OK;
 }

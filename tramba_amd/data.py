@@ -243,7 +243,13 @@ def _seed_worker(worker_id, rank=0):
 def train_loader(root, img_size=384, batch_size=4, num_workers=8, rank=0, world_size=1, seed=1026, distinct_workers=True):
     """train.py:288-293: Train split, shuffled, pinned.  With world_size > 1 every rank draws a disjoint shard of each
     epoch's permutation (call `loader.sampler.set_epoch(epoch)` per epoch)."""
-    ds = RGB_Dataset(root, ["Train"], img_size, "train")
+    return _train_dataloader(RGB_Dataset(root, ["Train"], img_size, "train"), batch_size, num_workers, rank, world_size,
+                             seed, distinct_workers)
+
+
+def _train_dataloader(ds, batch_size, num_workers, rank, world_size, seed, distinct_workers, collate_fn=None):
+    """train_loader's DataLoader around any train dataset: shuffle / shards, worker streams, pinning (collate_fn None: the
+    default collation).  tramba_amd.augment builds its loader of uint8 pairs here, so both see the same draws."""
     sampler = None
     if world_size > 1:
         from torch.utils.data.distributed import DistributedSampler
@@ -257,7 +263,8 @@ def train_loader(root, img_size=384, batch_size=4, num_workers=8, rank=0, world_
                       # on a GPU build they are always spawned, and kept across epochs (a spawn re-imports torch per worker)
                       multiprocessing_context=("spawn" if num_workers > 0 and torch.cuda.device_count() > 0 else None),
                       persistent_workers=num_workers > 0 and torch.cuda.device_count() > 0,
-                      worker_init_fn=functools.partial(_seed_worker, rank=rank) if (distinct_workers and num_workers > 0) else None)
+                      worker_init_fn=functools.partial(_seed_worker, rank=rank) if (distinct_workers and num_workers > 0) else None,
+                      collate_fn=collate_fn)
 
 
 def eval_loader(root, img_size=384, num_workers=8):

@@ -76,6 +76,14 @@ SIGNATURES = {
     "tramba_resize_table": (c_int, [c_int] * 4 + [c_vp] * 3 + [ctypes.c_size_t]),
     "tramba_frames_to_input": (c_int, [c_vp] * 3 + [c_int] * 6 + [c_vp]),
     "tramba_logits_to_u8": (c_int, [c_vp] * 2 + [c_int] * 6 + [c_vp]),
+    "tramba_augment_source_table_words": (ctypes.c_size_t, [c_int] * 3),
+    "tramba_augment_source_table": (c_int, [c_int] * 3 + [c_vp, ctypes.c_size_t]),
+    "tramba_augment_size_table_words": (ctypes.c_size_t, [c_int]),
+    "tramba_augment_size_table": (c_int, [c_int] + [c_vp] * 3 + [ctypes.c_size_t]),
+    "tramba_augment_scale_taps": (c_int, [c_int] * 2),
+    "tramba_augment_rotation": (c_int, [c_int] * 2 + [c_vp]),
+    "tramba_augment_workspace": (ctypes.c_size_t, [c_int] * 2),
+    "tramba_augment_batch": (c_int, [c_vp] * 2 + [ctypes.c_size_t] + [c_vp] * 4 + [ctypes.c_size_t] + [c_int] * 2 + [c_vp]),
     "tramba_dw_pack": (c_int, [c_vp] * 8 + [c_int] * 2 + [c_vp]),
     "tramba_dwconv_cl": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
     "tramba_dwconv_dual_cl": (c_int, [c_vp] * 5 + [c_int] * 8 + [c_vp]),
@@ -782,6 +790,87 @@ def logits_to_u8(logits, h: int, w: int):
     out = torch.empty((b, h, w), dtype=torch.uint8, device=logits.device)
     _check(lib().tramba_logits_to_u8(_ptr(logits), _ptr(out), b, ih, iw, h, w, dt(logits), _stream()), "logits_to_u8")
     return out
+
+
+AUG_DESC_WORDS = 32                                  # TRAMBA_AUG_DESC_WORDS
+AUG_CONTRAST, AUG_BRIGHTNESS, AUG_SHARPNESS = 0, 1, 2
+
+
+def _aug_size(what, size):
+    if not 3 <= size <= FRAME_MAX_OUT:
+        raise TrambaHipError(f"{what}: size {size} outside 3 .. {FRAME_MAX_OUT}")
+
+
+def augment_source_table_host(h: int, w: int, size: int) -> np.ndarray:
+    """int32 host table of one source size (h, w) -> (size, size) for augment_batch: the bilinear words of the image and
+    Pillow's nearest indices of the mask (layout: include/tramba_hip.h), computed by the library in fp64."""
+    words = lib().tramba_augment_source_table_words(h, w, size)
+    if words == 0:
+        raise TrambaHipError(f"augment_source_table: {h}x{w} -> {size} outside 1 .. {FRAME_MAX_DIM} per source side, "
+                             f"3 .. {FRAME_MAX_OUT} for the output side")
+    out = np.empty(words, dtype=np.int32)
+    _check(lib().tramba_augment_source_table(h, w, size, out.ctypes.data, words), "augment_source_table")
+    return out
+
+
+def augment_size_table_host(size: int, mean, std) -> np.ndarray:
+    """int32 host table of one output side: normalisation, label and SMOOTH tables and the bicubic S -> R axis table of
+    every reachable R (layout: include/tramba_hip.h)."""
+    _aug_size("augment_size_table", size)
+    words = lib().tramba_augment_size_table_words(size)
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    std = np.ascontiguousarray(std, dtype=np.float64)
+    if mean.shape != (3,) or std.shape != (3,):
+        raise TrambaHipError("augment_size_table: mean and std need 3 values each")
+    out = np.empty(words, dtype=np.int32)
+    _check(lib().tramba_augment_size_table(size, mean.ctypes.data, std.ctypes.data, out.ctypes.data, words),
+           "augment_size_table")
+    return out
+
+
+def augment_scale_taps(size: int, r: int) -> int:
+    return _check(lib().tramba_augment_scale_taps(size, r), "augment_scale_taps")
+
+
+def augment_rotation(size: int, degrees: int) -> np.ndarray:
+    """the 6 16.16 words of Image.rotate(degrees, expand=True) + centre crop on a (size, size) image"""
+    out = np.empty(6, dtype=np.int32)
+    _check(lib().tramba_augment_rotation(size, degrees, out.ctypes.data), "augment_rotation")
+    return out
+
+
+def augment_workspace_bytes(batch: int, size: int) -> int:
+    _aug_size("augment_workspace", size)
+    if not 1 <= batch <= 65535:
+        raise TrambaHipError(f"augment_workspace: batch {batch} outside 1 .. 65535")
+    return lib().tramba_augment_workspace(batch, size)
+
+
+def augment_batch(packed, desc_host: np.ndarray, size_table, size: int, workspace):
+    """packed (N,) u8 on the device (descriptors, then the pairs' bytes), desc_host its (B, AUG_DESC_WORDS) int64 host copy,
+    size_table the device copy of augment_size_table_host(size), workspace >= augment_workspace_bytes(B, size) bytes ->
+    (image (B, 3, size, size) f32, label (B, 1, size, size) f32): the loader's train transform for the recorded draws."""
+    _aug_size("augment_batch", size)
+    if packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise TrambaHipError(f"augment_batch: packed must be a flat uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    _dev(packed, size_table, workspace)
+    desc_host = np.ascontiguousarray(desc_host, dtype=np.int64)
+    if desc_host.ndim != 2 or desc_host.shape[1] != AUG_DESC_WORDS or not 1 <= desc_host.shape[0] <= 65535:
+        raise TrambaHipError(f"augment_batch: descriptors must be (B, {AUG_DESC_WORDS}) with 1 <= B <= 65535")
+    b = desc_host.shape[0]
+    hw = desc_host[:, 2:4]
+    if (hw < 1).any() or (hw > FRAME_MAX_DIM).any():
+        raise TrambaHipError(f"augment_batch: a source side is outside 1 .. {FRAME_MAX_DIM}")
+    if size_table.dtype != torch.int32 or size_table.numel() < lib().tramba_augment_size_table_words(size):
+        raise TrambaHipError("augment_batch: size_table does not belong to this size")
+    if workspace.numel() * workspace.element_size() < lib().tramba_augment_workspace(b, size):
+        raise TrambaHipError("augment_batch: workspace too small")
+    image = torch.empty((b, 3, size, size), dtype=torch.float32, device=packed.device)
+    label = torch.empty((b, 1, size, size), dtype=torch.float32, device=packed.device)
+    _check(lib().tramba_augment_batch(_ptr(packed), desc_host.ctypes.data, packed.numel(), _ptr(size_table), _ptr(image),
+                                      _ptr(label), _ptr(workspace), workspace.numel() * workspace.element_size(), b, size,
+                                      _stream()), "augment_batch")
+    return image, label
 
 
 def rowdot_cl(x, w, bias: float):
