@@ -498,6 +498,30 @@ int tramba_frames_to_input(const unsigned char *frames, const int *table, float 
  * batch <= 65535. */
 int tramba_logits_to_u8(const void *logits, unsigned char *out, int batch, int in_h, int in_w, int h, int w, int dtype,
                         void *stream);
+/* The same two ends for a batch of frames of DIFFERENT sizes (a dataset folder).  packed (device, packed_bytes, 16-byte
+ * aligned): batch descriptors of TRAMBA_FRAMES_DESC_WORDS int64 words, then the tramba_resize_table words of every frame
+ * size to (size, size) and the u8 frames (h, w, 3) at the byte offsets the descriptors name.  Words of a descriptor: frame
+ * offset, h, w, table offset (a multiple of 4), taps per output column, taps per output row, offset of the frame's (h, w) map
+ * in the output buffer (a multiple of 16, increasing, maps disjoint), then (float)size / (float)h and (float)size / (float)w
+ * as fp32 bits; the rest 0.  Frame i's input plane and map are bit for bit what the uniform entries give for that frame alone.
+ * Launch geometry and kernel arguments depend on (batch, size, out_capacity) only, never on the frame sizes, so one captured
+ * graph serves every packed batch that fits its buffers.  desc_host: a HOST copy of the descriptors, checked before the launch.
+ * tramba_frames_ragged_check is that check alone (no launch), for a caller that replays a graph: sides 1 ..
+ * TRAMBA_FRAME_MAX_DIM, 3 <= size <= TRAMBA_FRAME_MAX_OUT, batch <= 65535; parts & TRAMBA_RAGGED_IN: frames and tables inside
+ * packed_bytes and outside the descriptor area, taps those of the sizes; parts & TRAMBA_RAGGED_OUT: map offsets aligned,
+ * increasing, not overlapping, every map inside out_capacity, scale words those of the sizes.
+ * tramba_frames_to_input_ragged: out (batch, 3, size, size) f32.  tramba_logits_to_u8_ragged: logits (batch, 1, size, size)
+ * f32 / f16 / bf16, out a u8 buffer of out_capacity bytes (16-byte aligned) that receives the maps at their offsets; bytes
+ * between maps and after the last one are not written.  No allocation, copy or synchronisation in either. */
+#define TRAMBA_FRAMES_DESC_WORDS 16
+#define TRAMBA_RAGGED_IN 1
+#define TRAMBA_RAGGED_OUT 2
+int tramba_frames_ragged_check(const int64_t *desc_host, int batch, int size, size_t packed_bytes, size_t out_capacity,
+                               int parts);
+int tramba_frames_to_input_ragged(const unsigned char *packed, const int64_t *desc_host, size_t packed_bytes, float *out,
+                                  int batch, int size, int bgr, void *stream);
+int tramba_logits_to_u8_ragged(const void *logits, const unsigned char *packed, const int64_t *desc_host, unsigned char *out,
+                               size_t out_capacity, int batch, int size, int dtype, void *stream);
 
 /* ------------------------------------------------------------------ training: uint8 pairs in, train batches out */
 /* The train transform of the loader (data.get_transform(S, 'train'): static resize, scale-crop, mirror, rotation, the three

@@ -15,10 +15,13 @@
 //   uint8(sigmoid(F.interpolate(res.float(), (H, W), mode="bilinear", align_corners=False)) * 255).  The resize is written
 //   as torch's upsample_bilinear2d kernel computes it (source index, two-level lambda blend, with the FMAs its build
 //   contracts to); each thread stores 16 consecutive output bytes with one 16-byte store.
+// The *_ragged kernels are the same two computations for a batch of frames of different sizes: what depends on a frame's
+//   size travels in a per-frame descriptor in device memory instead of in the kernel arguments (layout below).
 #include "common.h"
 #include "resample.h"
 
 #include <math.h>
+#include <string.h>
 
 #include <vector>
 
@@ -142,10 +145,11 @@ __device__ __forceinline__ int clamp_u8(int acc)
     return v > 255 ? 255 : v;
 }
 
-__global__ __launch_bounds__(kFrThreads) void frames_to_input_kernel(const unsigned char *__restrict__ frames,
-                                                                     const int *__restrict__ table, float *__restrict__ out,
-                                                                     int H, int W, int OH, int OW, int kx, int ky, int slab,
-                                                                     int band, int chunk, int bgr)
+// One workgroup's tile of frame blockIdx.z: `src` is that frame, `table` its coefficient table.  Shared by the uniform kernel
+// (sizes in the arguments) and the ragged one (sizes in the frame's descriptor).
+__device__ __forceinline__ void frames_tile(const unsigned char *__restrict__ src, const int *__restrict__ table,
+                                            float *__restrict__ out, int W, int OH, int OW, int kx, int ky, int slab, int band,
+                                            int chunk, int bgr)
 {
     extern __shared__ unsigned char hrows[];   // [chunk][slab * 3]: input rows resampled along x, RGB interleaved
     __shared__ float lut[3 * 256];
@@ -159,7 +163,6 @@ __global__ __launch_bounds__(kFrThreads) void frames_to_input_kernel(const unsig
     const int rowlen = sw * 3;
     const int nout = (y1 - y0) * rowlen;       // outputs of the tile, ordered (row, channel, x)
     const int ylo = yb[2 * y0], yhi = yb[2 * (y1 - 1)] + yb[2 * (y1 - 1) + 1];   // bounds are monotone in the row
-    const unsigned char *src = frames + (size_t)b * H * W * 3;
 
     int acc[kFrMaxAcc];
 #pragma unroll
@@ -211,6 +214,46 @@ __global__ __launch_bounds__(kFrThreads) void frames_to_input_kernel(const unsig
             out[((size_t)b * 3 + c) * OH * OW + (size_t)(y0 + r) * OW + x0 + xl] = lut[c * 256 + clamp_u8(acc[k])];
         }
     }
+}
+
+__global__ __launch_bounds__(kFrThreads) void frames_to_input_kernel(const unsigned char *__restrict__ frames,
+                                                                     const int *__restrict__ table, float *__restrict__ out,
+                                                                     int H, int W, int OH, int OW, int kx, int ky, int slab,
+                                                                     int band, int chunk, int bgr)
+{
+    frames_tile(frames + (size_t)blockIdx.z * H * W * 3, table, out, W, OH, OW, kx, ky, slab, band, chunk, bgr);
+}
+
+// A packed batch of frames of different sizes (one flat u8 buffer): batch descriptors of TRAMBA_FRAMES_DESC_WORDS int64
+// words, then the coefficient tables (the tramba_resize_table words, one per distinct frame size) and the frames (h, w, 3)
+// at the byte offsets the descriptors name.  Both ragged launches depend on (batch, S) and the output capacity only, so one
+// captured graph serves every mix of sizes.
+enum {
+    kRgFrame = 0,       // byte offset of the (h, w, 3) frame in the packed buffer
+    kRgH,
+    kRgW,
+    kRgTable,           // byte offset of the tramba_resize_table words for (h, w) -> (S, S), a multiple of 4
+    kRgKx,              // taps per output column and per output row of that table
+    kRgKy,
+    kRgOut,             // byte offset of the (h, w) map in the output buffer, a multiple of 16
+    kRgRh,              // (float)S / (float)h and (float)S / (float)w as fp32 bits: torch's area_pixel_compute_scale, made on
+    kRgRw,              // the host as the uniform entry makes it, so no device-side division can round differently
+    kRgUsed
+};
+static_assert(kRgUsed <= TRAMBA_FRAMES_DESC_WORDS, "descriptor layout");
+
+__device__ __forceinline__ const long long *ragged_desc(const unsigned char *packed, int b)
+{
+    return reinterpret_cast<const long long *>(packed) + (size_t)b * TRAMBA_FRAMES_DESC_WORDS;
+}
+
+__global__ __launch_bounds__(kFrThreads) void frames_to_input_ragged_kernel(const unsigned char *__restrict__ packed,
+                                                                            float *__restrict__ out, int S, int slab, int band,
+                                                                            int chunk, int bgr)
+{
+    const long long *d = ragged_desc(packed, blockIdx.z);
+    frames_tile(packed + d[kRgFrame], reinterpret_cast<const int *>(packed + d[kRgTable]), out, (int)d[kRgW], S, S,
+                (int)d[kRgKx], (int)d[kRgKy], slab, band, chunk, bgr);
 }
 
 // ---------------------------------------------------------------------------------------------- logits -> u8 maps
@@ -288,6 +331,117 @@ __global__ __launch_bounds__(kU8Threads) void logits_to_u8_kernel(const T *__res
     }
 }
 
+// The grid covers the output buffer's CAPACITY, 16 bytes per thread.  The map offsets increase and are 16-byte aligned, so a
+// thread's 16 bytes belong to at most one map: the workgroup finds the last map that starts at or before its first byte by
+// binary search (as adam_kernel finds its tensor), a thread steps on from there (short maps: several per workgroup), and
+// bytes between two maps or past the last one are left alone.
+template <typename T>
+__global__ __launch_bounds__(kU8Threads) void logits_to_u8_ragged_kernel(const T *__restrict__ logits,
+                                                                         const unsigned char *__restrict__ packed,
+                                                                         unsigned char *__restrict__ out, int batch, int S)
+{
+    const size_t first = (size_t)blockIdx.x * kU8Threads * kU8Bytes;
+    const long long *last = ragged_desc(packed, batch - 1);
+    if (first >= (size_t)(last[kRgOut] + last[kRgH] * last[kRgW])) return;   // past the batch's last byte
+    int lo = 0, hi = batch;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((size_t)ragged_desc(packed, mid)[kRgOut] <= first) lo = mid; else hi = mid;
+    }
+    const size_t base = first + (size_t)threadIdx.x * kU8Bytes;
+    while (lo + 1 < batch && (size_t)ragged_desc(packed, lo + 1)[kRgOut] <= base) ++lo;
+    const long long *d = ragged_desc(packed, lo);
+    const size_t off = (size_t)d[kRgOut];
+    const int H = (int)d[kRgH], W = (int)d[kRgW];
+    const size_t total = (size_t)H * W;
+    if (base < off || base - off >= total) return;
+    const size_t at = base - off;
+    const float rh = __uint_as_float((unsigned)d[kRgRh]), rw = __uint_as_float((unsigned)d[kRgRw]);
+    const bool copy = S == H && S == W;
+    const T *img = logits + (size_t)lo * S * S;
+    int y = (int)(at / W), x = (int)(at - (size_t)y * W);
+    unsigned char v[kU8Bytes];
+#pragma unroll
+    for (int i = 0; i < kU8Bytes; ++i) {
+        v[i] = at + i < total ? saliency_u8(img, S, S, y, x, rh, rw, copy) : 0;
+        if (++x == W) {
+            x = 0;
+            ++y;
+        }
+    }
+    if (at + kU8Bytes <= total) {
+        Pack<unsigned char, kU8Bytes> pk;
+#pragma unroll
+        for (int i = 0; i < kU8Bytes; ++i) pk.v[i] = v[i];
+        *reinterpret_cast<Pack<unsigned char, kU8Bytes> *>(out + base) = pk;
+    } else {
+        for (int i = 0; at + i < total; ++i) out[base + i] = v[i];
+    }
+}
+
+static unsigned f32_bits(float f)
+{
+    unsigned u;
+    memcpy(&u, &f, sizeof u);
+    return u;
+}
+
+// The host copy of a packed batch's descriptors against the buffer sizes; `parts` selects the input half (frames and
+// tables inside packed_bytes), the output half (maps inside out_capacity), or both.
+static int ragged_check(const char *who, const int64_t *desc, int batch, int size, size_t packed_bytes, size_t out_capacity,
+                        int parts)
+{
+    TRAMBA_CHECK(desc, "%s: null pointer", who);
+    TRAMBA_CHECK(batch >= 1 && batch <= 65535, "%s: batch %d outside 1 .. 65535", who, batch);
+    TRAMBA_CHECK(size >= 3 && size <= TRAMBA_FRAME_MAX_OUT, "%s: output size %d outside 3 .. %d", who, size,
+                 TRAMBA_FRAME_MAX_OUT);
+    TRAMBA_CHECK(parts >= 1 && parts <= (TRAMBA_RAGGED_IN | TRAMBA_RAGGED_OUT), "%s: parts %d selects nothing known", who,
+                 parts);
+    const uint64_t head = (uint64_t)batch * TRAMBA_FRAMES_DESC_WORDS * 8;
+    if (parts & TRAMBA_RAGGED_IN)
+        TRAMBA_CHECK(packed_bytes >= head, "%s: %zu packed bytes do not hold the descriptor area of %d frames", who,
+                     packed_bytes, batch);
+    int64_t prev = -1, end = 0;                 // the previous map's offset and end
+    for (int b = 0; b < batch; ++b) {
+        const int64_t *d = desc + (size_t)b * TRAMBA_FRAMES_DESC_WORDS;
+        const int64_t h = d[kRgH], w = d[kRgW];
+        TRAMBA_CHECK(h >= 1 && w >= 1 && h <= TRAMBA_FRAME_MAX_DIM && w <= TRAMBA_FRAME_MAX_DIM,
+                     "%s: frame %d is %lldx%lld, a side outside 1 .. %d", who, b, (long long)h, (long long)w,
+                     TRAMBA_FRAME_MAX_DIM);
+        if (parts & TRAMBA_RAGGED_IN) {
+            const ResizeLayout L = resize_layout((int)h, (int)w, size, size);
+            const int64_t fo = d[kRgFrame], to = d[kRgTable];
+            TRAMBA_CHECK(fo >= (int64_t)head && to >= (int64_t)head,
+                         "%s: frame %d: offsets %lld / %lld lie inside the descriptor area of %llu bytes", who, b,
+                         (long long)fo, (long long)to, (unsigned long long)head);
+            TRAMBA_CHECK((uint64_t)fo <= packed_bytes && (uint64_t)(h * w * 3) <= packed_bytes - (uint64_t)fo &&
+                             (uint64_t)to <= packed_bytes && (uint64_t)L.words * 4 <= packed_bytes - (uint64_t)to,
+                         "%s: frame %d or its table lies outside the %zu packed bytes", who, b, packed_bytes);
+            TRAMBA_CHECK(to % 4 == 0, "%s: frame %d: table offset %lld is not aligned to 4 bytes", who, b, (long long)to);
+            TRAMBA_CHECK(d[kRgKx] == L.kx && d[kRgKy] == L.ky,
+                         "%s: frame %d: taps %lld / %lld, the table of %lldx%lld -> %d has %d / %d", who, b,
+                         (long long)d[kRgKx], (long long)d[kRgKy], (long long)h, (long long)w, size, L.kx, L.ky);
+        }
+        if (parts & TRAMBA_RAGGED_OUT) {
+            const int64_t oo = d[kRgOut];
+            TRAMBA_CHECK(oo > prev, "%s: map %d: output offset %lld is not increasing", who, b, (long long)oo);
+            TRAMBA_CHECK(oo % 16 == 0, "%s: map %d: output offset %lld is not aligned to 16 bytes", who, b, (long long)oo);
+            TRAMBA_CHECK(oo >= end, "%s: map %d at %lld would overlap map %d, which ends at %lld", who, b, (long long)oo, b - 1,
+                         (long long)end);
+            TRAMBA_CHECK((uint64_t)oo <= out_capacity && (uint64_t)(h * w) <= out_capacity - (uint64_t)oo,
+                         "%s: map %d ends at %lld, above the capacity of %zu bytes", who, b, (long long)(oo + h * w),
+                         out_capacity);
+            TRAMBA_CHECK(d[kRgRh] == (int64_t)f32_bits((float)size / (float)h) &&
+                             d[kRgRw] == (int64_t)f32_bits((float)size / (float)w),
+                         "%s: map %d: the scale words are not the fp32 bits of %d / %lld and %d / %lld", who, b, size,
+                         (long long)h, size, (long long)w);
+            prev = oo;
+            end = oo + h * w;
+        }
+    }
+    return TRAMBA_OK;
+}
+
 }  // namespace tramba
 
 using namespace tramba;
@@ -313,6 +467,28 @@ extern "C" int tramba_resize_table(int in_h, int in_w, int out_h, int out_w, con
     return TRAMBA_OK;
 }
 
+// A workgroup takes `band` output rows x `slab` output columns of one frame: at most kFrThreads * kFrMaxAcc outputs.  The
+// geometry is a function of (batch, output size) only, which is what lets the ragged entry share it.
+struct FrameGeometry {
+    int slab, band, chunk;
+    dim3 grid;
+    size_t lds;
+};
+
+static FrameGeometry frame_geometry(int batch, int out_h, int out_w)
+{
+    FrameGeometry g;
+    const int slab_max = kFrThreads * kFrMaxAcc / 3, nslab = (out_w + slab_max - 1) / slab_max;
+    g.slab = (out_w + nslab - 1) / nslab;
+    const int band_max = kFrThreads * kFrMaxAcc / (3 * g.slab);
+    const int band = (int)((long long)out_h * nslab * batch / kFrWantBlocks);
+    g.band = band < 1 ? 1 : (band > band_max ? band_max : band);
+    g.chunk = kFrLdsBytes / (3 * g.slab);        // >= 16 input rows per LDS chunk
+    g.grid = dim3(nslab, (out_h + g.band - 1) / g.band, batch);
+    g.lds = (size_t)g.chunk * 3 * g.slab;
+    return g;
+}
+
 extern "C" int tramba_frames_to_input(const unsigned char *frames, const int *table, float *out, int batch, int h, int w,
                                       int out_h, int out_w, int bgr, void *stream)
 {
@@ -322,16 +498,9 @@ extern "C" int tramba_frames_to_input(const unsigned char *frames, const int *ta
                  "frames_to_input: %dx%d -> %dx%d outside 1 .. %d per frame side, 1 .. %d per output side", h, w, out_h,
                  out_w, TRAMBA_FRAME_MAX_DIM, TRAMBA_FRAME_MAX_OUT);
     const ResizeLayout L = resize_layout(h, w, out_h, out_w);
-    // a workgroup takes `band` output rows x `slab` output columns of one frame: at most kFrThreads * kFrMaxAcc outputs
-    const int slab_max = kFrThreads * kFrMaxAcc / 3, nslab = (out_w + slab_max - 1) / slab_max;
-    const int slab = (out_w + nslab - 1) / nslab;
-    const int band_max = kFrThreads * kFrMaxAcc / (3 * slab);
-    int band = (int)((long long)out_h * nslab * batch / kFrWantBlocks);
-    band = band < 1 ? 1 : (band > band_max ? band_max : band);
-    const int chunk = kFrLdsBytes / (3 * slab);        // >= 16 input rows per LDS chunk
-    const dim3 grid(nslab, (out_h + band - 1) / band, batch);
-    hipLaunchKernelGGL(frames_to_input_kernel, grid, dim3(kFrThreads), (size_t)chunk * 3 * slab, (hipStream_t)stream, frames,
-                       table, out, h, w, out_h, out_w, L.kx, L.ky, slab, band, chunk, bgr ? 1 : 0);
+    const FrameGeometry g = frame_geometry(batch, out_h, out_w);
+    hipLaunchKernelGGL(frames_to_input_kernel, g.grid, dim3(kFrThreads), g.lds, (hipStream_t)stream, frames, table, out, h, w,
+                       out_h, out_w, L.kx, L.ky, g.slab, g.band, g.chunk, bgr ? 1 : 0);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -352,6 +521,43 @@ extern "C" int tramba_logits_to_u8(const void *logits, unsigned char *out, int b
     TRAMBA_DISPATCH_DTYPE(dtype, T,
                           hipLaunchKernelGGL(logits_to_u8_kernel<T>, grid, dim3(kU8Threads), 0, (hipStream_t)stream,
                                              reinterpret_cast<const T *>(logits), out, in_h, in_w, h, w, total, rh, rw));
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_frames_ragged_check(const int64_t *desc_host, int batch, int size, size_t packed_bytes,
+                                          size_t out_capacity, int parts)
+{
+    return ragged_check("frames_ragged_check", desc_host, batch, size, packed_bytes, out_capacity, parts);
+}
+
+extern "C" int tramba_frames_to_input_ragged(const unsigned char *packed, const int64_t *desc_host, size_t packed_bytes,
+                                             float *out, int batch, int size, int bgr, void *stream)
+{
+    TRAMBA_CHECK(packed && desc_host && out, "frames_to_input_ragged: null pointer");
+    TRAMBA_CHECK(aligned16(packed), "frames_to_input_ragged: the packed buffer is not aligned to 16 bytes");
+    const int rc = ragged_check("frames_to_input_ragged", desc_host, batch, size, packed_bytes, 0, TRAMBA_RAGGED_IN);
+    if (rc != TRAMBA_OK) return rc;
+    const FrameGeometry g = frame_geometry(batch, size, size);
+    hipLaunchKernelGGL(frames_to_input_ragged_kernel, g.grid, dim3(kFrThreads), g.lds, (hipStream_t)stream, packed, out, size,
+                       g.slab, g.band, g.chunk, bgr ? 1 : 0);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_logits_to_u8_ragged(const void *logits, const unsigned char *packed, const int64_t *desc_host,
+                                          unsigned char *out, size_t out_capacity, int batch, int size, int dtype, void *stream)
+{
+    TRAMBA_CHECK(logits && packed && desc_host && out, "logits_to_u8_ragged: null pointer");
+    TRAMBA_CHECK(aligned16(packed) && aligned16(out),
+                 "logits_to_u8_ragged: the packed or the output buffer is not aligned to 16 bytes");
+    const int rc = ragged_check("logits_to_u8_ragged", desc_host, batch, size, 0, out_capacity, TRAMBA_RAGGED_OUT);
+    if (rc != TRAMBA_OK) return rc;
+    const size_t per_block = (size_t)kU8Threads * kU8Bytes, blocks = (out_capacity + per_block - 1) / per_block;
+    TRAMBA_CHECK(blocks <= 0x7fffffff, "logits_to_u8_ragged: a capacity of %zu bytes is too large", out_capacity);
+    TRAMBA_DISPATCH_DTYPE(dtype, T,
+                          hipLaunchKernelGGL(logits_to_u8_ragged_kernel<T>, dim3((unsigned)blocks), dim3(kU8Threads), 0,
+                                             (hipStream_t)stream, reinterpret_cast<const T *>(logits), packed, out, batch, size));
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -13,7 +13,8 @@ WeightedFmeasure needs an exact Euclidean distance transform with nearest-pixel 
 `tramba_weighted_f_sums` reduces the error spreading, the 7x7 Gaussian, the pixel weights and the weighted sums to three
 numbers per image; R, P and Q are finished on the host in fp64.  It shares the upload of the other four (one copy of a
 host map per step).  `WeightedFmeasure(host=True)` keeps the reference's scipy path, for A/B and for hosts without a
-device.  `evaluate_folder` is the package's counterpart of Evaluation/evaluate_TSOD.py for one folder pair.
+device.  `evaluate_folder` is the package's counterpart of Evaluation/evaluate_TSOD.py for one folder pair;
+`evaluate_dataset` gives the same numbers for a model and a dataset root without the PNG round trip between the two.
 """
 import os
 import struct
@@ -391,6 +392,11 @@ def evaluate_folder(salmap_root, gt_root, model=None, dataset=None, save_dir=Non
                 ahead.append(pool.submit(_load_pair, pairs[i + 2 * workers]))
             for m in (fm, wfm, sm, em, mae):
                 m.step(pred=pred, gt=gt)
+    return _folder_results(fm, wfm, sm, em, mae, model, dataset, save_dir)
+
+
+def _folder_results(fm, wfm, sm, em, mae, model, dataset, save_dir, weighted=True):
+    """evaluate_folder's results dictionary from the five stepped metric objects"""
     (f, fnr), e = fm.get_results(), em.get_results()["em"]
     precision, recall = np.array(f["pr"]["p"], np.float32), np.array(f["pr"]["r"], np.float32)
     if save_dir is not None:
@@ -401,10 +407,62 @@ def evaluate_folder(salmap_root, gt_root, model=None, dataset=None, save_dir=Non
     return {
         "model": model, "dataset": dataset,
         "Smeasure_r": r4(sm.get_results()["sm"]),
-        "Wmeasure_r": r4(wfm.get_results()["wfm"]),
+        "Wmeasure_r": r4(wfm.get_results()["wfm"]) if weighted else None,
         "MAE_r": r4(mae.get_results()["mae"]),
         "adpEm_r": r4(e["adp"]), "meanEm_r": r4(e["curve"].mean()), "maxEm_r": r4(e["curve"].max()),
         "adpFm_r": r4(f["fm"]["adp"]), "meanFm_r": r4(f["fm"]["curve"].mean()), "maxFm_r": r4(f["fm"]["curve"].max()),
         "fnr_r": r4(fnr),
         "precision": precision, "recall": recall,
     }
+
+
+def _read_pair(paths):
+    """(image path, mask path) -> (RGB frame (h, w, 3) u8, mask (h, w) bool).  The mask is convert("L") != 0, which is what
+    `_load_pair` followed by `_upload` reduces to: dividing by max + 1e-8 keeps every non-zero pixel non-zero."""
+    from PIL import Image
+    from .infer import _read_rgb
+    with Image.open(paths[1]) as im:
+        mask = np.asarray(im.convert("L")) != 0
+    return _read_rgb(paths[0]), mask
+
+
+def evaluate_dataset(model, root, img_size=384, batch=4, graph=True, workers=8, weighted=True, save_path=None):
+    """The reference's two-step flow (test_TSOD.py, then Evaluation/evaluate_TSOD.py) for `<root>/Test/image` and
+    `<root>/Test/mask` (`data.RGB_Dataset`'s pairing, pairs of different sizes dropped) without leaving the device: the
+    pairs are decoded on a pool of at most 16 threads, consecutive groups of `batch` images in the loader's natural order go
+    through `infer.FramePredictor`'s mixed-size path, and the five metric objects are stepped, in that order, on each
+    (h, w) uint8 map taken straight from the predictor's packed output, as u / 255 in fp32 (a 256-entry table made on the
+    host, so the division is numpy's, as `_load_pair`'s is).  Returns `evaluate_folder`'s dictionary; every entry equals,
+    exactly, `evaluate_folder(P, <root>/Test/mask)` for the PNGs P of `infer.predict_folder(..., batch=batch)` when both step
+    the images in the same order (`evaluate_folder` sorts the file names as plain strings and pairs by full name).
+    weighted=False leaves the weighted F-measure out (Wmeasure_r None).  With `save_path` the maps are also written there as
+    <stem>.png, the files `predict_folder` writes."""
+    from . import data, infer
+    ds = data.RGB_Dataset(root, ["Test"], img_size, "Test")
+    pairs = dict(zip(ds.images, ds.gts))
+    fm, wfm, sm, em, mae = Fmeasure_and_FNR(), WeightedFmeasure(), Smeasure(), Emeasure(), MAE()
+    was_training = model.training
+    model.eval()
+    pred = infer.FramePredictor(model, img_size, "RGB", graph=graph)
+    unit = torch.from_numpy(np.arange(256, dtype=np.float32) / 255).to(pred.device)
+    workers = max(1, min(16, int(workers)))
+    infer.folder_groups([], batch)                # refuses a bad batch before anything is read
+    pending = []
+    if save_path is not None:
+        os.makedirs(save_path, exist_ok=True)
+    with ThreadPoolExecutor(max_workers=workers) as pool, torch.cuda.device(pred.device):
+        def use(path, m, mask):
+            p, g = unit[m.int()], torch.from_numpy(mask).to(pred.device)
+            for metric in (fm, wfm, sm, em, mae) if weighted else (fm, sm, em, mae):
+                metric.step(pred=p, gt=g)
+            if save_path is not None:
+                pending.append(pool.submit(write_png_gray8, os.path.join(save_path, data._stem(path) + ".png"),
+                                           m.cpu().numpy()))
+                while len(pending) > 2 * workers + batch:
+                    pending.pop(0).result()
+
+        infer._predict_groups(pred, ds.images, batch, pool, workers, lambda p: _read_pair((p, pairs[p])), use)
+        for f in pending:
+            f.result()
+    model.train(was_training)
+    return _folder_results(fm, wfm, sm, em, mae, None, None, None, weighted)

@@ -76,6 +76,9 @@ SIGNATURES = {
     "tramba_resize_table": (c_int, [c_int] * 4 + [c_vp] * 3 + [ctypes.c_size_t]),
     "tramba_frames_to_input": (c_int, [c_vp] * 3 + [c_int] * 6 + [c_vp]),
     "tramba_logits_to_u8": (c_int, [c_vp] * 2 + [c_int] * 6 + [c_vp]),
+    "tramba_frames_ragged_check": (c_int, [c_vp, c_int, c_int, ctypes.c_size_t, ctypes.c_size_t, c_int]),
+    "tramba_frames_to_input_ragged": (c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, c_int, c_int, c_int, c_vp]),
+    "tramba_logits_to_u8_ragged": (c_int, [c_vp] * 4 + [ctypes.c_size_t] + [c_int] * 3 + [c_vp]),
     "tramba_augment_source_table_words": (ctypes.c_size_t, [c_int] * 3),
     "tramba_augment_source_table": (c_int, [c_int] * 3 + [c_vp, ctypes.c_size_t]),
     "tramba_augment_size_table_words": (ctypes.c_size_t, [c_int]),
@@ -789,6 +792,61 @@ def logits_to_u8(logits, h: int, w: int):
     b, _, ih, iw = logits.shape
     out = torch.empty((b, h, w), dtype=torch.uint8, device=logits.device)
     _check(lib().tramba_logits_to_u8(_ptr(logits), _ptr(out), b, ih, iw, h, w, dt(logits), _stream()), "logits_to_u8")
+    return out
+
+
+FRAMES_DESC_WORDS = 16                               # TRAMBA_FRAMES_DESC_WORDS
+RAGGED_IN, RAGGED_OUT = 1, 2                         # TRAMBA_RAGGED_IN / TRAMBA_RAGGED_OUT
+
+
+def _ragged_desc(what, desc_host):
+    desc_host = np.ascontiguousarray(desc_host, dtype=np.int64)
+    if desc_host.ndim != 2 or desc_host.shape[1] != FRAMES_DESC_WORDS or not 1 <= desc_host.shape[0] <= 65535:
+        raise TrambaHipError(f"{what}: descriptors must be (B, {FRAMES_DESC_WORDS}) with 1 <= B <= 65535")
+    return desc_host
+
+
+def frames_ragged_check(desc_host: np.ndarray, size: int, packed_bytes: int, out_capacity: int,
+                        parts: int = RAGGED_IN | RAGGED_OUT):
+    """the library's check of a packed batch's host descriptors (layout: include/tramba_hip.h) against the sizes of the
+    packed buffer and of the output buffer; raises TrambaHipError.  Call it before replaying a graph, where no entry runs."""
+    desc_host = _ragged_desc("frames_ragged_check", desc_host)
+    _check(lib().tramba_frames_ragged_check(desc_host.ctypes.data, desc_host.shape[0], size, packed_bytes, out_capacity,
+                                            parts), "frames_ragged_check")
+
+
+def frames_to_input_ragged(packed, desc_host: np.ndarray, size: int, bgr: bool = False):
+    """packed (N,) u8 on the device (descriptors, tables, frames of any sizes), desc_host its (B, FRAMES_DESC_WORDS) int64
+    host copy -> (B, 3, size, size) f32: row i is frames_to_input of frame i alone, bit for bit."""
+    if packed.dtype != torch.uint8 or packed.dim() != 1:
+        raise TrambaHipError(f"frames_to_input_ragged: packed must be a flat uint8 tensor, got {packed.dtype} {tuple(packed.shape)}")
+    _dev(packed)
+    desc_host = _ragged_desc("frames_to_input_ragged", desc_host)
+    b = desc_host.shape[0]
+    if not 3 <= size <= FRAME_MAX_OUT:
+        raise TrambaHipError(f"frames_to_input_ragged: size {size} outside 3 .. {FRAME_MAX_OUT}")
+    out = torch.empty((b, 3, size, size), dtype=torch.float32, device=packed.device)
+    _check(lib().tramba_frames_to_input_ragged(_ptr(packed), desc_host.ctypes.data, packed.numel(), _ptr(out), b, size,
+                                               int(bool(bgr)), _stream()), "frames_to_input_ragged")
+    return out
+
+
+def logits_to_u8_ragged(logits, packed, desc_host: np.ndarray, out):
+    """logits (B, 1, S, S) f32 / f16 / bf16, packed: a device buffer that starts with the descriptors, desc_host their host
+    copy, out: a flat u8 device buffer -> out, with map i = logits_to_u8(logits[i:i+1], h_i, w_i) at the byte offset
+    descriptor i names.  Bytes of out between the maps are left as they are."""
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.shape[2] != logits.shape[3]:
+        raise TrambaHipError(f"logits_to_u8_ragged: logits must be (B, 1, S, S), got {tuple(logits.shape)}")
+    if packed.dtype != torch.uint8 or packed.dim() != 1 or out.dtype != torch.uint8 or out.dim() != 1:
+        raise TrambaHipError("logits_to_u8_ragged: packed and out must be flat uint8 tensors")
+    logits = logits.contiguous()
+    _dev(logits, packed, out)
+    desc_host = _ragged_desc("logits_to_u8_ragged", desc_host)
+    b, _, s, _ = logits.shape
+    if desc_host.shape[0] != b or packed.numel() < desc_host.nbytes:
+        raise TrambaHipError(f"logits_to_u8_ragged: {desc_host.shape[0]} descriptors for {b} logit planes")
+    _check(lib().tramba_logits_to_u8_ragged(_ptr(logits), _ptr(packed), desc_host.ctypes.data, _ptr(out), out.numel(), b, s,
+                                            dt(logits), _stream()), "logits_to_u8_ragged")
     return out
 
 
