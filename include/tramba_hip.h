@@ -104,6 +104,7 @@ int tramba_tune_get(int knob);
                                         else the entry's own rule.  0 = the library's rule; 7 = 64x64 LDS-DMA tiles on 4 stages (plain
                                         entry only); 13 / 14 = the same on 2 / 3 stages; 16 / 17 = producer / consumer tiles on 3 / 4
                                         stages; 18 = the rule without the producer / consumer and weight-stationary forms (the r03
+                                        kernels; it alone also reaches tramba_linear2_cl and tramba_conv3x3s2_cl: their register-staged
                                         kernels); 19 = weight-stationary wherever it can run.  Other values are refused. */
 #define TRAMBA_TUNE_MAILBOX_SKIP 4   /* tests only: > 0 withholds the carry hand-over of that tile (chain order) in the fused scans, so that
                                         the wave waiting for it runs out of polls (~0.1 s) and the device error word is raised; 0 = off */
@@ -111,7 +112,8 @@ int tramba_tune_get(int knob);
 #define TRAMBA_TUNE_DW_FORM 6        /* 7x7 depth-wise stencil and its weight gradient: 1 = the r03 kernels (one output row per thread / tap row outer),
                                         0 = the kernels that march down a band of rows (default) */
 #define TRAMBA_TUNE_DW_ROWS 7        /* rows per band of the marching 7x7 kernels (0 = the library's choice) */
-#define TRAMBA_TUNE_COUNT 8
+#define TRAMBA_TUNE_MERGE_PW 8       /* pixels per wave of the streaming merge: 4 / 8 / 16 force one (0 = the library's choice, by the wave count) */
+#define TRAMBA_TUNE_COUNT 9
 #define TRAMBA_PROF_SCAN_BOUNDARY 0
 #define TRAMBA_PROF_SCAN_FUSED 1
 #define TRAMBA_PROF_GEMM 2          /* tramba_linear_cl (1x1-conv projections) */

@@ -923,12 +923,34 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
 // hosts one loader wave and one multiplier wave (a workgroup's waves go to the SIMDs cyclically).
 // LNIN: the row statistics are read back from the staged tile by the loader waves (they have nothing else to do between
 // their DMA issue and the next barrier), same arithmetic and summation order as linear_dma_kernel: bit-identical results.
+//
+// ASRC: where the A tile of a K step comes from.  Only the loader waves 4-5 see it -- the multiplier waves read the same
+// staged tile, run the same MFMA sequence and the same epilogue, so each form is bit-identical to the register-staged kernel
+// it replaces (linear_lean_kernel with two sources, linear_tiled_kernel<.., CONV>: 64-deep steps in the same K order).
+//   A_TWO   A = [x (M, K1) | x2 (M, K - K1)], both parts whole K steps: two descriptors, a wave-uniform select per step;
+//   A_CONV  implicit GEMM of a 3x3 / stride-2 / pad-1 convolution (ConvGeom, Cin % 64 == 0: step kt lies inside tap
+//           kt / (Cin / 64)).  One descriptor over the whole input map; a lane keeps, per piece, the byte offset of its row's
+//           output pixel at tap (0, 0) and that pixel's input coordinates; a step adds the wave-uniform offset of its tap and
+//           channel run.  A tap outside the map, or a row past M, gets an out-of-range offset: the LDS-DMA writes zeros there
+//           (the zero padding; as the marching 7x7 stencils of norm_conv.hip do it).  The whole offset rides in the VECTOR
+//           offset, which is what the hardware range-checks.  Always four pieces per step: the counted waits stay valid.
+enum { A_PLAIN = 0, A_TWO = 1, A_CONV = 2 };
+struct ASrc {
+    const void *x2;     // A_TWO: the second source
+    int k1;             // A_TWO: row length of the first
+    ConvGeom cg;        // A_CONV
+    unsigned abytes;    // A_CONV: bytes of the input map (< 2^31, host-checked)
+};
+
 #define TRAMBA_DSR128_(OUT, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(OUT) : "v"(ADDR) : "memory")
-template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false>
-__global__ __launch_bounds__(512) void linear_pc_kernel(const T *__restrict__ x, const T *__restrict__ w,
+// (A_CONV on 3 stages asks for six waves per SIMD = three workgroups per CU by name: its loader code is a little longer, and left alone the
+//  register allocator ends two registers above the 80 that the other forms need, with unused holes below)
+template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false, int ASRC = A_PLAIN>
+__global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void linear_pc_kernel(const T *__restrict__ x, const T *__restrict__ w,
                                                        const float *__restrict__ bias, const T *__restrict__ res,
                                                        TO *__restrict__ y, long M, int N, int K, int act,
-                                                       LnIn li = LnIn{nullptr, 0.f}, TO *__restrict__ y_pre = nullptr)
+                                                       LnIn li = LnIn{nullptr, 0.f}, TO *__restrict__ y_pre = nullptr,
+                                                       ASrc as = ASrc{nullptr, 0, ConvGeom{0, 0, 0, 0, 0}, 0u})
 {
 #if defined(__HIP_DEVICE_COMPILE__)   // (vector-register asm in a kernel template: see ss2d_scan_dma_kernel)
     constexpr int BM = 64, BN = 64;
@@ -960,27 +982,107 @@ __global__ __launch_bounds__(512) void linear_pc_kernel(const T *__restrict__ x,
     const int nrows = N - n0 < BN ? N - n0 : BN;
     // loader waves 4-5 stage A (rows of x), 6-7 stage B (rows of w): one descriptor per wave, wave-uniform
     const bool stage_b = cw >= 2;
-    const __amdgpu_buffer_rsrc_t rs = stage_b ? make_rsrc(w + (long)n0 * K, (unsigned)nrows * rowb)
-                                              : make_rsrc(x + m0 * K, (unsigned)mrows * rowb);
+    __amdgpu_buffer_rsrc_t rs, rsx;               // (rsx: A_TWO only)
+    // Per-lane loader state beyond voff shares its registers with the fragment read addresses of the multiplier waves (lx / ly
+    // below become aad / bad there).  A wave is one or the other for life, but the compiler sees ONE K loop with a branch per
+    // step and would keep both sets live throughout: 84 / 88 VGPRs instead of 80, i.e. two workgroups on a CU instead of three.
     unsigned voff[4];
+    unsigned lx[4] = {0u, 0u, 0u, 0u}, ly[4] = {0u, 0u, 0u, 0u};
+    unsigned(&voff2)[4] = lx;                     // A_TWO: my offsets in the second source
+    unsigned(&chy)[4] = lx, (&cwx)[4] = ly;       // A_CONV: input row / column (as int) of my rows' output pixels at tap (0, 0)
+    int nsw = nk;                                 // A_TWO: K steps served by rs / voff, the rest by rsx / voff2
+    unsigned hlim = 0xffffffffu, wlim = 0xffffffffu;   // A_CONV: the map's extent (a weight wave: no limit, chy = cwx = 0)
+    int ccs = 0, cdy = 0, cdx = 0;                // A_CONV: channel run and tap of the next step to be issued (wave-uniform)
+    if constexpr (ASRC == A_TWO) {
+        const int ka = as.k1;
+        const unsigned rowa = (unsigned)ka * 2u, rowa2 = (unsigned)(K - ka) * 2u;
+        rs = stage_b ? make_rsrc(w + (long)n0 * K, (unsigned)nrows * rowb) : make_rsrc(x + m0 * ka, (unsigned)mrows * rowa);
+        rsx = stage_b ? rs : make_rsrc((const T *)as.x2 + m0 * (K - ka), (unsigned)mrows * rowa2);
+        if (!stage_b) nsw = ka / kBK;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = ((cw & 1) * 4 + j) * 8 + (lane >> 3);
-        const int c = (lane & 7) ^ ((row >> 1) & 7);
-        voff[j] = (unsigned)row * rowb + (unsigned)c * 16u;
+        for (int j = 0; j < 4; ++j) {
+            const int row = ((cw & 1) * 4 + j) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            voff[j] = (unsigned)row * (stage_b ? rowb : rowa) + (unsigned)c * 16u;
+            voff2[j] = (unsigned)row * (stage_b ? rowb : rowa2) + (unsigned)c * 16u;
+        }
+    } else if constexpr (ASRC == A_CONV) {
+        rs = stage_b ? make_rsrc(w + (long)n0 * K, (unsigned)nrows * rowb) : make_rsrc(x, as.abytes);
+        if (!stage_b) {
+            hlim = (unsigned)as.cg.hin;
+            wlim = (unsigned)as.cg.win;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = ((cw & 1) * 4 + j) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            if (stage_b) {
+                voff[j] = (unsigned)row * rowb + (unsigned)c * 16u;
+                chy[j] = cwx[j] = 0u;
+            } else {
+                const long gr = m0 + row;
+                const bool ok = gr < M;
+                const unsigned pix = ok ? (unsigned)gr : 0u;            // (b*hout + ho)*wout + wo, M < 2^22 (grid limit)
+                const unsigned wo = pix % (unsigned)as.cg.wout, t = pix / (unsigned)as.cg.wout;
+                const unsigned ho = t % (unsigned)as.cg.hout, b = t / (unsigned)as.cg.hout;
+                chy[j] = (unsigned)(ok ? 2 * (int)ho - 1 : -4);         // a row past M: every tap above the map
+                cwx[j] = (unsigned)(2 * (int)wo - 1);
+                // byte offset of (b, chy, cwx, 0) + my chunk, modulo 2^32: the sum with a tap inside the map is exact
+                voff[j] = ((b * (unsigned)as.cg.hin + chy[j]) * (unsigned)as.cg.win + cwx[j]) * ((unsigned)as.cg.cin * 2u) +
+                          (unsigned)c * 16u;
+            }
+        }
+    } else {
+        rs = stage_b ? make_rsrc(w + (long)n0 * K, (unsigned)nrows * rowb) : make_rsrc(x + m0 * K, (unsigned)mrows * rowb);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int row = ((cw & 1) * 4 + j) * 8 + (lane >> 3);
+            const int c = (lane & 7) ^ ((row >> 1) & 7);
+            voff[j] = (unsigned)row * rowb + (unsigned)c * 16u;
+        }
     }
     unsigned char *mine = lds + (stage_b ? BM * kBK * 2 : 0) + (cw & 1) * 4096;   // my four pieces inside a stage
-    auto issue = [&](int kt, int stg) {
-        const unsigned so = (unsigned)kt * (kBK * 2);
+    auto issue = [&](int kt, int stg) {   // (A_CONV: called once per K step, in K order)
+        if constexpr (ASRC == A_TWO) {
+            // a wave-uniform SELECT of descriptor, step offset and per-lane offset (not a branch around the DMA)
+            const bool first = kt < nsw;
+            const __amdgpu_buffer_rsrc_t rsel = first ? rs : rsx;
+            const unsigned so = (unsigned)(first ? kt : kt - nsw) * (kBK * 2);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16, voff[j], so, 0,
-                                                     0);
+            for (int j = 0; j < 4; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsel, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16,
+                                                         first ? voff[j] : voff2[j], so, 0, 0);
+        } else if constexpr (ASRC == A_CONV) {
+            // step offset: the K step for a weight wave, (tap row, tap column, channel run) for an activation wave
+            const unsigned so = stage_b ? (unsigned)kt * (kBK * 2)
+                                        : (unsigned)((cdy * as.cg.win + cdx) * as.cg.cin + ccs * kBK) * 2u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                // (one unsigned compare per axis: a negative coordinate wraps past any map size)
+                const unsigned hy = chy[j] + (unsigned)cdy, wx = cwx[j] + (unsigned)cdx;
+                unsigned out = (hy < hlim && wx < wlim) ? 0u : 1u;
+                // outside: bit 31 set = past any map the host admits.  (An OR of the shifted flag, opaque to the compiler: as a
+                // select it keeps the constant 2^31 in a vector register for the whole loop.)
+                asm volatile("" : "+v"(out));
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16,
+                                                         (voff[j] + so) | (out << 31), 0, 0, 0);
+            }
+            if (++ccs == as.cg.cin / kBK) {
+                ccs = 0;
+                if (++cdx == 3) { cdx = 0; ++cdy; }
+            }
+        } else {
+            const unsigned so = (unsigned)kt * (kBK * 2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void *)(mine + stg * TILE_BYTES + j * 1024), 16, voff[j], so,
+                                                         0, 0);
+        }
     };
     // fragment read addresses (absolute LDS bytes) of the four 16-deep slices: chunk (2 kk + hi) ^ ((row >> 1) & 7)
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds;
-    unsigned aad[4], bad[4];
-    {
+    unsigned(&aad)[4] = lx, (&bad)[4] = ly;          // (shared with the loader state above)
+    if (ASRC == A_PLAIN || !loader) {
         const int ra_ = wm * 32 + r32, rb_ = wn * 32 + r32;
         const unsigned a0 = lbase + (unsigned)(ra_ * 128 + ((hi ^ ((ra_ >> 1) & 7)) * 16));
         const unsigned b0 = lbase + (unsigned)(BM * kBK * 2 + rb_ * 128 + ((hi ^ ((rb_ >> 1) & 7)) * 16));
@@ -1523,10 +1625,23 @@ struct GemmPlan {
 
 // TRAMBA_TUNE_GEMM_TILE (the only place it is read) forces a form on the plain, LayerNorm-folded and dual-output entries
 // wherever the LDS-DMA kernels can run: 7 = DMA4 (plain entry only: the other two have no 4-stage LDS-DMA kernel and keep their
-// rule), 13 / 14 = DMA2 / DMA3, 16 / 17 = PC3 / PC4, 18 = the rule without the PC and WS forms (the r03 kernels), 19 = WS
-// wherever it can run, else the rule.  0 = the rule.
-static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool same_dtype)
+// rule), 13 / 14 = DMA2 / DMA3, 16 / 17 = PC3 / PC4, 18 = the rule without the PC and WS forms (the r03 kernels; the only value
+// the two-source and convolution entries look at: their register-staged kernels), 19 = WS wherever it can run, else the rule.
+// 0 = the rule.
+static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool same_dtype, bool a_dma = true)
 {
+    int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
+    // Two-source A operand and implicit-GEMM convolution (a_dma: the operand fits the LDS-DMA loaders -- both K parts whole
+    // steps / the input map within one descriptor): the producer / consumer kernel, whose loader waves alone carry the
+    // addressing, on the stage count of the plain rule.  Where the plain rule keeps linear_dma_kernel (K >= 2048 on 257-320
+    // tiles: 12.7 against 12.9 us for the plain GEMM, a tie) these stay on 3 producer / consumer stages -- linear_dma_kernel
+    // has no such loaders, and the convolution there (M = 2304, N = 512, K = 2304) is faster than on the tiled kernel all the
+    // same (scripts/bench_stragglers.py, profiles/stragglers_forms.txt).  Knob 18 = the register-staged kernels of r03.
+    if ((kind == GEMM_TWO_SRC || kind == GEMM_CONV) && a_dma && tune != 18 && k % 64 == 0 &&
+        (double)k * 2.0 * 128.0 < 2147483648.0) {
+        const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
+        return {pc_rule(tiles64, k, GEMM_PLAIN) == 4 ? GemmForm::PC4 : GemmForm::PC3, 0};
+    }
     if (kind == GEMM_TWO_SRC) return {GemmForm::LEAN, 0};
     // whole 64-deep K steps, and a 64-row operand panel within 32-bit byte offsets
     if (kind == GEMM_CONV || k % 64 != 0 || (double)k * 2.0 * 128.0 >= 2147483648.0) {
@@ -1534,7 +1649,6 @@ static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool sam
         if (big >= 2048 && k >= 1024) return {GemmForm::TILED128, 0};
         return {k <= 128 ? GemmForm::TILED64 : GemmForm::TILED64_PF3, 0};   // 1-2 K steps: a 2-stage ring, no padded dummy steps
     }
-    int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
     if (tune == 7 && kind != GEMM_PLAIN) tune = 0;
     if (tune == 0 || tune == 19) {
         const bool ws_act = act == TRAMBA_ACT_NONE || act == TRAMBA_ACT_GELU || act == TRAMBA_ACT_SILU;
@@ -1572,6 +1686,7 @@ struct GemmArgs {
     const void *x2 = nullptr;     // two-source entry: A = [x (m, k1) | x2 (m, k - k1)]
     int k1 = 0;
     ConvGeom cg{0, 0, 0, 0, 0};   // implicit-GEMM convolution
+    unsigned abytes = 0;          // implicit-GEMM convolution on the LDS-DMA loaders: bytes of the input map
 };
 
 template <typename T, typename TO, bool LNIN = false, bool DUAL = false, bool CONV = false>
@@ -1587,11 +1702,26 @@ static void launch_gemm(const GemmPlan &p, const GemmArgs &a, hipStream_t s)
         launch_ws_k<T, LNIN, DUAL>(p.ncw, a.x, a.w, a.bias, a.res, a.y, m, n, k, act, a.li, a.y_pre, s);
         break;
     case GemmForm::PC3:
-        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+    case GemmForm::PC4: {
+        const bool four = p.form == GemmForm::PC4;
+        if constexpr (CONV) {
+            const ASrc as{nullptr, 0, a.cg, a.abytes};
+            if (four) hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, false, false, A_CONV>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre, as);
+            else hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, false, false, A_CONV>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre, as);
+            break;
+        }
+        if constexpr (!LNIN && !DUAL) {
+            if (a.x2) {
+                const ASrc as{a.x2, a.k1, a.cg, 0u};
+                if (four) hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, false, false, A_TWO>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre, as);
+                else hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, false, false, A_TWO>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre, as);
+                break;
+            }
+        }
+        if (four) hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+        else hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         break;
-    case GemmForm::PC4:
-        hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
-        break;
+    }
     case GemmForm::DMA2:
         hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2, LNIN, DUAL>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         break;
@@ -1814,9 +1944,12 @@ extern "C" int tramba_conv3x3s2_cl(const void *x, const void *w, const float *bi
     const long m = (long)batch * cg.hout * cg.wout;
     TRAMBA_CHECK((m + 63) / 64 <= 65535, "conv3x3s2_cl: too many output pixels");
     hipStream_t s = (hipStream_t)stream;
-    const GemmPlan p = gemm_plan(GEMM_CONV, m, cout, 9 * cin, TRAMBA_ACT_NONE, true);
+    // the LDS-DMA loaders address the whole input map through one descriptor with 32-bit byte offsets (2^31 = out of range)
+    const double xbytes = (double)batch * hin * win * cin * 2.0;
+    const GemmPlan p = gemm_plan(GEMM_CONV, m, cout, 9 * cin, TRAMBA_ACT_NONE, true, xbytes < 2147483648.0);
     GemmArgs a{x, w, bias, nullptr, y, m, cout, 9 * cin, TRAMBA_ACT_NONE};
     a.cg = cg;
+    a.abytes = (unsigned)xbytes;
     if (dtype == TRAMBA_BF16) launch_gemm<__hip_bfloat16, __hip_bfloat16, false, false, true>(p, a, s);
     else launch_gemm<__half, __half, false, false, true>(p, a, s);
     TRAMBA_LAUNCH_CHECK();

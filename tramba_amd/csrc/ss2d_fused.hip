@@ -1991,8 +1991,8 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
     const int nit_need = (d + kWave * v - 1) / (kWave * v);
     const int nit = nit_need <= 1 ? 1 : (nit_need <= 2 ? 2 : (nit_need <= 4 ? 4 : 8));
     // Streaming form (measured, scripts/bench_scan.py): wins where one batch covers a pixel (K <= 4), the row
-    // is at most two wave iterations and the map is large enough to fill the chip with 16-pixel waves
-    // (6 TB/s on 96x96 D=256); elsewhere one wave per pixel is faster.
+    // is at most two wave iterations and the map is large enough to fill the chip (>= 8192 pixels; pixels per wave: below);
+    // elsewhere one wave per pixel is faster.
     ProfScope prof(TRAMBA_PROF_MERGE, s, (double)batch * k * l * (double)d * dtype_size(ys_dtype) +
                                               (double)batch * l * (double)d * dtype_size(dtype));
     const bool sum_only = eps < 0.f;   // no LayerNorm: only the per-pixel form implements it
@@ -2000,7 +2000,17 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
     const bool stream_ok = !sum_only && nit <= 2 && k <= 8 && (double)k * l * d * 4.0 < 4294967296.0;
     const bool stream_form = stream_ok && (tune == 2 || (tune == 0 && k <= 4 && npix >= 8192));
     const bool wide = k > 4;               // 8 rows per batch, 4 pixels per wave (a Helix pixel lists >= 6 entries)
-    const int pw = wide ? 4 : 16;
+    // pixels per wave (the kernel's P; sums and LayerNorm are per pixel, so the output does not depend on it): the most of
+    // 16 / 8 / 4 that still leaves four waves per SIMD (4096 waves on 256 CUs) -- the streaming form hides its gather latency
+    // by occupancy, not by depth.  scripts/bench_stragglers.py, profiles/stragglers_forms.txt, us at 4 / 8 / 16: 9216 pixels
+    // (48x48 batch 4, D = 512) 15.1 / 19.2 / 28.8, (96x96 batch 1, D = 256) 9.7 / 12.8 / 20.5; 36864 pixels 20.4 / 20.8 / 26.1.
+    // The Helix tables (8-row batches) keep 4.  TRAMBA_TUNE_MERGE_PW 4 / 8 / 16 forces one.
+    const int pw_tune = tramba_tune_get(TRAMBA_TUNE_MERGE_PW);
+    TRAMBA_CHECK(pw_tune == 0 || pw_tune == 4 || pw_tune == 8 || pw_tune == 16, "TRAMBA_TUNE_MERGE_PW %d: 0, 4, 8 or 16", pw_tune);
+    int pw = wide ? 4 : 16;
+    if (pw_tune > 0) pw = pw_tune;
+    else
+        while (pw > 4 && (long)batch * ((l + pw - 1) / pw) < 4096) pw >>= 1;
     const int nchunk = (l + pw - 1) / pw;
     const long nwaves = (long)batch * nchunk;
     int hs = 0;                            // many-to-one tables on square maps: image rows centre-out

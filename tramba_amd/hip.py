@@ -264,6 +264,7 @@ def scan_order(family: str, h: int, w: int, device, param: int = 0) -> ScanOrder
 
 # ----------------------------------------------------------------------------- profiling / tuning
 TUNE_MERGE_FORM, TUNE_SCAN_FORM, TUNE_SCAN_W, TUNE_GEMM_TILE, TUNE_MAILBOX_SKIP, TUNE_DW_FORM, TUNE_DW_ROWS = 0, 1, 2, 3, 4, 6, 7   # (5 retired)
+TUNE_MERGE_PW = 8
 
 
 def device_error():
