@@ -588,6 +588,40 @@ int tramba_sod_loss_grad(const float *logits, const float *label, const float *c
 int tramba_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                      float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2, double eps,
                      double weight_decay, void *stream);
+/* ---- step control: gradient accumulation, norm clipping and the skip of a non-finite step, decided on the device ----
+ * (No reference counterpart: train.py steps once per batch.)  The record lives in device memory, owned by the caller; the
+ * entries below read and write it, so that a replayed hipGraph of a whole optimisation step needs no host value that changes
+ * from step to step.  Zero-filled = "no micro-batch yet, nothing skipped". */
+typedef struct tramba_step_ctl {
+    float norm;              /* L2 norm of the MEAN gradient before clipping (what torch's clip_grad_norm_ returns) */
+    float scale;             /* what the optimizer multiplies the accumulated gradient by: mean_scale * clip factor */
+    int32_t skip;            /* 1: an element was Inf / NaN and the caller asked for skipping -- the optimizer changes nothing */
+    int32_t micro;           /* micro-batches accumulated since the last tramba_grad_norm */
+    int64_t skipped_steps;   /* steps skipped since the record was zeroed */
+} tramba_step_ctl;
+/* acc[i] = grads[i] when ctl->micro == 0, else acc[i] += grads[i] (fp32, element-wise: the accumulated value is the
+ * micro-batch gradients added in micro-batch order); then ctl->micro += 1 (a one-lane launch behind the others).
+ * grads[i] == NULL: the micro-batch produced no gradient for tensor i -- zeros (stored on the first micro-batch, nothing
+ * to add later).  HOST arrays, tensors by value (128 per launch), any alignment, 16-byte aligned pairs take the vector path. */
+int tramba_grad_accumulate(float *const *acc, const float *const *grads, const int64_t *numel, int count,
+                           tramba_step_ctl *ctl, void *stream);
+/* The global L2 norm over `count` fp32 tensors and the decisions that hang on it, written into the record:
+ *   norm  = sqrt(sum of squares) * mean_scale         squares formed and added in fp64, per chunk of 8192 elements, the
+ *                                                     partials added by one block in a fixed order (no atomics)
+ *   skip  = skip_nonfinite && any element Inf / NaN   (decided per element, not from the norm)
+ *   scale = mean_scale * min(1, max_norm / (norm + 1e-6))     (torch.nn.utils.clip_grad_norm_;  max_norm <= 0: mean_scale)
+ *   skipped_steps += skip;  micro = 0.
+ * mean_scale > 0 is 1 / micro-batches.  workspace: tramba_grad_norm_workspace() bytes, 8-byte aligned. */
+size_t tramba_grad_norm_workspace(const int64_t *numel, int count);
+int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
+                     int skip_nonfinite, tramba_step_ctl *ctl, void *workspace, size_t workspace_bytes, void *stream);
+/* tramba_adam_step with two device scalars (either may be NULL; both NULL is tramba_adam_step bit for bit):
+ *   gscale: g = gscale[0] * g in fp32 before the weight decay and everything else;
+ *   skip:   skip[0] != 0 -- the call changes nothing: parameters, both moments and the step counters keep their bits.
+ * Both are read by the kernels when they run (a replayed graph follows the record, not the values at capture). */
+int tramba_adam_step_ctl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                         float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, const float *gscale, const int *skip, void *stream);
 
 #ifdef __cplusplus
 }

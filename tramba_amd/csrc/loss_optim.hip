@@ -9,9 +9,15 @@
 //   * Adam (train.py:266-280, torch.optim.Adam's arithmetic): one read and one write of p / exp_avg / exp_avg_sq and one
 //     read of the gradient per step, the tensors of a launch described BY VALUE in the kernel arguments (nothing is
 //     copied to the device, hipGraph-capture safe: the gradients of a captured step live at other addresses than the
-//     warm-up's).
+//     warm-up's);
+//   * what sits between backward and Adam when a step is built from several micro-batches (no reference counterpart: the
+//     reference steps once per batch): gradient accumulation, the global L2 norm with its clip factor and the "a
+//     gradient is not finite: skip this step" decision.  The decisions live in a small record ON THE DEVICE
+//     (tramba_step_ctl) that the kernels read and write, so a replayed hipGraph needs no host value that changes from
+//     step to step.
 //
-// Both are HBM-streaming kernels: the loss moves 8 B per label pixel and output, Adam 28 B per parameter.
+// All are HBM-streaming kernels: the loss moves 8 B per label pixel and output, Adam 28 B per parameter, an accumulate
+// pass 12 B (8 B on the first micro-batch), the norm 4 B.
 #include "common.h"
 
 #include <algorithm>
@@ -246,15 +252,19 @@ struct AdamArgs {
     int first[kAdamTensors + 1];   // first workgroup of each tensor (ascending); first[count] = the grid
     int count;
     double lr, beta1, beta2, eps, weight_decay;
+    const float *gscale;           // device scalar the gradient is multiplied by first (null: the gradient as it is)
+    const int *skip;               // device flag: non-zero = this launch changes nothing (null: never)
 };
 struct BumpArgs {
     float *step[kBumpTensors];
     int count;
+    const int *skip;
 };
 static_assert(sizeof(AdamArgs) <= 4096 && sizeof(BumpArgs) <= 4096, "kernel arguments are limited to 4 KB");
 
 __global__ __launch_bounds__(kBumpTensors) void adam_bump_kernel(BumpArgs a)
 {
+    if (a.skip && *a.skip) return;
     if ((int)threadIdx.x < a.count) *a.step[threadIdx.x] += 1.f;
 }
 
@@ -278,12 +288,16 @@ __device__ __forceinline__ void adam_store(float *p, adam_f4 v)
 }
 
 struct AdamCoef {
-    float step_size, bc2_sqrt, b1w, beta2, b2w, eps, wd;
+    float step_size, bc2_sqrt, b1w, beta2, b2w, eps, wd, gs;
+    bool scaled;
 };
 // torch.optim.Adam (amsgrad off, maximize off):  g += wd p;  m = lerp(m, g, 1 - b1);  v = b2 v + (1 - b2) g g;
 // p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+// A scaled step (tramba_adam_step_ctl) multiplies the gradient first, rounded to fp32 on its own (never contracted into what
+// follows): the step equals tramba_adam_step on gradients that were scaled beforehand.
 __device__ __forceinline__ void adam_math(float &p, float g, float &m, float &v, const AdamCoef &c)
 {
+    if (c.scaled) g = __fmul_rn(c.gs, g);
     g = fmaf(c.wd, p, g);
     m = fmaf(c.b1w, g - m, m);
     v = fmaf(c.beta2, v, c.b2w * g * g);
@@ -343,6 +357,7 @@ __device__ __forceinline__ void adam_chunk(const AdamTensor &t, long off, const 
 __global__ __launch_bounds__(kAdamThreads) void adam_kernel(AdamArgs a)
 {
     __shared__ float corr[2];
+    if (a.skip && *a.skip) return;                // (uniform over the grid: parameters and moments keep their bits)
     int lo = 0, hi = a.count;                     // the tensor this workgroup works on: first[lo] <= blockIdx.x < first[lo + 1]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -364,9 +379,219 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(AdamArgs a)
     c.b2w = (float)(1.0 - a.beta2);
     c.eps = (float)a.eps;
     c.wd = (float)a.weight_decay;
+    c.scaled = a.gscale != nullptr;
+    c.gs = c.scaled ? *a.gscale : 1.f;
     const bool al = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
                       reinterpret_cast<uintptr_t>(t.v)) & 15) == 0;
     if (al) adam_chunk<true>(t, off, c); else adam_chunk<false>(t, off, c);
+}
+
+// ------------------------------------------------------------------------------------------------- step control
+// Tensors of a launch are dealt like Adam's: by value in the kernel arguments, a workgroup per chunk of kAdamChunk elements.
+constexpr int kAccTensors = 128, kNormTensors = 160, kNormThreads = 256;
+struct AccTensor {
+    float *acc;
+    const float *g;                // null: this micro-batch produced no gradient for the tensor (zeros)
+    long n;
+};
+struct AccArgs {
+    AccTensor t[kAccTensors];
+    int first[kAccTensors + 1];
+    int count;
+    const tramba_step_ctl *ctl;
+};
+struct NormTensor {
+    const float *g;
+    long n;
+};
+struct NormArgs {
+    NormTensor t[kNormTensors];
+    int first[kNormTensors + 1];
+    int count, chunk_base;         // this launch's first slot in the tables of partials
+    double *part;
+    unsigned *bad;
+};
+static_assert(sizeof(AccArgs) <= 4096 && sizeof(NormArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+template <typename A>
+__device__ __forceinline__ int tensor_of_block(const A &a)
+{
+    int lo = 0, hi = a.count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// acc = g on the first micro-batch of a step (ctl->micro == 0), acc += g afterwards
+template <bool ALIGNED>
+__device__ __forceinline__ void acc_chunk(float *acc, const float *g, int here, bool first)
+{
+    const int nvec = here >> 2;
+    constexpr int U = 4;
+    for (int j0 = threadIdx.x; j0 < nvec; j0 += U * kAdamThreads) {
+        adam_f4 aa[U], gg[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * kAdamThreads;
+            if (j < nvec) {
+                gg[u] = g ? adam_load<ALIGNED>(g + 4 * j) : adam_f4{0.f, 0.f, 0.f, 0.f};
+                if (!first) aa[u] = adam_load<ALIGNED>(acc + 4 * j);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * kAdamThreads;
+            if (j < nvec) adam_store<ALIGNED>(acc + 4 * j, first ? gg[u] : aa[u] + gg[u]);
+        }
+    }
+    const int j = (nvec << 2) + threadIdx.x;
+    if (j < here) {
+        const float ge = g ? g[j] : 0.f;
+        acc[j] = first ? ge : acc[j] + ge;
+    }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void grad_accumulate_kernel(AccArgs a)
+{
+    const int ti = tensor_of_block(a);
+    const AccTensor t = a.t[ti];
+    const bool first = a.ctl->micro == 0;
+    if (!t.g && !first) return;                   // nothing to add
+    const long off = (long)((int)blockIdx.x - a.first[ti]) * kAdamChunk;
+    const long left = t.n - off;
+    const int here = left < kAdamChunk ? (int)left : kAdamChunk;
+    const float *g = t.g ? t.g + off : nullptr;
+    const bool al = ((reinterpret_cast<uintptr_t>(t.acc) | reinterpret_cast<uintptr_t>(t.g)) & 15) == 0;
+    if (al) acc_chunk<true>(t.acc + off, g, here, first); else acc_chunk<false>(t.acc + off, g, here, first);
+}
+
+__global__ void step_ctl_advance_kernel(tramba_step_ctl *ctl)
+{
+    if (threadIdx.x == 0) ctl->micro += 1;
+}
+
+// part[chunk] = sum of squares of the chunk in fp64 (products of fp32 values are exact there), bad[chunk] = any element
+// with an all-ones exponent (Inf / NaN): decided per element, a sum can overflow or cancel its way to either verdict
+__global__ __launch_bounds__(kNormThreads) void grad_norm_parts_kernel(NormArgs a)
+{
+    __shared__ double red[kNormThreads / kWave];
+    __shared__ unsigned redbad[kNormThreads / kWave];
+    const int ti = tensor_of_block(a);
+    const NormTensor t = a.t[ti];
+    const long off = (long)((int)blockIdx.x - a.first[ti]) * kAdamChunk;
+    const long left = t.n - off;
+    const int here = left < kAdamChunk ? (int)left : kAdamChunk;
+    const float *g = t.g + off;
+    double s = 0.0;
+    unsigned bad = 0;
+    auto take = [&](float x) {
+        bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;
+        s = fma((double)x, (double)x, s);
+    };
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        const int nvec = here >> 2;
+        constexpr int U = 4;
+        for (int j0 = threadIdx.x; j0 < nvec; j0 += U * kNormThreads) {
+            adam_f4 gg[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int j = j0 + u * kNormThreads;
+                gg[u] = j < nvec ? adam_load<true>(g + 4 * j) : adam_f4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) take(gg[u][e]);
+        }
+        const int j = (nvec << 2) + threadIdx.x;
+        if (j < here) take(g[j]);
+    } else {
+        for (int j = threadIdx.x; j < here; j += kNormThreads) take(g[j]);
+    }
+    s = wave_sum_f64(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad |= __shfl_xor(bad, o, 64);
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wv] = s;
+        redbad[wv] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        unsigned b = 0;
+        for (int q = 0; q < kNormThreads / kWave; ++q) {
+            tot += red[q];
+            b |= redbad[q];
+        }
+        a.part[a.chunk_base + blockIdx.x] = tot;
+        a.bad[a.chunk_base + blockIdx.x] = b;
+    }
+}
+
+// One block adds the partials in a fixed order (a thread strides over the chunks, a shuffle tree per wave, the waves in
+// order) and writes the record.
+constexpr int kNormFinishThreads = 1024;
+__global__ __launch_bounds__(kNormFinishThreads) void grad_norm_finish_kernel(const double *__restrict__ part,
+                                                                             const unsigned *__restrict__ bad, int nchunk,
+                                                                             double mean_scale, double max_norm,
+                                                                             int skip_nonfinite, tramba_step_ctl *ctl)
+{
+    __shared__ double red[kNormFinishThreads / kWave];
+    __shared__ unsigned redbad[kNormFinishThreads / kWave];
+    double s = 0.0;
+    unsigned b = 0;
+    for (int i = threadIdx.x; i < nchunk; i += kNormFinishThreads) {
+        s += part[i];
+        b |= bad[i];
+    }
+    s = wave_sum_f64(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b |= __shfl_xor(b, o, 64);
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wv] = s;
+        redbad[wv] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        unsigned any = 0;
+        for (int q = 0; q < kNormFinishThreads / kWave; ++q) {
+            tot += red[q];
+            any |= redbad[q];
+        }
+        const float norm = (float)(sqrt(tot) * mean_scale);
+        double scale = mean_scale;
+        if (max_norm > 0.0) {                       // torch.nn.utils.clip_grad_norm_: min(1, max_norm / (norm + 1e-6))
+            const double coef = max_norm / ((double)norm + 1e-6);
+            scale = mean_scale * (coef < 1.0 ? coef : 1.0);   // (a NaN norm gives a NaN scale, as torch's clamp does)
+            if (coef != coef) scale = coef;
+        }
+        const int skip = (any && skip_nonfinite) ? 1 : 0;
+        ctl->norm = norm;
+        ctl->scale = (float)scale;
+        ctl->skip = skip;
+        ctl->micro = 0;
+        ctl->skipped_steps += skip;
+    }
+}
+
+// the tensors dealt to ceil(count / per_launch) launches of equal weight: largest first, in snake order
+static std::vector<std::vector<int>> snake_bins(const int64_t *numel, int count, int per_launch)
+{
+    const int nlaunch = (count + per_launch - 1) / per_launch;
+    std::vector<int> order(count);
+    for (int i = 0; i < count; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return numel[x] > numel[y]; });
+    std::vector<std::vector<int>> bins(nlaunch);
+    for (int i = 0; i < count; ++i) {
+        const int round = i / nlaunch, pos = i % nlaunch;
+        bins[(round & 1) ? nlaunch - 1 - pos : pos].push_back(order[i]);
+    }
+    return bins;
 }
 
 }  // namespace tramba
@@ -449,9 +674,9 @@ extern "C" int tramba_sod_loss_grad(const float *logits, const float *label, con
     return TRAMBA_OK;
 }
 
-extern "C" int tramba_adam_step(float *const *params, const float *const *grads, float *const *exp_avg,
-                                float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr,
-                                double beta1, double beta2, double eps, double weight_decay, void *stream)
+static int adam_step_impl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                          float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, const float *gscale, const int *skip, void *stream)
 {
     TRAMBA_CHECK(params && grads && exp_avg && exp_avg_sq && steps && numel && count > 0, "adam_step: empty input");
     TRAMBA_CHECK(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0,
@@ -464,21 +689,14 @@ extern "C" int tramba_adam_step(float *const *params, const float *const *grads,
         BumpArgs b;
         b.count = count - base < kBumpTensors ? count - base : kBumpTensors;
         for (int i = 0; i < kBumpTensors; ++i) b.step[i] = i < b.count ? steps[base + i] : nullptr;
+        b.skip = skip;
         hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(kBumpTensors), 0, s, b);
         TRAMBA_LAUNCH_CHECK();
     }
     // Launches of equal weight: the tensors are dealt to ceil(count / 72) launches largest first, in snake order (a launch of
     // 72 bias vectors alone would put 72 workgroups on 256 CUs; the order of the updates does not matter, they are independent).
-    const int nlaunch = (count + kAdamTensors - 1) / kAdamTensors;
-    std::vector<int> order(count);
-    for (int i = 0; i < count; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return numel[x] > numel[y]; });
-    std::vector<std::vector<int>> bins(nlaunch);
-    for (int i = 0; i < count; ++i) {
-        const int round = i / nlaunch, pos = i % nlaunch;
-        bins[(round & 1) ? nlaunch - 1 - pos : pos].push_back(order[i]);
-    }
-    for (int l = 0; l < nlaunch; ++l) {
+    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAdamTensors);
+    for (size_t l = 0; l < bins.size(); ++l) {
         AdamArgs a;
         long blocks = 0;
         const int c = (int)bins[l].size();           // <= kAdamTensors by construction
@@ -494,8 +712,121 @@ extern "C" int tramba_adam_step(float *const *params, const float *const *grads,
         for (int i = c; i <= kAdamTensors; ++i) a.first[i] = (int)blocks;
         for (int i = c; i < kAdamTensors; ++i) a.t[i] = AdamTensor{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
         a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+        a.gscale = gscale;
+        a.skip = skip;
         hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
         TRAMBA_LAUNCH_CHECK();
     }
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_adam_step(float *const *params, const float *const *grads, float *const *exp_avg,
+                                float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr,
+                                double beta1, double beta2, double eps, double weight_decay, void *stream)
+{
+    return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, nullptr,
+                          nullptr, stream);
+}
+
+extern "C" int tramba_adam_step_ctl(float *const *params, const float *const *grads, float *const *exp_avg,
+                                    float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr,
+                                    double beta1, double beta2, double eps, double weight_decay, const float *gscale,
+                                    const int *skip, void *stream)
+{
+    return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, gscale,
+                          skip, stream);
+}
+
+// chunks (= workgroups) over all tensors of a call, -1 beyond what a grid holds
+static long norm_chunks(const int64_t *numel, int count)
+{
+    long n = 0;
+    for (int i = 0; i < count; ++i) {
+        if (numel[i] <= 0) return -1;
+        n += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+        if (n >= 2147483647L) return -1;
+    }
+    return n;
+}
+
+extern "C" int tramba_grad_accumulate(float *const *acc, const float *const *grads, const int64_t *numel, int count,
+                                      tramba_step_ctl *ctl, void *stream)
+{
+    TRAMBA_CHECK(acc && grads && numel && ctl, "grad_accumulate: null argument");
+    TRAMBA_CHECK(count > 0, "grad_accumulate: count must be positive (got %d)", count);
+    for (int i = 0; i < count; ++i)
+        TRAMBA_CHECK(acc[i] && numel[i] > 0, "grad_accumulate: tensor %d: null accumulator or no elements", i);
+    TRAMBA_CHECK(norm_chunks(numel, count) > 0, "grad_accumulate: too many workgroups");   // (before the first launch)
+    hipStream_t s = (hipStream_t)stream;
+    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAccTensors);
+    for (size_t l = 0; l < bins.size(); ++l) {
+        AccArgs a;
+        long blocks = 0;
+        const int c = (int)bins[l].size();
+        for (int i = 0; i < c; ++i) {
+            const int j = bins[l][i];
+            a.t[i] = AccTensor{acc[j], grads[j], (long)numel[j]};
+            a.first[i] = (int)blocks;
+            blocks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
+        }
+        a.count = c;
+        for (int i = c; i <= kAccTensors; ++i) a.first[i] = (int)blocks;
+        for (int i = c; i < kAccTensors; ++i) a.t[i] = AccTensor{nullptr, nullptr, 0};
+        a.ctl = ctl;
+        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
+        TRAMBA_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(step_ctl_advance_kernel, dim3(1), dim3(kWave), 0, s, ctl);   // after every read of the counter
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" size_t tramba_grad_norm_workspace(const int64_t *numel, int count)
+{
+    if (!numel || count <= 0) return 0;
+    const long n = norm_chunks(numel, count);
+    return n < 0 ? 0 : (size_t)n * (sizeof(double) + sizeof(unsigned));
+}
+
+extern "C" int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
+                                int skip_nonfinite, tramba_step_ctl *ctl, void *workspace, size_t workspace_bytes, void *stream)
+{
+    TRAMBA_CHECK(grads && numel && ctl && workspace, "grad_norm: null argument");
+    TRAMBA_CHECK(count > 0, "grad_norm: count must be positive (got %d)", count);
+    TRAMBA_CHECK(mean_scale > 0.0, "grad_norm: mean_scale must be positive");
+    for (int i = 0; i < count; ++i)
+        TRAMBA_CHECK(grads[i] && numel[i] > 0, "grad_norm: tensor %d: null pointer or no elements", i);
+    const long nchunk = norm_chunks(numel, count);
+    TRAMBA_CHECK(nchunk > 0, "grad_norm: too many workgroups");
+    TRAMBA_CHECK(workspace_bytes >= tramba_grad_norm_workspace(numel, count) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+                 "grad_norm: an 8-byte aligned workspace of %zu bytes needed", tramba_grad_norm_workspace(numel, count));
+    hipStream_t s = (hipStream_t)stream;
+    double *part = (double *)workspace;
+    unsigned *bad = (unsigned *)(part + nchunk);
+    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kNormTensors);
+    long base = 0;
+    for (size_t l = 0; l < bins.size(); ++l) {
+        NormArgs a;
+        long blocks = 0;
+        const int c = (int)bins[l].size();
+        for (int i = 0; i < c; ++i) {
+            const int j = bins[l][i];
+            a.t[i] = NormTensor{grads[j], (long)numel[j]};
+            a.first[i] = (int)blocks;
+            blocks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
+        }
+        a.count = c;
+        for (int i = c; i <= kNormTensors; ++i) a.first[i] = (int)blocks;
+        for (int i = c; i < kNormTensors; ++i) a.t[i] = NormTensor{nullptr, 0};
+        a.chunk_base = (int)base;
+        a.part = part;
+        a.bad = bad;
+        hipLaunchKernelGGL(grad_norm_parts_kernel, dim3((unsigned)blocks), dim3(kNormThreads), 0, s, a);
+        TRAMBA_LAUNCH_CHECK();
+        base += blocks;
+    }
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kNormFinishThreads), 0, s, part, bad, (int)nchunk, mean_scale,
+                       max_norm, skip_nonfinite, ctl);
+    TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -73,15 +73,26 @@ class GraphedTrainStep:
     `adjust_learning_rate` changes them.  A capture needs eager warm-up steps (optimizer state and lazy caches must exist
     before the stream is captured); parameters and optimizer state are saved before and restored after them, so every call
     -- capturing or not -- advances the optimisation by exactly one step on the batch it was given.  Stochastic depth draws
-    from torch's device generator, which hipGraph capture advances per replay.  Returns the loss (a static buffer)."""
+    from torch's device generator, which hipGraph capture advances per replay.  Returns the loss (a static buffer).
 
-    def __init__(self, model, opt, reducer=None, warmup=2):
+    With `control` (tramba_amd.train.StepControl) a call takes what `train_step(..., control=control)` takes -- tensors that
+    split into `control.accumulate` micro-batches, or sequences of micro-batches -- and the whole controlled step replays
+    without a host decision, as TWO graphs per micro-batch shape that share one memory pool: "micro-batch + accumulate",
+    replayed for all micro-batches but the last (each copied into the static input first), and "micro-batch + accumulate
+    + (all-reduce +) norm + Adam + refreshes" for the last one.  Whether a micro-batch stores or adds is decided by the
+    control record's counter on the device; the clip norm and 1 / micro-batches are host scalars baked into the second
+    graph like the learning rates, so they are part of its key (a short last group of an epoch gets an update graph of
+    its own, the full one stays).  The warm-up steps are one-micro-batch controlled steps; the control record, the
+    accumulators and `skipped_steps` are put back with the parameters afterwards.  Returns the mean micro-batch loss."""
+
+    def __init__(self, model, opt, reducer=None, warmup=2, control=None):
         if reducer is not None and getattr(reducer, "world", 1) > 1 and getattr(reducer, "find_unused", False):
             raise RuntimeError("GraphedTrainStep: a reducer with find_unused=True reads flags on the host every step and "
                                "cannot be captured")
         if not all(g.get("capturable", False) for g in opt.param_groups):
             raise RuntimeError("GraphedTrainStep needs an optimizer with capturable=True")
         self.model, self.opt, self.reducer, self.warmup = model, opt, reducer, warmup
+        self.control = control
         self._graphs = {}
         self._lr_key = None
         self._trainable_key = None
@@ -96,7 +107,10 @@ class GraphedTrainStep:
             st = self.opt.state.get(p)
             saved.append((p, p.detach().clone(),
                           None if not st else {k: v.clone() for k, v in st.items() if torch.is_tensor(v)}))
-        return saved, [(b, b.detach().clone()) for b in self.model.buffers()]     # buffers: BatchNorm running statistics
+        buffers = [(b, b.detach().clone()) for b in self.model.buffers()]         # buffers: BatchNorm running statistics
+        if self.control is not None:
+            buffers += [(t, t.clone()) for t in self.control._state_tensors()]
+        return saved, buffers
 
     def _restore(self, snapshot):
         from .modules import refresh_dw_packs, refresh_lowp_shadows
@@ -161,6 +175,87 @@ class GraphedTrainStep:
         torch.cuda.set_rng_state(rng, dev)
         return graph, sx, sy, loss, keep_alive
 
+    # ------------------------------------------------------------------ a controlled step: two graphs per shape
+    def _capture_controlled(self, sx, sy, count, pool, update):
+        """one micro-batch on the static inputs (+ the update of a `count`-micro-batch step) -> (graph, loss, keep_alive)"""
+        from . import train
+        from .modules import model_mask_pool
+        control, all_ranks = self.control, self.reducer is not None and getattr(self.reducer, "world", 1) > 1
+        params = control._bind(self.opt, self.reducer)
+        masks = model_mask_pool(self.model)
+        masks.forget_draw()
+        graph = torch.cuda.CUDAGraph()
+        mode = "thread_local" if all_ranks else "global"
+        control._used = set()
+        with torch.cuda.graph(graph, pool=pool, capture_error_mode=mode):
+            # (first=True: store-or-add is the record's decision at replay, the host treats every micro-batch alike)
+            loss = train._controlled_micro_batch(self.model, self.opt, sx, sy, control, params, True, all_ranks)
+            if update:
+                train._controlled_finish(self.model, self.opt, control, params, count, self.reducer, all_ranks, True)
+        control._used = set()
+        keep_alive = (masks.probs, masks.buf, masks.buf32)
+        masks.forget_draw()
+        return graph, loss, keep_alive
+
+    def _warm_controlled(self, x, y):
+        """static inputs for this micro-batch shape; optimizer state, accumulators and all lazy caches exist afterwards"""
+        from .train import train_step
+        sx, sy = x.clone(), y.clone()
+        self.control._bind(self.opt, self.reducer)
+        if not self.control._device_path:
+            raise RuntimeError("GraphedTrainStep(control=...): only the library's optimizer on fp32 device parameters "
+                               "(train.get_opt(..., capturable=True)) can be captured: torch's functions decide the skip "
+                               "of a non-finite step on the host")
+        saved = self._snapshot()
+        dev = x.device
+        rng = torch.cuda.get_rng_state(dev)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(self.warmup):
+                train_step(self.model, self.opt, [sx], [sy], reducer=self.reducer, control=self.control)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        return sx, sy, saved, rng
+
+    def _call_controlled(self, images, label):
+        from .train import _micro_batches
+        control = self.control
+        xs, ys = _micro_batches(images, label, control)
+        count, x0, y0 = len(xs), xs[0], ys[0]
+        shape_key = (tuple(x0.shape), x0.dtype, tuple(y0.shape), y0.dtype)
+        entry = self._graphs.get(shape_key)
+        if entry is None:
+            entry = self._graphs[shape_key] = {"static": None, "mid": None, "update": {}, "pool": torch.cuda.graph_pool_handle()}
+        need_mid = count > 1 and entry["mid"] is None
+        update_key = (count, control.clip_norm, control.skip_nonfinite)
+        need_update = update_key not in entry["update"]
+        if need_mid or need_update:
+            if entry["static"] is None:
+                sx, sy, saved, rng = self._warm_controlled(x0, y0)
+                entry["static"] = (sx, sy)
+            else:                                   # (a further update graph for a known shape: everything is warm)
+                sx, sy = entry["static"]
+                saved = rng = None                  # (a capture executes nothing: there is nothing to put back)
+            if need_mid:
+                entry["mid"] = self._capture_controlled(sx, sy, count, entry["pool"], False)
+            if need_update:
+                entry["update"][update_key] = self._capture_controlled(sx, sy, count, entry["pool"], True)
+            if saved is not None:
+                self._restore(saved)
+                torch.cuda.set_rng_state(rng, x0.device)
+        sx, sy = entry["static"]
+        control._begin_step()                       # (outside the graphs: one 4-byte fill per optimizer step)
+        total = None
+        for k, (x, y) in enumerate(zip(xs, ys)):
+            graph, loss = (entry["mid"] if k < count - 1 else entry["update"][update_key])[:2]
+            sx.copy_(x, non_blocking=True)
+            sy.copy_(y, non_blocking=True)
+            graph.replay()
+            total = loss.clone() if total is None else total + loss
+        self._mark_modified()
+        return total / count
+
     def __call__(self, images, label):
         if not self.model.training:
             raise RuntimeError("GraphedTrainStep: the model is in eval mode (an evaluation callback must switch it back "
@@ -171,6 +266,8 @@ class GraphedTrainStep:
         if lrs != self._lr_key or trainable != self._trainable_key:
             self._graphs.clear()
             self._lr_key, self._trainable_key = lrs, trainable
+        if self.control is not None:
+            return self._call_controlled(images, label)
         key = (tuple(images.shape), images.dtype, tuple(label.shape), label.dtype)
         entry = self._graphs.get(key)
         if entry is None:

@@ -121,6 +121,10 @@ SIGNATURES = {
     "tramba_sod_loss_grad_workspace": (ctypes.c_size_t, [c_int] * 5),
     "tramba_sod_loss_grad": (c_int, [c_vp] * 6 + [ctypes.c_size_t] + [c_int] * 5 + [c_vp]),
     "tramba_adam_step": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp]),
+    "tramba_grad_accumulate": (c_int, [c_vp] * 3 + [c_int, c_vp, c_vp]),
+    "tramba_grad_norm_workspace": (ctypes.c_size_t, [c_vp, c_int]),
+    "tramba_grad_norm": (c_int, [c_vp] * 2 + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "tramba_adam_step_ctl": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp] * 3),
 }
 
 _lib = None
@@ -1160,11 +1164,52 @@ def pointer_array(tensors):
     return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
-def adam_step_raw(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, lr, beta1, beta2, eps, weight_decay=0.0):
+def adam_step_raw(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, lr, beta1, beta2, eps, weight_decay=0.0, gscale=None,
+                  skip=None):
     """`adam_step` on prepared pointer arrays (tramba_amd.train.Adam keeps those of the parameters and of the state between
-    steps and rebuilds only the gradients'); the caller vouches for fp32, contiguous, same-size device tensors."""
-    _check(lib().tramba_adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1), float(beta2),
-                                  float(eps), float(weight_decay), _stream()), "adam_step")
+    steps and rebuilds only the gradients'); the caller vouches for fp32, contiguous, same-size device tensors.
+    `gscale` (fp32) / `skip` (int32): device scalars of a step-control record -- the gradient is multiplied by the first, a
+    non-zero second makes the call change nothing (tramba_adam_step_ctl)."""
+    if gscale is None and skip is None:
+        _check(lib().tramba_adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
+                                      float(beta2), float(eps), float(weight_decay), _stream()), "adam_step")
+        return
+    if gscale is not None and (gscale.dtype != torch.float32 or not gscale.is_cuda):
+        raise TrambaHipError("adam_step: gscale is an fp32 scalar on the device")
+    if skip is not None and (skip.dtype != torch.int32 or not skip.is_cuda):
+        raise TrambaHipError("adam_step: skip is an int32 scalar on the device")
+    _check(lib().tramba_adam_step_ctl(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
+                                      float(beta2), float(eps), float(weight_decay), _ptr(gscale), _ptr(skip), _stream()),
+           "adam_step_ctl")
+
+
+STEP_CTL_BYTES = 24      # struct tramba_step_ctl: float norm, float scale, int32 skip, int32 micro, int64 skipped_steps
+
+
+def step_ctl_record(device):
+    """a zeroed tramba_step_ctl on `device` and typed 0-dim views of its fields:
+    (record, {"norm", "scale": fp32, "skip", "micro": int32, "skipped_steps": int64})"""
+    rec = torch.zeros(STEP_CTL_BYTES // 8, dtype=torch.int64, device=device)
+    f, i = rec.view(torch.float32), rec.view(torch.int32)
+    return rec, {"norm": f[0], "scale": f[1], "skip": i[2], "micro": i[3], "skipped_steps": rec[2]}
+
+
+def grad_accumulate_raw(accs, grads, numel, n, ctl):
+    """acc[i] = g[i] on the first micro-batch of a step (the record's counter is 0), acc[i] += g[i] afterwards; the counter
+    advances.  Pointer arrays as `adam_step_raw` takes them; a null gradient pointer stands for zeros."""
+    _check(lib().tramba_grad_accumulate(accs, grads, numel, n, ctl.data_ptr(), _stream()), "grad_accumulate")
+
+
+def grad_norm_workspace(numel, n):
+    return lib().tramba_grad_norm_workspace(numel, n)
+
+
+def grad_norm_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, workspace):
+    """global L2 norm of the tensors -> the record's norm / scale / skip (tramba_grad_norm); `workspace`: a device tensor of
+    at least grad_norm_workspace() bytes"""
+    _check(lib().tramba_grad_norm(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
+                                  ctl.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+           "grad_norm")
 
 
 def im2col3x3_cl(x, stride, pad, ckp):

@@ -218,6 +218,37 @@ class GradBucketReducer:
         self._have_local = {}
         self._armed = False
 
+    # ------------------------------------------------------------------ a step of several micro-batches (train.StepControl)
+    def begin_accumulation(self):
+        """Call before the first backward of a controlled step.  The hooks stay quiet during its micro-batches: the flat
+        buckets are the step's ACCUMULATORS (their per-parameter views are what tramba_grad_accumulate adds into), and
+        `reduce_accumulated` all-reduces them once per optimizer step."""
+        if self.find_unused and self.world > 1:
+            raise RuntimeError("GradBucketReducer: find_unused=True cannot be combined with a StepControl (which ranks used "
+                               "a parameter would have to be tracked per micro-batch): parameters a rank did not use "
+                               "contribute zeros")
+        if self.bucket_dtype is not None:
+            raise RuntimeError("GradBucketReducer: a StepControl accumulates in the fp32 buckets; bucket_dtype must be None")
+        if self._signature() != self._sig:
+            self._build()
+        self._handles = []
+        self._armed = False
+
+    def reduce_accumulated(self):
+        """One all-reduce round over the accumulated buckets (the 1 / world average folded in as in a plain step: ncclAvg,
+        or a pre-scale for gloo).  Runs before the norm, so every rank sees the same norm, clip factor and skip decision."""
+        if self.world <= 1:
+            return
+        handles = []
+        for flat in self.flat:
+            if not self._native_avg:
+                flat.mul_(1.0 / self.world)
+            op = dist.ReduceOp.AVG if self._native_avg else dist.ReduceOp.SUM
+            handles.append(dist.all_reduce(flat, op=op, group=self.group, async_op=True))
+        for h in handles:
+            h.wait()
+
     def bytes_per_step(self):
-        """Bytes this rank hands to the collective per step (gradients; the per-parameter flags are ~3 KB)."""
+        """Bytes this rank hands to the collective per step (gradients; the per-parameter flags are ~3 KB).  Under a
+        StepControl that is per OPTIMIZER step, whatever the number of micro-batches."""
         return sum(sum(p.numel() for p in b) * f.element_size() for f, b in zip(self.flat, self.buckets))

@@ -151,7 +151,10 @@ class Adam(torch.optim.Adam):
         return plan
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, gscale=None, skip=None):
+        """`gscale` (fp32) / `skip` (int32): 0-dim device tensors read by the kernel when it runs -- every gradient is
+        multiplied by the first before anything else, a non-zero second leaves parameters, moments and step counters as
+        they are (StepControl hands both over; a captured step follows their values at replay)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -169,7 +172,7 @@ class Adam(torch.optim.Adam):
             plan = self._plan(gi, ps)
             b1, b2 = group["betas"]
             hip.adam_step_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps), group["lr"], b1, b2,
-                              group["eps"], group["weight_decay"])
+                              group["eps"], group["weight_decay"], gscale=gscale, skip=skip)
             # the kernel writes through raw pointers: bump the version counters as an in-place torch op would (every
             # derived-weight cache of the inference path is keyed on them)
             torch.autograd.graph.increment_version(ps)
@@ -210,9 +213,267 @@ def _has_standing_grads(opt):
     return False
 
 
-def train_step(model, opt, images, label, reducer=None):
+class StepControl:
+    """What an optimisation step built from several micro-batches needs to keep between them, and between replays of a
+    captured step:
+
+      accumulate      micro-batches per optimizer step: their gradients are added in fp32, in micro-batch order, and the
+                      optimizer steps once on the mean (N micro-batches accumulated == N data-parallel ranks averaged);
+      clip_norm       the mean gradient is scaled by min(1, clip_norm / (norm + 1e-6)), torch's clip_grad_norm_ rule;
+      skip_nonfinite  a step whose accumulated gradient holds an Inf / NaN element changes nothing (parameters, moments,
+                      Adam's step counters) and is counted in `skipped_steps`.
+
+    On the device (fp32 parameters, the library's `Adam`) all three are the library's kernels around a 24-byte record in
+    device memory (tramba_step_ctl): tramba_grad_accumulate after each backward, tramba_grad_norm once, and the optimizer
+    kernel reads the scale and the skip flag from the record -- no host decision, so the whole step replays as hipGraphs
+    (tramba_amd.graph.GraphedTrainStep(control=...)).  The gradients are NOT rewritten: after a step `p.grad` is a view of
+    the accumulator and holds the unscaled SUM over the micro-batches; the scale lives in the optimizer kernel.  Host
+    tensors / other dtypes (the rule `get_opt` picks the optimizer by) get the same semantics from torch's own functions
+    (there `p.grad` ends up as the clipped mean, as clip_grad_norm_ leaves it).
+
+    `grad_norm` (the norm of the mean gradient before clipping) and `skipped_steps` are 0-dim tensors on the parameters'
+    device, valid after the first step: log them once per epoch, reading them costs a sync.  Memory: one fp32 accumulator
+    per trainable parameter (with a data-parallel reducer its flat buckets are the accumulators)."""
+
+    def __init__(self, accumulate=1, clip_norm=None, skip_nonfinite=False):
+        if int(accumulate) != accumulate or accumulate < 1:
+            raise ValueError(f"StepControl: accumulate must be a positive integer (got {accumulate!r})")
+        if clip_norm is not None and not clip_norm > 0:
+            raise ValueError(f"StepControl: clip_norm must be positive or None (got {clip_norm!r})")
+        self.accumulate = int(accumulate)
+        self.clip_norm = None if clip_norm is None else float(clip_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self._key = None            # what the buffers below were laid out for
+        self._device_path = None
+        self._record = self._fields = self._flat = self._workspace = None
+        self._acc = {}              # parameter -> its accumulator (a 16-byte aligned view)
+        self._norm = self._skipped = None
+        self._plans = {}
+        self._used = set()          # parameters that had a gradient in a micro-batch of the step under way
+        self._dirty = set()         # parameters whose accumulator holds an earlier step's sums
+
+    # ------------------------------------------------------------------ read-outs
+    @property
+    def grad_norm(self):
+        if self._key is None:
+            raise RuntimeError("StepControl.grad_norm: no step has run yet")
+        return self._fields["norm"] if self._device_path else self._norm
+
+    @property
+    def skipped_steps(self):
+        if self._key is None:
+            raise RuntimeError("StepControl.skipped_steps: no step has run yet")
+        return self._fields["skipped_steps"] if self._device_path else self._skipped
+
+    # ------------------------------------------------------------------ buffers
+    def _bind(self, opt, reducer=None):
+        """lay the record, the accumulators and the norm workspace out for the trainable parameters of `opt` (again when
+        that set, or the reducer's buckets, change: freeze_encoder / unfreeze_encoder)"""
+        params = [p for g in opt.param_groups for p in g["params"] if p.requires_grad and p.numel() > 0]
+        if not params:
+            raise ValueError("StepControl: the optimizer has no trainable parameter")
+        if reducer is not None:
+            reducer.begin_accumulation()
+        key = (tuple(id(p) for p in params), id(reducer), None if reducer is None else tuple(f.data_ptr() for f in reducer.flat))
+        if key == self._key:
+            return self._params
+        dev = params[0].device
+        device_path = isinstance(opt, Adam) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
+        if reducer is not None:
+            self._flat = reducer.flat
+            self._acc = {p: v for bucket, views in zip(reducer.buckets, reducer._views) for p, v in zip(bucket, views)}
+            # (the norm is taken over the whole buckets: a bucket view no optimizer group owns would never be written)
+            if len(self._acc) != len(params) or any(p not in self._acc for p in params):
+                raise ValueError("StepControl: the reducer's trainable parameters and the optimizer's must be the same set")
+        else:
+            self._acc, offs, n = {}, [], 0
+            by_kind = {}
+            for p in params:
+                by_kind.setdefault((p.dtype, p.device), []).append(p)
+            self._flat = []
+            for (dtype, device), ps in by_kind.items():
+                al = max(1, 16 // torch.empty((), dtype=dtype).element_size())
+                offs, n = [], 0
+                for p in ps:
+                    offs.append(n)
+                    n += (p.numel() + al - 1) // al * al
+                flat = torch.zeros(n, dtype=dtype, device=device)
+                self._flat.append(flat)
+                for p, off in zip(ps, offs):
+                    self._acc[p] = flat[off:off + p.numel()].view_as(p)
+        skipped = 0 if self._key is None else int(self.skipped_steps)      # (a re-layout keeps the count)
+        if device_path:
+            import ctypes
+            self._record, self._fields = hip.step_ctl_record(dev)
+            self._fields["skipped_steps"].fill_(skipped)
+            numel = (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat])
+            nbytes = hip.grad_norm_workspace(numel, len(self._flat))
+            self._workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        else:
+            self._norm = torch.zeros((), dtype=params[0].dtype if params[0].dtype.is_floating_point else torch.float32, device=dev)
+            self._skipped = torch.full((), skipped, dtype=torch.int64, device=dev)
+        self._device_path, self._params, self._key, self._plans = device_path, params, key, {}
+        self._dirty = set(params) if reducer is not None else set()    # own buffers start as zeros, a reducer's buckets may not
+        return params
+
+    def _begin_step(self):
+        """a step starts with no micro-batch accumulated, whatever became of the last one (a step that raised between two
+        micro-batches leaves the record's counter standing, and the next store would be an add)"""
+        self._used = set()
+        if self._device_path:
+            self._fields["micro"].zero_()
+
+    def _state_tensors(self):
+        """every tensor of this object that a step rewrites (GraphedTrainStep saves and restores them around its warm-up)"""
+        ts = [self._record] if self._device_path else [self._norm, self._skipped]
+        return ts + list(self._flat)
+
+    # ------------------------------------------------------------------ the two halves of a step
+    def _accumulate(self, params, first, all_ranks):
+        """fold the gradients autograd has just left in .grad into the accumulators; -> the parameters that had one"""
+        have = [p for p in params if p.grad is not None]
+        if self._device_path:
+            import ctypes
+            for p in have:
+                g = p.grad
+                if g.dtype != torch.float32 or g.layout != torch.strided or not g.is_contiguous() or g.numel() != p.numel():
+                    raise hip.TrambaHipError("StepControl: dense contiguous fp32 gradients only")
+            # a parameter without a gradient takes part with a null pointer (= zeros) when it had one in an earlier
+            # micro-batch, or when other ranks may have one
+            take = params if all_ranks else [p for p in params if p.grad is not None or p in self._used]
+            if take:
+                ids = tuple(id(p) for p in take)
+                plan = self._plans.get(ids)
+                if plan is None:
+                    plan = self._plans[ids] = (hip.pointer_array([self._acc[p] for p in take]),
+                                               (ctypes.c_int64 * len(take))(*[p.numel() for p in take]))
+                grads = (ctypes.c_void_p * len(take))(*[None if p.grad is None else p.grad.data_ptr() for p in take])
+                # a parameter first used in a LATER micro-batch: its accumulator still holds an older step's values
+                late = [self._acc[p] for p in take if not first and p not in self._used and not all_ranks]
+                if late:
+                    torch._foreach_zero_(late)
+                hip.grad_accumulate_raw(plan[0], grads, plan[1], len(take), self._record)
+        else:
+            with torch.no_grad():
+                if first:
+                    none = [self._acc[p] for p in params if p.grad is None]
+                    if none:
+                        torch._foreach_zero_(none)
+                    if have:
+                        torch._foreach_copy_([self._acc[p] for p in have], [p.grad for p in have])
+                elif have:
+                    torch._foreach_add_([self._acc[p] for p in have], [p.grad for p in have])
+        self._used.update(have)
+        return have
+
+    def _finish(self, opt, params, count, reducer, all_ranks):
+        """the accumulated sums become the gradients; norm, clip factor and skip decision; one optimizer step"""
+        used = params if all_ranks else [p for p in params if p in self._used]
+        for p in params:
+            p.grad = self._acc[p] if (all_ranks or p in self._used) else None
+        self._used = set()
+        if reducer is not None:
+            reducer.reduce_accumulated()
+        if not used:
+            return
+        if self._device_path:
+            import ctypes
+            # The norm is taken over the FLAT buffers the accumulators are views of -- one aligned stream in one launch
+            # instead of 673 tensors in five (the padding between the views is zero).  Accumulators of parameters that
+            # had a gradient in an earlier step and none in this one hold that step's sums: zeroed first.
+            now = set(used)
+            stale = [self._acc[p] for p in self._dirty if p not in now]
+            if stale:
+                torch._foreach_zero_(stale)
+            self._dirty = now
+            plan = self._plans.get("norm")
+            if plan is None:
+                plan = self._plans["norm"] = (hip.pointer_array(self._flat),
+                                              (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat]))
+            hip.grad_norm_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
+                              self._record, self._workspace)
+            opt.step(gscale=self._fields["scale"], skip=self._fields["skip"])
+            return
+        with torch.no_grad():
+            grads = [p.grad for p in used]
+            finite = bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()) if self.skip_nonfinite else True
+            torch._foreach_div_(grads, float(count))
+            norm = torch.nn.utils.clip_grad_norm_(used, float("inf") if self.clip_norm is None else self.clip_norm)
+            self._norm.copy_(norm)
+        if finite:
+            opt.step()
+        else:
+            self._skipped += 1
+
+
+def _micro_batches(images, label, control):
+    """the micro-batches of one controlled step: `images` / `label` as one tensor each (split in order into
+    control.accumulate equal parts) or as sequences of equal-shaped tensors, one per micro-batch"""
+    if torch.is_tensor(images) != torch.is_tensor(label):
+        raise ValueError("train_step: images and label are either both tensors or both sequences of micro-batches")
+    if torch.is_tensor(images):
+        n = control.accumulate
+        if images.shape[0] != label.shape[0] or images.shape[0] == 0 or images.shape[0] % n:
+            raise ValueError(f"train_step: a batch of {images.shape[0]} images (labels: {label.shape[0]}) does not split into "
+                             f"{n} equal micro-batches")
+        return list(images.chunk(n)), list(label.chunk(n))
+    xs, ys = list(images), list(label)
+    if len(xs) != len(ys) or not 1 <= len(xs) <= control.accumulate:
+        raise ValueError(f"train_step: {len(xs)} image / {len(ys)} label micro-batches for accumulate={control.accumulate}")
+    if any(x.shape != xs[0].shape for x in xs) or any(y.shape != ys[0].shape for y in ys):
+        raise ValueError("train_step: the micro-batches of a step have one shape")
+    return xs, ys
+
+
+def _controlled_micro_batch(model, opt, images, label, control, params, first, all_ranks):
+    """forward, loss, backward of one micro-batch and its gradients added to the accumulators; -> the loss"""
+    loss = tramba_loss(model(images), label)
+    # .grad = None on every parameter: the engine then adopts the gradient tensors as they are, which is what lets the
+    # deferred partial sums stay on (see train_step) -- the adding is tramba_grad_accumulate's, not one `+=` per parameter
+    for g in opt.param_groups:
+        for p in g["params"]:
+            p.grad = None
+    if DEFER_SUMS:
+        with hip.deferred_sums():
+            loss.backward()
+    else:
+        loss.backward()
+    control._accumulate(params, first, all_ranks)
+    return loss.detach()
+
+
+def _controlled_finish(model, opt, control, params, count, reducer, all_ranks, on_device):
+    control._finish(opt, params, count, reducer, all_ranks)
+    refresh_lowp_shadows(model, getattr(model, "compute_dtype", None))
+    if on_device:
+        refresh_dw_packs(model)
+
+
+def _controlled_step(model, opt, images, label, reducer, control):
+    xs, ys = _micro_batches(images, label, control)
+    params = control._bind(opt, reducer)
+    all_ranks = reducer is not None and reducer.world > 1      # another rank may hold a gradient this one does not
+    control._begin_step()
+    total = None
+    for k, (x, y) in enumerate(zip(xs, ys)):
+        loss = _controlled_micro_batch(model, opt, x, y, control, params, k == 0, all_ranks)
+        total = loss if total is None else total + loss
+    _controlled_finish(model, opt, control, params, len(xs), reducer, all_ranks, xs[0].is_cuda)
+    return total / len(xs)
+
+
+def train_step(model, opt, images, label, reducer=None, control=None):
     """One optimisation step (train.py:74-89).  `reducer` (tramba_amd.parallel.GradBucketReducer)
-    averages gradients across data-parallel ranks; its all-reduces overlap the backward."""
+    averages gradients across data-parallel ranks; its all-reduces overlap the backward.
+    `control` (StepControl): the step is built from `control.accumulate` micro-batches -- `images` / `label` are tensors
+    whose leading dimension splits into that many equal parts, or sequences of equal-shaped tensors, one per micro-batch
+    (a shorter sequence is a step over what it holds).  Every micro-batch runs forward, loss and backward by itself (its own
+    stochastic-depth table, its own BatchNorm statistics, as a data-parallel rank would), the gradients are added in
+    micro-batch order, then -- with a reducer: one all-reduce round of the accumulated buckets -- the norm of the mean
+    gradient, the clip factor and the skip decision are formed and the optimizer steps once.  Returns the mean of the
+    micro-batch losses."""
+    if control is not None:
+        return _controlled_step(model, opt, images, label, reducer, control)
     outputs = model(images)
     loss = tramba_loss(outputs, label)
     if reducer is not None:
@@ -276,23 +537,45 @@ def load_resume(resume, save_model, method, model, opt, map_location=None):
     return int(os.path.basename(resume).split("_")[-1].split(".")[0])
 
 
+def _grouped(batches, n):
+    """(images, label) batches -> ([images] * n, [label] * n) groups in order; the last one may be shorter, and a batch of
+    another shape (the short last batch of an epoch) starts a group of its own"""
+    xs, ys = [], []
+    for images, label in batches:
+        if xs and (images.shape != xs[0].shape or label.shape != ys[0].shape):
+            yield xs, ys
+            xs, ys = [], []
+        xs.append(images)
+        ys.append(label)
+        if len(xs) == n:
+            yield xs, ys
+            xs, ys = [], []
+    if xs:
+        yield xs, ys
+
+
 def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_model, method, start_epoch=0,
-        evaluate=None, see=0, best_mae=None, reducer=None, is_main=True, log=None, graph=False):
+        evaluate=None, see=0, best_mae=None, reducer=None, is_main=True, log=None, graph=False, control=None):
     """Epoch loop of train.py:212-263 around `train_step`.  `batches(epoch)` yields (images, label) device tensors;
     `evaluate(model, epoch) -> MAE` runs from epoch `see` on (train.py:237); rank 0 (`is_main`) writes the files.
     `graph=True` (single process, optimizer from `get_opt(..., capturable=True)`): every step is a hipGraph replay
-    (tramba_amd.graph.GraphedTrainStep), re-captured by itself when the learning rate steps."""
+    (tramba_amd.graph.GraphedTrainStep), re-captured by itself when the learning rate steps.
+    `control` (StepControl): `control.accumulate` consecutive batches of `batches(epoch)` make one optimizer step; a short
+    last group is a step over the batches it has, as a short last batch is a step today."""
     step_fn = train_step
     if graph:
         from .graph import GraphedTrainStep
-        graphed = GraphedTrainStep(model, opt, reducer=reducer)
-        step_fn = lambda m_, o_, images, label, reducer=None: graphed(images, label)  # noqa: E731
+        graphed = GraphedTrainStep(model, opt, reducer=reducer, control=control)
+        step_fn = lambda m_, o_, images, label, reducer=None, **kw: graphed(images, label)  # noqa: E731
     history = []
     for epoch in range(start_epoch, epochs):
         lr = adjust_learning_rate(opt, epoch, decay_epochs, base_lr, decay_factors)
         total, n = None, 0
-        for images, label in batches(epoch):
-            loss = step_fn(model, opt, images, label, reducer=reducer)
+        for images, label in (batches(epoch) if control is None else _grouped(batches(epoch), control.accumulate)):
+            if control is None:
+                loss = step_fn(model, opt, images, label, reducer=reducer)
+            else:
+                loss = step_fn(model, opt, images, label, reducer=reducer, control=control)
             total = loss.clone() if total is None else total + loss     # clone: a graphed step reuses its loss buffer
             n += 1
         mean_loss = float(total / max(n, 1)) if total is not None else float("nan")   # one host sync per epoch
