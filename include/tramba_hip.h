@@ -578,6 +578,33 @@ int tramba_sod_loss_finish(const float *const *parts, const int *nblk, const flo
 size_t tramba_sod_loss_grad_workspace(int planes, int h, int w, int hout, int wout);
 int tramba_sod_loss_grad(const float *logits, const float *label, const float *coef, const float *gscale, float *glogits,
                          void *workspace, size_t workspace_bytes, int planes, int h, int w, int hout, int wout, void *stream);
+/* ---- the weighted losses: structure_loss (utils/loss.py:14-34) and wbce (utils/loss.py:37-42) ----
+ * weit (planes, h, w) f32 = 1 + 5 |avg_pool2d(label, k, stride 1, padding k / 2) - label| (utils/loss.py:22 with k = 31,
+ * utils/loss.py:39 with k = 15): zero padding, divisor k * k everywhere (count_include_pad, torch's default).  Odd k <= 63, any
+ * h, w >= 1 (windows larger than the image included), labels any floats.  Separable sums in LDS, fixed order, plain stores. */
+int tramba_loss_weight_map(const float *label, float *weit, int planes, int h, int w, int k, void *stream);
+/* tramba_sod_loss_sums with a per-pixel weight W and a smoothed BCE target yhat = (1 - eps) y + eps / 2 (utils/loss.py:16-19,
+ * 26; eps = 0.001 for structure_loss, 0 for wbce):
+ *   part[plane][blk][0..5) = sum of { bce(z, yhat),  W bce(z, yhat),  W,  W sigmoid(z) y,  W (sigmoid(z) + y) }
+ * (utils/loss.py:27-28, 30-32; y unsmoothed in the last two, as there).  wmap (planes, hout, wout) f32 is the map of
+ * tramba_loss_weight_map (W = wmap) or, with weight_is_raw != 0, the caller's `weight` of utils/loss.py:23-24 (W = 1 + 5 wmap). */
+int tramba_sod_wloss_sums(const float *logits, const float *label, const float *wmap, float *part, int planes, int h, int w,
+                          int hout, int wout, int nblk, float eps, int weight_is_raw, void *stream);
+/* tramba_sod_loss_finish for the tables above (parts[o]: (planes, nblk[o], 5)).  With I = sum W p y, U = sum W (p + y):
+ *   loss[0] = sum_o weights[o] * ( BCE term + [with_iou] mean over planes of 1 - (I + 1) / (U - I + 1) )       (utils/loss.py:33-34)
+ *   per_pixel == 0: BCE term = sum bce / (planes npix) -- utils/loss.py:27 AS IT EXECUTES: `reduce='none'` is the legacy
+ *                   argument and a non-empty string is true, so the call returns the batch mean and W cancels in line 28;
+ *   per_pixel != 0: BCE term = mean over planes of (sum W bce) / (sum W) -- lines 27-28 with reduction='none', as published.
+ * coefs[o] (planes, 4) f32 = { a, cI, cU, per_pixel } of d loss / d resized logit = a omega (p - yhat) + p (1 - p) W (cI y + cU),
+ * omega = W when per_pixel, else 1;  with_iou == 0 (wbce): cI = cU = 0.  Host arrays by value, planes <= 512, as above. */
+int tramba_sod_wloss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs, int nout,
+                            int planes, int64_t npix, int per_pixel, int with_iou, float *loss, void *stream);
+/* tramba_sod_loss_grad for the weighted losses (autograd through utils/loss.py:26-34): the same passes reading the weight map
+ * as well, the same device scalar gscale, the same workspace and limits. */
+size_t tramba_sod_wloss_grad_workspace(int planes, int h, int w, int hout, int wout);
+int tramba_sod_wloss_grad(const float *logits, const float *label, const float *wmap, const float *coef, const float *gscale,
+                          float *glogits, void *workspace, size_t workspace_bytes, int planes, int h, int w, int hout, int wout,
+                          float eps, int weight_is_raw, void *stream);
 /* One Adam step (torch.optim.Adam as train.py:266-280 builds it: amsgrad off, maximize off) on `count` fp32 tensors:
  *   steps[i][0] += 1 (device counters, part of the optimizer's state_dict);  g += weight_decay p;
  *   exp_avg = lerp(exp_avg, g, 1 - beta1);  exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g g;

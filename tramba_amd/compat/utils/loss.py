@@ -1,2 +1,2 @@
-"""Shim for utils/loss.py (only iou_loss is used by train.py:80-85)."""
-from tramba_amd.train import iou_loss  # noqa: F401
+"""Shim for utils/loss.py: iou_loss (what train.py:80-85 uses), structure_loss and wbce, argument order as there."""
+from tramba_amd.train import iou_loss, structure_loss, wbce  # noqa: F401

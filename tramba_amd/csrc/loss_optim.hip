@@ -16,6 +16,9 @@
 //     (tramba_step_ctl) that the kernels read and write, so a replayed hipGraph needs no host value that changes from
 //     step to step.
 //
+//   * the reference's other two losses (utils/loss.py:14-42: structure_loss, wbce): the same passes with a per-pixel weight
+//     map formed once per call from the label (separable box sums in LDS), 12 B per label pixel and output;
+//
 // All are HBM-streaming kernels: the loss moves 8 B per label pixel and output, Adam 28 B per parameter, an accumulate
 // pass 12 B (8 B on the first micro-batch), the norm 4 B.
 #include "common.h"
@@ -236,6 +239,207 @@ __global__ __launch_bounds__(256) void sod_loss_grad_cols_kernel(const float *__
     float acc = 0.f;
     for (int Y = Y0; Y <= Y1; ++Y) acc = fmaf(tap_weight(tap(Y, sy, h), y), r[(long)Y * w], acc);
     gz[i] = acc;
+}
+
+// ------------------------------------------------------------------------------------------------- weighted losses
+// structure_loss / wbce (utils/loss.py:14-42): the same passes with a per-pixel weight W = 1 + 5 |box_k(y) - y| and a
+// smoothed BCE target yhat = (1 - eps) y + eps / 2.  The weight depends on the label only: one map per loss call, shared by
+// the deep-supervision outputs (12 B per label pixel and output instead of 8, plus the map's own pass).
+//
+// weit = 1 + 5 |avg_pool2d(label, k, stride 1, pad k / 2) - label|, zero padding, divisor k * k (count_include_pad).  A
+// workgroup owns a 32 x 32 tile: the tile with its halo of r = k / 2 goes to LDS (zeros outside the image), row sums of k
+// neighbours into a second LDS band, then column sums of those -- every sum in a fixed order that depends on the pixel's
+// position only.
+constexpr int kWmapTile = 32, kWmapMaxK = 63;
+__global__ __launch_bounds__(256) void loss_weight_map_kernel(const float *__restrict__ label, float *__restrict__ weit, int H,
+                                                             int W, int r)
+{
+    extern __shared__ float wm_lds[];
+    const int side = kWmapTile + 2 * r, k = 2 * r + 1;
+    float *raw = wm_lds;                    // [side][side]
+    float *hs = wm_lds + side * side;       // [side][kWmapTile]
+    const int x0 = blockIdx.x * kWmapTile, y0 = blockIdx.y * kWmapTile;
+    const long base = (long)blockIdx.z * H * W;
+    const float *yp = label + base;
+    for (int e = threadIdx.x; e < side * side; e += blockDim.x) {
+        const int ry = e / side, rx = e - ry * side, Y = y0 - r + ry, X = x0 - r + rx;
+        raw[e] = (Y >= 0 && Y < H && X >= 0 && X < W) ? yp[(long)Y * W + X] : 0.f;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < side * kWmapTile; e += blockDim.x) {
+        const float *p = raw + (e / kWmapTile) * side + (e % kWmapTile);
+        float s = 0.f;
+        for (int d = 0; d < k; ++d) s += p[d];
+        hs[e] = s;
+    }
+    __syncthreads();
+    const float kk = (float)(k * k);
+    for (int e = threadIdx.x; e < kWmapTile * kWmapTile; e += blockDim.x) {
+        const int y = e / kWmapTile, x = e % kWmapTile, Y = y0 + y, X = x0 + x;
+        if (Y >= H || X >= W) continue;
+        float s = 0.f;
+        for (int d = 0; d < k; ++d) s += hs[(y + d) * kWmapTile + x];
+        weit[base + (long)Y * W + X] = 1.f + 5.f * fabsf(s / kk - raw[(y + r) * side + x + r]);
+    }
+}
+
+// How the kernels below read the map: W = wadd + wmul * wmap[i] -- { 0, 1 } for the box-filter map above, { 1, 5 } for a
+// caller's `weight` tensor (utils/loss.py:24); and the BCE target yhat = ysc * y + yadd = (1 - eps) y + eps / 2.
+struct WLossForm {
+    float wadd, wmul, ysc, yadd;
+};
+
+// part[plane][blockIdx.x][5] = { sum bce(z, yhat), sum W bce, sum W, sum W p y, sum W (p + y) }  (y unsmoothed in the last two)
+template <bool SAME>
+__global__ __launch_bounds__(kLossThreads) void sod_wloss_sums_kernel(const float *__restrict__ z,
+                                                                     const float *__restrict__ label,
+                                                                     const float *__restrict__ wmap,
+                                                                     float *__restrict__ part, int h, int w, int H, int W,
+                                                                     WLossForm f)
+{
+    __shared__ float red[kLossThreads / kWave][5];
+    const int plane = blockIdx.y, nblk = gridDim.x;
+    const long npix = (long)H * W;
+    const float *zp = z + (long)plane * h * w, *yp = label + plane * npix, *wp = wmap + plane * npix;
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (long i = (long)blockIdx.x * kLossThreads + threadIdx.x; i < npix; i += (long)nblk * kLossThreads) {
+        float zz;
+        if constexpr (SAME) {
+            zz = zp[i];
+        } else {
+            const int Y = (int)(i / W), X = (int)(i - (long)Y * W);
+            zz = resized(zp, w, tap(Y, sy, h), tap(X, sx, w));
+        }
+        const float y = yp[i], wt = fmaf(f.wmul, wp[i], f.wadd);
+        float p, tail;
+        sig_terms(zz, p, tail);
+        const float bce = fmaxf(zz, 0.f) - zz * fmaf(f.ysc, y, f.yadd) + tail;
+        s[0] += bce;
+        s[1] = fmaf(wt, bce, s[1]);
+        s[2] += wt;
+        s[3] = fmaf(wt, p * y, s[3]);
+        s[4] = fmaf(wt, p + y, s[4]);
+    }
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        s[j] = wave_sum(s[j]);
+        if (lane == 0) red[wv][j] = s[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        float t = 0.f;
+        for (int q = 0; q < kLossThreads / kWave; ++q) t += red[q][threadIdx.x];
+        part[((long)plane * nblk + blockIdx.x) * 5 + threadIdx.x] = t;
+    }
+}
+
+struct WLossFinishArgs {
+    const float *part[kLossOutputs];   // (planes, nblk[i], 5)
+    float *coef[kLossOutputs];         // (planes, 4): { a, cI, cU, omega selector }
+    int nblk[kLossOutputs];
+    float weight[kLossOutputs];
+    int nout, planes, pixel, iou;
+    double npix;
+    float *loss;
+};
+// One block, as sod_loss_finish_kernel.  Per output o and plane q, with I = sum W p y, U = sum W (p + y), D = U - I + 1:
+//   BCE term, the reference as it executes (`reduce='none'` resolves to the mean, the weight cancels): sum_q bce_q / (planes npix)
+//             per pixel (the published form):                                        mean_q (sum W bce)_q / (sum W)_q
+//   IoU term (when on): mean_q (1 - (I + 1) / D)
+// and the coefficients of d loss / d logit = a omega (p - yhat) + p (1 - p) W (cI y + cU):
+//   reference: omega = 1 (c[3] = 0), a = w_o / (planes npix);   per pixel: omega = W (c[3] = 1), a = w_o / (planes (sum W)_q);
+//   cI = -(w_o / planes) (U + 2) / D^2,  cU = (w_o / planes) (I + 1) / D^2,  both 0 without the IoU term.
+__global__ __launch_bounds__(1024) void sod_wloss_finish_kernel(WLossFinishArgs a)
+{
+    __shared__ double term[kLossOutputs][kLossPlanes];
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    for (int item = wv; item < a.nout * a.planes; item += nwave) {
+        const int o = item / a.planes, q = item - o * a.planes;
+        const float *p = a.part[o] + (long)q * a.nblk[o] * 5;
+        double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int s = lane; s < a.nblk[o]; s += kWave)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) v[j] += (double)p[5 * s + j];
+#pragma unroll
+        for (int j = 0; j < 5; ++j) v[j] = wave_sum_f64(v[j]);
+        if (lane == 0) {
+            const double w = (double)a.weight[o], planes = (double)a.planes, I = v[3], U = v[4], D = U - I + 1.0;
+            const double bce = a.pixel ? v[1] / v[2] / planes : v[0] / (planes * a.npix);
+            term[o][q] = w * (bce + (a.iou ? (1.0 - (I + 1.0) / D) / planes : 0.0));
+            float *c = a.coef[o] + 4 * (long)q;
+            c[0] = (float)(w / (planes * (a.pixel ? v[2] : a.npix)));
+            c[1] = a.iou ? (float)(-(w / planes) * (U + 2.0) / (D * D)) : 0.f;
+            c[2] = a.iou ? (float)((w / planes) * (I + 1.0) / (D * D)) : 0.f;
+            c[3] = a.pixel ? 1.f : 0.f;
+        }
+    }
+    __syncthreads();
+    if (wv == 0) {
+        double s = 0.0;
+        for (int item = lane; item < a.nout * a.planes; item += kWave) s += term[item / a.planes][item % a.planes];
+        s = wave_sum_f64(s);
+        if (lane == 0) *a.loss = (float)s;
+    }
+}
+
+struct WLossCoef {
+    float ca, ci, cu;
+    bool pixel;
+};
+__device__ __forceinline__ WLossCoef wloss_coef(const float *__restrict__ coef, const float *__restrict__ gscale, int plane)
+{
+    const float gs = gscale ? *gscale : 1.f;
+    return {gs * coef[4 * plane], gs * coef[4 * plane + 1], gs * coef[4 * plane + 2], coef[4 * plane + 3] != 0.f};
+}
+__device__ __forceinline__ float wloss_grad(float zz, float y, float wraw, const WLossCoef &c, const WLossForm &f)
+{
+    float p, tail;
+    sig_terms(zz, p, tail);
+    const float wt = fmaf(f.wmul, wraw, f.wadd);
+    return c.ca * (c.pixel ? wt : 1.f) * (p - fmaf(f.ysc, y, f.yadd)) + p * (1.f - p) * wt * fmaf(c.ci, y, c.cu);
+}
+
+// the weighted forms of sod_loss_grad_same_kernel / sod_loss_grad_rows_kernel (the columns kernel serves both)
+__global__ __launch_bounds__(256) void sod_wloss_grad_same_kernel(const float *__restrict__ z, const float *__restrict__ label,
+                                                                 const float *__restrict__ wmap,
+                                                                 const float *__restrict__ coef,
+                                                                 const float *__restrict__ gscale, float *__restrict__ gz,
+                                                                 long npix, WLossForm f)
+{
+    const int plane = blockIdx.y;
+    const WLossCoef c = wloss_coef(coef, gscale, plane);
+    const long base = (long)plane * npix;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x)
+        gz[base + i] = wloss_grad(z[base + i], label[base + i], wmap[base + i], c, f);
+}
+__global__ __launch_bounds__(256) void sod_wloss_grad_rows_kernel(const float *__restrict__ z, const float *__restrict__ label,
+                                                                 const float *__restrict__ wmap,
+                                                                 const float *__restrict__ coef,
+                                                                 const float *__restrict__ gscale, float *__restrict__ rows,
+                                                                 int h, int w, int H, int W, WLossForm f)
+{
+    extern __shared__ float band[];               // [kGradRows][W]
+    const int plane = blockIdx.y, yb = blockIdx.x * kGradRows;
+    const WLossCoef c = wloss_coef(coef, gscale, plane);
+    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
+    const float *zp = z + (long)plane * h * w, *yp = label + (long)plane * H * W, *wp = wmap + (long)plane * H * W;
+    for (int e = threadIdx.x; e < kGradRows * W; e += blockDim.x) {
+        const int r = e / W, X = e - r * W, Y = yb + r;
+        if (Y < H)
+            band[e] = wloss_grad(resized(zp, w, tap(Y, sy, h), tap(X, sx, w)), yp[(long)Y * W + X], wp[(long)Y * W + X], c, f);
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kGradRows * w; e += blockDim.x) {
+        const int r = e / w, x = e - r * w, Y = yb + r;
+        if (Y >= H) continue;
+        int X0, X1;
+        window(x, sx, W, X0, X1);
+        float acc = 0.f;
+        for (int X = X0; X <= X1; ++X) acc = fmaf(tap_weight(tap(X, sx, w), x), band[r * W + X], acc);
+        rows[((long)plane * H + Y) * w + x] = acc;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------- Adam
@@ -667,6 +871,110 @@ extern "C" int tramba_sod_loss_grad(const float *logits, const float *label, con
         TRAMBA_LAUNCH_CHECK();
         const long total = (long)planes * h * w;
         TRAMBA_CHECK((total + 255) / 256 < 2147483647L, "sod_loss_grad: too many workgroups");
+        hipLaunchKernelGGL(sod_loss_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows, glogits, h, w,
+                           hout, total);
+    }
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_loss_weight_map(const float *label, float *weit, int planes, int h, int w, int k, void *stream)
+{
+    TRAMBA_CHECK(label && weit, "loss_weight_map: null tensor");
+    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0, "loss_weight_map: bad shape");
+    TRAMBA_CHECK(k >= 1 && k <= kWmapMaxK && (k & 1), "loss_weight_map: odd windows of 1..%d (got %d)", kWmapMaxK, k);
+    const long gx = ((long)w + kWmapTile - 1) / kWmapTile, gy = ((long)h + kWmapTile - 1) / kWmapTile;
+    TRAMBA_CHECK(gy <= 65535, "loss_weight_map: at most %d rows (got %d)", 65535 * kWmapTile, h);
+    const int r = k / 2, side = kWmapTile + 2 * r;
+    hipLaunchKernelGGL(loss_weight_map_kernel, dim3((unsigned)gx, (unsigned)gy, (unsigned)planes), dim3(256),
+                       (size_t)(side * side + side * kWmapTile) * sizeof(float), (hipStream_t)stream, label, weit, h, w, r);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+static bool wloss_form(float eps, int weight_is_raw, WLossForm &f)
+{
+    if (!(eps >= 0.f && eps < 1.f)) return false;
+    f = weight_is_raw ? WLossForm{1.f, 5.f, 1.f - eps, 0.5f * eps} : WLossForm{0.f, 1.f, 1.f - eps, 0.5f * eps};
+    return true;
+}
+
+extern "C" int tramba_sod_wloss_sums(const float *logits, const float *label, const float *wmap, float *part, int planes,
+                                     int h, int w, int hout, int wout, int nblk, float eps, int weight_is_raw, void *stream)
+{
+    TRAMBA_CHECK(logits && label && wmap && part, "sod_wloss_sums: null tensor");
+    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0 && hout > 0 && wout > 0 && nblk > 0, "sod_wloss_sums: bad shape");
+    WLossForm f;
+    TRAMBA_CHECK(wloss_form(eps, weight_is_raw, f), "sod_wloss_sums: label smoothing in [0, 1)");
+    const dim3 grid((unsigned)nblk, (unsigned)planes);
+    if (h == hout && w == wout)
+        hipLaunchKernelGGL(sod_wloss_sums_kernel<true>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, wmap,
+                           part, h, w, hout, wout, f);
+    else
+        hipLaunchKernelGGL(sod_wloss_sums_kernel<false>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, wmap,
+                           part, h, w, hout, wout, f);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_sod_wloss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs,
+                                       int nout, int planes, int64_t npix, int per_pixel, int with_iou, float *loss,
+                                       void *stream)
+{
+    TRAMBA_CHECK(parts && nblk && coefs && loss, "sod_wloss_finish: null argument");
+    TRAMBA_CHECK(nout > 0 && nout <= kLossOutputs, "sod_wloss_finish: 1..%d outputs (got %d)", kLossOutputs, nout);
+    TRAMBA_CHECK(planes > 0 && planes <= kLossPlanes && npix > 0, "sod_wloss_finish: 1..%d planes (got %d)", kLossPlanes, planes);
+    WLossFinishArgs a;
+    for (int o = 0; o < kLossOutputs; ++o) {
+        const bool on = o < nout;
+        TRAMBA_CHECK(!on || (parts[o] && coefs[o] && nblk[o] > 0), "sod_wloss_finish: output %d: null table", o);
+        a.part[o] = on ? parts[o] : nullptr;
+        a.coef[o] = on ? coefs[o] : nullptr;
+        a.nblk[o] = on ? nblk[o] : 0;
+        a.weight[o] = on ? (weights ? weights[o] : 1.f) : 0.f;
+    }
+    a.nout = nout;
+    a.planes = planes;
+    a.pixel = per_pixel != 0;
+    a.iou = with_iou != 0;
+    a.npix = (double)npix;
+    a.loss = loss;
+    hipLaunchKernelGGL(sod_wloss_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" size_t tramba_sod_wloss_grad_workspace(int planes, int h, int w, int hout, int wout)
+{
+    return tramba_sod_loss_grad_workspace(planes, h, w, hout, wout);
+}
+
+extern "C" int tramba_sod_wloss_grad(const float *logits, const float *label, const float *wmap, const float *coef,
+                                     const float *gscale, float *glogits, void *workspace, size_t workspace_bytes, int planes,
+                                     int h, int w, int hout, int wout, float eps, int weight_is_raw, void *stream)
+{
+    TRAMBA_CHECK(logits && label && wmap && coef && glogits, "sod_wloss_grad: null tensor");
+    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0, "sod_wloss_grad: bad shape");
+    WLossForm f;
+    TRAMBA_CHECK(wloss_form(eps, weight_is_raw, f), "sod_wloss_grad: label smoothing in [0, 1)");
+    hipStream_t s = (hipStream_t)stream;
+    if (h == hout && w == wout) {
+        const long npix = (long)h * w;
+        const unsigned gx = (unsigned)((npix + 1023) / 1024);
+        hipLaunchKernelGGL(sod_wloss_grad_same_kernel, dim3(gx, (unsigned)planes), dim3(256), 0, s, logits, label, wmap, coef,
+                           gscale, glogits, npix, f);
+    } else {
+        TRAMBA_CHECK(hout >= h && wout >= w, "sod_wloss_grad: outputs are resized UP to the label (%dx%d -> %dx%d)", h, w, hout, wout);
+        TRAMBA_CHECK(wout <= 4096, "sod_wloss_grad: label rows of at most 4096 pixels (got %d)", wout);
+        TRAMBA_CHECK(workspace && workspace_bytes >= tramba_sod_wloss_grad_workspace(planes, h, w, hout, wout),
+                     "sod_wloss_grad: workspace of %zu bytes needed", tramba_sod_wloss_grad_workspace(planes, h, w, hout, wout));
+        float *rows = (float *)workspace;
+        hipLaunchKernelGGL(sod_wloss_grad_rows_kernel, dim3((unsigned)((hout + kGradRows - 1) / kGradRows), (unsigned)planes),
+                           dim3(256), (size_t)kGradRows * wout * sizeof(float), s, logits, label, wmap, coef, gscale, rows, h, w,
+                           hout, wout, f);
+        TRAMBA_LAUNCH_CHECK();
+        const long total = (long)planes * h * w;
+        TRAMBA_CHECK((total + 255) / 256 < 2147483647L, "sod_wloss_grad: too many workgroups");
         hipLaunchKernelGGL(sod_loss_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows, glogits, h, w,
                            hout, total);
     }

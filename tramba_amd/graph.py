@@ -83,9 +83,12 @@ class GraphedTrainStep:
     control record's counter on the device; the clip norm and 1 / micro-batches are host scalars baked into the second
     graph like the learning rates, so they are part of its key (a short last group of an epoch gets an update graph of
     its own, the full one stays).  The warm-up steps are one-micro-batch controlled steps; the control record, the
-    accumulators and `skipped_steps` are put back with the parameters afterwards.  Returns the mean micro-batch loss."""
+    accumulators and `skipped_steps` are put back with the parameters afterwards.  Returns the mean micro-batch loss.
 
-    def __init__(self, model, opt, reducer=None, warmup=2, control=None):
+    `loss` (tramba_amd.train.SodLoss; None: `tramba_loss`) is what `train_step(..., loss=loss)` takes; it is recorded into
+    the graphs, so it is fixed here, at construction."""
+
+    def __init__(self, model, opt, reducer=None, warmup=2, control=None, loss=None):
         if reducer is not None and getattr(reducer, "world", 1) > 1 and getattr(reducer, "find_unused", False):
             raise RuntimeError("GraphedTrainStep: a reducer with find_unused=True reads flags on the host every step and "
                                "cannot be captured")
@@ -93,6 +96,7 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep needs an optimizer with capturable=True")
         self.model, self.opt, self.reducer, self.warmup = model, opt, reducer, warmup
         self.control = control
+        self.loss = loss
         self._graphs = {}
         self._lr_key = None
         self._trainable_key = None
@@ -155,7 +159,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                       # optimizer state and all lazy caches exist before capture
             for _ in range(self.warmup):
-                train_step(self.model, self.opt, sx, sy, reducer=self.reducer)
+                train_step(self.model, self.opt, sx, sy, reducer=self.reducer, loss=self.loss)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         from .modules import model_mask_pool
@@ -168,7 +172,7 @@ class GraphedTrainStep:
         # calls -- what PyTorch documents for capturing NCCL collectives.
         mode = "thread_local" if (self.reducer is not None and getattr(self.reducer, "world", 1) > 1) else "global"
         with torch.cuda.graph(graph, capture_error_mode=mode):   # records, executes nothing
-            loss = train_step(self.model, self.opt, sx, sy, reducer=self.reducer)
+            loss = train_step(self.model, self.opt, sx, sy, reducer=self.reducer, loss=self.loss)
         keep_alive = (pool.probs, pool.buf, pool.buf32)              # the keep-probabilities the captured bernoulli / divide nodes read
         pool.forget_draw()                                  # (the table drawn during capture lives in the graph's pool)
         self._restore(saved)
@@ -189,7 +193,7 @@ class GraphedTrainStep:
         control._used = set()
         with torch.cuda.graph(graph, pool=pool, capture_error_mode=mode):
             # (first=True: store-or-add is the record's decision at replay, the host treats every micro-batch alike)
-            loss = train._controlled_micro_batch(self.model, self.opt, sx, sy, control, params, True, all_ranks)
+            loss = train._controlled_micro_batch(self.model, self.opt, sx, sy, control, params, True, all_ranks, self.loss)
             if update:
                 train._controlled_finish(self.model, self.opt, control, params, count, self.reducer, all_ranks, True)
         control._used = set()
@@ -213,7 +217,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(self.warmup):
-                train_step(self.model, self.opt, [sx], [sy], reducer=self.reducer, control=self.control)
+                train_step(self.model, self.opt, [sx], [sy], reducer=self.reducer, control=self.control, loss=self.loss)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         return sx, sy, saved, rng

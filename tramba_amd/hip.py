@@ -120,6 +120,11 @@ SIGNATURES = {
     "tramba_sod_loss_finish": (c_int, [c_vp] * 4 + [c_int, c_int, c_i64, c_vp, c_vp]),
     "tramba_sod_loss_grad_workspace": (ctypes.c_size_t, [c_int] * 5),
     "tramba_sod_loss_grad": (c_int, [c_vp] * 6 + [ctypes.c_size_t] + [c_int] * 5 + [c_vp]),
+    "tramba_loss_weight_map": (c_int, [c_vp] * 2 + [c_int] * 4 + [c_vp]),
+    "tramba_sod_wloss_sums": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_f, c_int, c_vp]),
+    "tramba_sod_wloss_finish": (c_int, [c_vp] * 4 + [c_int, c_int, c_i64, c_int, c_int, c_vp, c_vp]),
+    "tramba_sod_wloss_grad_workspace": (ctypes.c_size_t, [c_int] * 5),
+    "tramba_sod_wloss_grad": (c_int, [c_vp] * 7 + [ctypes.c_size_t] + [c_int] * 5 + [c_f, c_int, c_vp]),
     "tramba_adam_step": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp]),
     "tramba_grad_accumulate": (c_int, [c_vp] * 3 + [c_int, c_vp, c_vp]),
     "tramba_grad_norm_workspace": (ctypes.c_size_t, [c_vp, c_int]),
@@ -1136,6 +1141,77 @@ def sod_loss_grad(output, label, coef, gscale=None):
     ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=output.device) if nbytes else None
     _check(lib().tramba_sod_loss_grad(_ptr(output), _ptr(label), _ptr(coef), _ptr(gscale), _ptr(g), _ptr(ws), nbytes, planes, h, w,
                                       hh, ww, _stream()), "sod_loss_grad")
+    return g
+
+
+def loss_weight_map(label, k):
+    """weit = 1 + 5 |avg_pool2d(label, k, stride 1, padding k // 2) - label| (utils/loss.py:22 with k = 31, :39 with k = 15):
+    label (B, C, H, W) f32, odd k <= 63.  One launch; the map is shared by every deep-supervision output of a loss call."""
+    _dev(label)
+    if label.dtype != torch.float32 or label.dim() != 4:
+        raise TrambaHipError("loss_weight_map: a (B, C, H, W) fp32 label")
+    hh, ww = label.shape[-2:]
+    weit = torch.empty_like(label)
+    _check(lib().tramba_loss_weight_map(_ptr(label), _ptr(weit), label.numel() // (hh * ww), hh, ww, int(k), _stream()),
+           "loss_weight_map")
+    return weit
+
+
+def _wloss_check(what, tensors, label, wmap):
+    _dev(label, wmap, *tensors)
+    if label.dtype != torch.float32 or wmap.dtype != torch.float32 or any(o.dtype != torch.float32 for o in tensors):
+        raise TrambaHipError(f"{what}: fp32 logits, labels and weights only")
+    if wmap.shape != label.shape:
+        raise TrambaHipError(f"{what}: the weight map {tuple(wmap.shape)} does not match the label {tuple(label.shape)}")
+
+
+def sod_wloss(outputs, label, wmap, weights=None, eps=0.0, per_pixel=False, with_iou=True, weight_is_raw=False):
+    """`sod_loss` for the weighted losses of utils/loss.py:14-42 (structure_loss: eps = 0.001, with_iou; wbce: eps = 0, no IoU
+    term): wmap (B, C, H, W) f32 from `loss_weight_map`, or the caller's `weight` tensor with weight_is_raw (W = 1 + 5 wmap).
+    per_pixel: the BCE term weighted pixel by pixel (the published form) instead of the reference as it executes (batch-mean
+    BCE).  Returns (loss, coefs) as `sod_loss`; coefs feeds `sod_wloss_grad`."""
+    _wloss_check("sod_wloss", outputs, label, wmap)
+    hh, ww = label.shape[-2:]
+    planes = label.numel() // (hh * ww)
+    nout = len(outputs)
+    if not 0 < nout <= 8:
+        raise TrambaHipError(f"sod_wloss: 1..8 outputs, got {nout}")
+    nblk = _loss_nblk(hh * ww)
+    stream = _stream()
+    parts = torch.empty((nout, planes, nblk, 5), dtype=torch.float32, device=label.device)
+    coefs = torch.empty((nout, planes, 4), dtype=torch.float32, device=label.device)
+    for i, o in enumerate(outputs):
+        h, w = o.shape[-2:]
+        if o.numel() != planes * h * w or h > hh or w > ww:
+            raise TrambaHipError(f"sod_wloss: output {i} {tuple(o.shape)} does not match the label {tuple(label.shape)}")
+        _check(lib().tramba_sod_wloss_sums(_ptr(o), _ptr(label), _ptr(wmap), parts[i].data_ptr(), planes, h, w, hh, ww, nblk,
+                                           float(eps), int(bool(weight_is_raw)), stream), "sod_wloss_sums")
+    loss = torch.empty((), dtype=torch.float32, device=label.device)
+    pp = (ctypes.c_void_p * nout)(*[parts[i].data_ptr() for i in range(nout)])
+    cc = (ctypes.c_void_p * nout)(*[coefs[i].data_ptr() for i in range(nout)])
+    nb = (ctypes.c_int * nout)(*([nblk] * nout))
+    wt = None if weights is None else (ctypes.c_float * nout)(*[float(w) for w in weights])
+    _check(lib().tramba_sod_wloss_finish(pp, nb, wt, cc, nout, planes, hh * ww, int(bool(per_pixel)), int(bool(with_iou)),
+                                         _ptr(loss), stream), "sod_wloss_finish")
+    return loss, coefs
+
+
+def sod_wloss_grad(output, label, wmap, coef, gscale=None, eps=0.0, weight_is_raw=False):
+    """d loss / d output for one output of `sod_wloss` (the same eps / weight_is_raw), times the device scalar `gscale`."""
+    _wloss_check("sod_wloss_grad", (output,), label, wmap)
+    _dev(coef, gscale)
+    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1):
+        raise TrambaHipError("sod_wloss_grad: the incoming gradient must be one fp32 scalar")
+    hh, ww = label.shape[-2:]
+    h, w = output.shape[-2:]
+    planes = label.numel() // (hh * ww)
+    if output.numel() != planes * h * w or h > hh or w > ww:
+        raise TrambaHipError(f"sod_wloss_grad: output {tuple(output.shape)} does not match the label {tuple(label.shape)}")
+    g = torch.empty_like(output)
+    nbytes = lib().tramba_sod_wloss_grad_workspace(planes, h, w, hh, ww)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=output.device) if nbytes else None
+    _check(lib().tramba_sod_wloss_grad(_ptr(output), _ptr(label), _ptr(wmap), _ptr(coef), _ptr(gscale), _ptr(g), _ptr(ws), nbytes,
+                                       planes, h, w, hh, ww, float(eps), int(bool(weight_is_raw)), _stream()), "sod_wloss_grad")
     return g
 
 

@@ -2,6 +2,7 @@
 
 loss:       train.py:76-85 -- every output bilinearly resized to the label size, then
             binary_cross_entropy_with_logits + iou_loss (utils/loss.py:6-11), weights 1.
+            `SodLoss` selects the reference's other two losses instead (structure_loss, wbce: utils/loss.py:14-42).
 optimizer:  train.py:266-280 -- Adam, parameters whose name contains "encoder" at 0.1 x lr.
 lr decay:   utils/lr.py:1-17.
 epoch loop, resume / best-MAE checkpoint files: train.py:212-263.
@@ -92,6 +93,144 @@ def tramba_loss(outputs, label, loss_weights=None):
             term = term * loss_weights[i]
         total = term if total is None else total + term
     return total
+
+
+# ----------------------------------------------------------------------------- structure loss / weighted BCE
+# utils/loss.py:14-42.  The reference calls F.binary_cross_entropy_with_logits(..., reduce='none'): `reduce` is the legacy
+# argument and a non-empty string is true, so the call returns the batch MEAN and the weight cancels out of the BCE term
+# (lines 27-28, 40-41).  bce="reference" is that loss as it executes -- what continues a reference experiment;
+# bce="pixel" weights the BCE pixel by pixel, the loss as published (F3Net).
+_WLOSS_KINDS = {"structure": (31, 0.001, True), "wbce": (15, 0.0, False)}      # kind: (box window, label smoothing, IoU term)
+_WLOSS_READINGS = ("reference", "pixel")
+
+
+class _SodWLossHIP(torch.autograd.Function):
+    """`_SodLossHIP` for the weighted losses: five sums per image and output in one pass each, one finishing block, one
+    gradient pass per output; the weight map is the caller's (one launch per loss call, shared by the outputs)."""
+
+    @staticmethod
+    def forward(ctx, label, wmap, form, *outs):
+        weights, eps, per_pixel, with_iou, raw = form
+        loss, coefs = hip.sod_wloss(outs, label, wmap, weights, eps, per_pixel, with_iou, raw)
+        ctx.save_for_backward(label, wmap, coefs, *outs)
+        ctx.form = (eps, raw)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        label, wmap, coefs, *outs = ctx.saved_tensors
+        gl = gl.to(torch.float32).contiguous()
+        eps, raw = ctx.form
+        return (None, None, None) + tuple(hip.sod_wloss_grad(o, label, wmap, coefs[i], gl, eps, raw)
+                                          if ctx.needs_input_grad[3 + i] else None for i, o in enumerate(outs))
+
+
+def _weighted_term(o, label, weit, eps, with_iou, per_pixel):
+    """one output at label size against the label: utils/loss.py:26-34 (40-42 without the IoU term)"""
+    bce = F.binary_cross_entropy_with_logits(o, (1 - eps) * label + eps / 2, reduction="none" if per_pixel else "mean")
+    if per_pixel:
+        bce = ((weit * bce).sum(dim=(2, 3)) / weit.sum(dim=(2, 3))).mean()
+    if not with_iou:
+        return bce
+    p = torch.sigmoid(o)
+    inter = ((p * label) * weit).sum(dim=(2, 3))
+    union = ((p + label) * weit).sum(dim=(2, 3))
+    return bce + (1 - (inter + 1) / (union - inter + 1)).mean()
+
+
+def _weighted_loss(kind, bce, outputs, label, weight=None, loss_weights=None):
+    if kind not in _WLOSS_KINDS:
+        raise ValueError(f"unknown weighted loss {kind!r}: one of {sorted(_WLOSS_KINDS)}")
+    if bce not in _WLOSS_READINGS:
+        raise ValueError(f"bce={bce!r}: 'reference' (the loss as utils/loss.py executes) or 'pixel' (per-pixel weights)")
+    k, eps, with_iou = _WLOSS_KINDS[kind]
+    if weight is not None and kind != "structure":
+        raise ValueError("only structure_loss takes a caller's weight (utils/loss.py:15)")
+    outputs = list(outputs)
+    if loss_weights is not None and len(loss_weights) != len(outputs):
+        raise ValueError(f"{kind}: {len(loss_weights)} loss weights for {len(outputs)} outputs")
+    per_pixel = bce == "pixel"
+    if _loss_on_device(outputs, label) and (weight is None or (weight.is_cuda and weight.shape == label.shape)):
+        lab = label.float().contiguous()
+        wmap = hip.loss_weight_map(lab, k) if weight is None else weight.detach().float().contiguous()
+        form = (None if loss_weights is None else tuple(float(w) for w in loss_weights), eps, per_pixel, with_iou,
+                weight is not None)
+        return _SodWLossHIP.apply(lab, wmap, form, *[o.float().contiguous() for o in outputs])
+    # host tensors / shapes the kernels refuse: the reference's own composition.  The LABEL picks the precision, as
+    # tramba_loss's .float() does: fp64 only when the label is fp64 (fp64 logits against an fp32 label compute in fp32),
+    # fp32 for every other label dtype, bf16 logits included
+    dtype = torch.float64 if label.dtype == torch.float64 else torch.float32
+    label = label.to(dtype)
+    h, w = label.shape[-2:]
+    if weight is None:
+        weit = 1 + 5 * torch.abs(F.avg_pool2d(label, kernel_size=k, stride=1, padding=k // 2) - label)
+    else:
+        weit = 1 + 5 * weight.to(dtype)
+    total = None
+    for i, o in enumerate(outputs):
+        o = o.to(dtype)
+        if o.shape[-2:] != (h, w):
+            o = _resize_bilinear(o, (h, w))
+        term = _weighted_term(o, label, weit, eps, with_iou, per_pixel)
+        if loss_weights is not None:
+            term = term * loss_weights[i]
+        total = term if total is None else total + term
+    return total
+
+
+def structure_loss(pred, mask, weight=None, bce="reference"):
+    """utils/loss.py:15-34 (L_STR): BCE against the smoothed labels + IoU weighted by 1 + 5 |avg_pool31(mask) - mask|, or by
+    1 + 5 `weight`.  bce="reference": what the reference computes (its BCE term is the unweighted batch mean, see above);
+    bce="pixel": the BCE weighted pixel by pixel.  On a HIP device the library's kernels, elsewhere a torch composition in
+    fp32 -- in fp64 only when `mask` is fp64 (the mask, not `pred`, picks the precision).
+    `weight` on the device must be a device tensor of exactly `mask`'s shape; any other `weight` (a host tensor, a shape
+    that only broadcasts) takes the torch composition, as shapes the kernels refuse do in `tramba_loss`.  The kernels treat
+    `weight` as a constant: no gradient flows to it on the device (the composition, like the reference, would give one)."""
+    return _weighted_loss("structure", bce, [pred], mask, weight)
+
+
+def wbce(pred, mask, bce="reference"):
+    """utils/loss.py:38-42 (L_wBCE), window 15, no smoothing; bce="reference" is plain mean BCE (the weight cancels)."""
+    return _weighted_loss("wbce", bce, [pred], mask)
+
+
+class SodLoss:
+    """Which loss a training step uses over the deep-supervision outputs: each output against the full-size label, the terms
+    summed with `loss_weights`, as `tramba_loss` does.
+
+      kind  "bce_iou"    BCE-with-logits + IoU (train.py:76-85): exactly `tramba_loss`, through the same kernels;
+            "structure"  utils/loss.py:15-34;      "wbce"  utils/loss.py:38-42;
+      bce   "reference" | "pixel": the two readings of the weighted BCE term (see `structure_loss`); no effect on "bce_iou".
+
+    `loss(outputs, label, weight=None)`; `weight` only with kind="structure" (utils/loss.py:23-24)."""
+
+    def __init__(self, kind="bce_iou", bce="reference", loss_weights=None):
+        if kind != "bce_iou" and kind not in _WLOSS_KINDS:
+            raise ValueError(f"SodLoss: kind={kind!r}: one of 'bce_iou', 'structure', 'wbce'")
+        if bce not in _WLOSS_READINGS:
+            raise ValueError(f"SodLoss: bce={bce!r}: 'reference' or 'pixel'")
+        self.kind, self.bce = kind, bce
+        self.loss_weights = None if loss_weights is None else tuple(float(w) for w in loss_weights)
+
+    def __call__(self, outputs, label, weight=None):
+        if self.kind == "bce_iou":
+            if weight is not None:
+                raise ValueError("SodLoss('bce_iou') takes no weight")
+            return tramba_loss(outputs, label, self.loss_weights)
+        return _weighted_loss(self.kind, self.bce, outputs, label, weight, self.loss_weights)
+
+    def __repr__(self):
+        return f"SodLoss(kind={self.kind!r}, bce={self.bce!r}, loss_weights={self.loss_weights!r})"
+
+
+def _step_loss(loss, outputs, label):
+    """the loss of a training step: `loss` is a SodLoss, None = tramba_loss.  Nothing else: a step may be recorded into a
+    hipGraph, and only the spec's own paths are known to be capture-safe"""
+    if loss is None:
+        return tramba_loss(outputs, label)
+    if not isinstance(loss, SodLoss):
+        raise TypeError(f"loss={loss!r}: a tramba_amd.train.SodLoss or None")
+    return loss(outputs, label)
 
 
 class Adam(torch.optim.Adam):
@@ -425,9 +564,9 @@ def _micro_batches(images, label, control):
     return xs, ys
 
 
-def _controlled_micro_batch(model, opt, images, label, control, params, first, all_ranks):
+def _controlled_micro_batch(model, opt, images, label, control, params, first, all_ranks, loss_fn=None):
     """forward, loss, backward of one micro-batch and its gradients added to the accumulators; -> the loss"""
-    loss = tramba_loss(model(images), label)
+    loss = _step_loss(loss_fn, model(images), label)
     # .grad = None on every parameter: the engine then adopts the gradient tensors as they are, which is what lets the
     # deferred partial sums stay on (see train_step) -- the adding is tramba_grad_accumulate's, not one `+=` per parameter
     for g in opt.param_groups:
@@ -449,20 +588,20 @@ def _controlled_finish(model, opt, control, params, count, reducer, all_ranks, o
         refresh_dw_packs(model)
 
 
-def _controlled_step(model, opt, images, label, reducer, control):
+def _controlled_step(model, opt, images, label, reducer, control, loss_fn=None):
     xs, ys = _micro_batches(images, label, control)
     params = control._bind(opt, reducer)
     all_ranks = reducer is not None and reducer.world > 1      # another rank may hold a gradient this one does not
     control._begin_step()
     total = None
     for k, (x, y) in enumerate(zip(xs, ys)):
-        loss = _controlled_micro_batch(model, opt, x, y, control, params, k == 0, all_ranks)
+        loss = _controlled_micro_batch(model, opt, x, y, control, params, k == 0, all_ranks, loss_fn)
         total = loss if total is None else total + loss
     _controlled_finish(model, opt, control, params, len(xs), reducer, all_ranks, xs[0].is_cuda)
     return total / len(xs)
 
 
-def train_step(model, opt, images, label, reducer=None, control=None):
+def train_step(model, opt, images, label, reducer=None, control=None, loss=None):
     """One optimisation step (train.py:74-89).  `reducer` (tramba_amd.parallel.GradBucketReducer)
     averages gradients across data-parallel ranks; its all-reduces overlap the backward.
     `control` (StepControl): the step is built from `control.accumulate` micro-batches -- `images` / `label` are tensors
@@ -471,11 +610,12 @@ def train_step(model, opt, images, label, reducer=None, control=None):
     stochastic-depth table, its own BatchNorm statistics, as a data-parallel rank would), the gradients are added in
     micro-batch order, then -- with a reducer: one all-reduce round of the accumulated buckets -- the norm of the mean
     gradient, the clip factor and the skip decision are formed and the optimizer steps once.  Returns the mean of the
-    micro-batch losses."""
+    micro-batch losses.
+    `loss` (SodLoss): the loss over the deep-supervision outputs; None is `tramba_loss` (BCE + IoU, train.py:76-85)."""
     if control is not None:
-        return _controlled_step(model, opt, images, label, reducer, control)
+        return _controlled_step(model, opt, images, label, reducer, control, loss)
     outputs = model(images)
-    loss = tramba_loss(outputs, label)
+    loss = _step_loss(loss, outputs, label)
     if reducer is not None:
         reducer.prepare()
     else:
@@ -555,17 +695,19 @@ def _grouped(batches, n):
 
 
 def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_model, method, start_epoch=0,
-        evaluate=None, see=0, best_mae=None, reducer=None, is_main=True, log=None, graph=False, control=None):
+        evaluate=None, see=0, best_mae=None, reducer=None, is_main=True, log=None, graph=False, control=None, loss=None):
     """Epoch loop of train.py:212-263 around `train_step`.  `batches(epoch)` yields (images, label) device tensors;
     `evaluate(model, epoch) -> MAE` runs from epoch `see` on (train.py:237); rank 0 (`is_main`) writes the files.
     `graph=True` (single process, optimizer from `get_opt(..., capturable=True)`): every step is a hipGraph replay
     (tramba_amd.graph.GraphedTrainStep), re-captured by itself when the learning rate steps.
     `control` (StepControl): `control.accumulate` consecutive batches of `batches(epoch)` make one optimizer step; a short
-    last group is a step over the batches it has, as a short last batch is a step today."""
+    last group is a step over the batches it has, as a short last batch is a step today.
+    `loss` (SodLoss): the loss every step uses (None: `tramba_loss`)."""
+    loss_fn = loss
     step_fn = train_step
     if graph:
         from .graph import GraphedTrainStep
-        graphed = GraphedTrainStep(model, opt, reducer=reducer, control=control)
+        graphed = GraphedTrainStep(model, opt, reducer=reducer, control=control, loss=loss_fn)
         step_fn = lambda m_, o_, images, label, reducer=None, **kw: graphed(images, label)  # noqa: E731
     history = []
     for epoch in range(start_epoch, epochs):
@@ -573,9 +715,9 @@ def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_
         total, n = None, 0
         for images, label in (batches(epoch) if control is None else _grouped(batches(epoch), control.accumulate)):
             if control is None:
-                loss = step_fn(model, opt, images, label, reducer=reducer)
+                loss = step_fn(model, opt, images, label, reducer=reducer, loss=loss_fn)
             else:
-                loss = step_fn(model, opt, images, label, reducer=reducer, control=control)
+                loss = step_fn(model, opt, images, label, reducer=reducer, control=control, loss=loss_fn)
             total = loss.clone() if total is None else total + loss     # clone: a graphed step reuses its loss buffer
             n += 1
         mean_loss = float(total / max(n, 1)) if total is not None else float("nan")   # one host sync per epoch
