@@ -27,6 +27,9 @@
  *   tramba_dw_pack              weight re-layout + DWMSMlp fold (h+dw3+dw5+dw7, vmamba.py:624)
  *   tramba_dct_split_cl         DCT2D.forward                   Models/DCT_2D.py:12-29
  *   tramba_linear_cl            Linear2d.forward (1x1 conv)     Models/modules.py:10-13
+ *   tramba_window_attn_cl       WindowAttention.forward + roll / window_partition / window_reverse / shift mask
+ *                                                               Models/encoder/swin_encoder.py:116-147,213-268
+ *   tramba_kv_attn_cl           Attention.forward (after q / kv) Models/encoder/pvtv2_encoder.py:95-116
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
  *   tramba_stem_conv_ln_gelu
  *   tramba_resize_table /       get_transform(S, 'Test'): Resize + ToTensor + Normalize
@@ -649,6 +652,29 @@ int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count,
 int tramba_adam_step_ctl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                          float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
                          double eps, double weight_decay, const float *gscale, const int *skip, void *stream);
+
+/* ------------------------------------------------------------------ fused attention (Tramba-S / -P encoders, inference) */
+/* Both entries: K and V of one (problem, head) are staged whole in LDS (at most 256 keys), scores on MFMA with f32
+ * accumulation, scale = hd^-0.5 applied in f32 to the accumulated score, softmax in f32 with the row max subtracted, P
+ * rounded to dtype only as the operand of P V, P V accumulated in f32, divided by the f32 row sum and rounded once.  No
+ * atomics, fixed summation order (bitwise reproducible), no allocation or synchronisation (capturable).  bf16 / fp16 only,
+ * hd = 32 or 64, tensors 16-byte aligned.  The query rows of one problem are dealt to several workgroups when the
+ * (problem, head) pairs alone do not fill the chip. */
+/* WindowAttention.forward with the cyclic shift, window_partition / window_reverse and the shift mask around it
+ * (Models/encoder/swin_encoder.py:116-147, 213-232, 236-268).  qkv: (B, H, W, 3 C) as the qkv Linear writes it on the
+ * unpermuted token map (channel order [3][heads][hd], C = heads * hd); table: ((2 ws - 1)^2, heads) f32, the module's
+ * relative_position_bias_table; y: (B, H, W, C).  Window (wy, wx), local (i, j) is map position ((wy ws + i + shift) mod H,
+ * (wx ws + j + shift) mod W), read and written there.  Bias index (i_q - i_k + ws - 1)(2 ws - 1) + (j_q - j_k + ws - 1).
+ * shift > 0: rolled-frame rows / columns get a region 0 / 1 / 2 with cuts at H - ws and H - shift (W likewise), pair id
+ * 3 r + c; query / key pairs of different id get -100 added (finite, as the reference).  No (nW, heads, N, N) tensor exists.
+ * ws * ws <= 256, H % ws == 0, W % ws == 0, 0 <= shift < ws. */
+int tramba_window_attn_cl(const void *qkv, const float *table, void *y, int batch, int h, int w, int heads, int hd,
+                          int ws, int shift, int dtype, void *stream);
+/* Attention.forward after its projections (Models/encoder/pvtv2_encoder.py:95-116): q (B, N, C), kv (B, M, 2 C) (channel
+ * order [2][heads][hd]) -> y (B, N, C), all read and written in place through head strides; no bias.  1 <= M <= 256 (any M:
+ * pad keys are kept out of the max, the sum and P), N >= 1. */
+int tramba_kv_attn_cl(const void *q, const void *kv, void *y, int batch, int64_t n, int m, int heads, int hd, int dtype,
+                      void *stream);
 
 #ifdef __cplusplus
 }

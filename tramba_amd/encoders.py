@@ -5,9 +5,13 @@ reference's Models/encoder/{swin_encoder,pvtv2_encoder}.py (so `swin_base_patch4
 Token-major throughout: a (B, H*W, C) token tensor IS a channels-last (B, H, W, C) map, which is what the
 decoder's HIP kernels take -- the reference's reshape/permute/contiguous hand-offs disappear.  In inference the
 LayerNorms, every Linear (bias, GELU and the residual add fused in the GEMM epilogue) and PVT's depth-wise 3x3 run on
-the library's HIP kernels; attention itself is stock `scaled_dot_product_attention` (no new kernels),
-with Swin's relative-position bias and shift mask folded into one cached additive mask per block.  With autograd on
-everything is stock torch ops on the device.
+the library's HIP kernels, and so does attention in 16-bit inference: the qkv / q / kv GEMMs run on the token map as it
+lies and `hip.window_attention_cl` (Swin: cyclic shift, window gather, relative-position bias and shift mask by index
+arithmetic in the kernel) or `hip.kv_attention_cl` (PVT: heads by stride) reads and writes it in place, so a block is
+LayerNorm, GEMM, attention, GEMM (+ residual), LayerNorm, GEMM, GEMM with no framework op between.  fp32 inference,
+shapes the kernels do not take (more than 256 keys, head dims other than 32 / 64) and everything with autograd on keep
+the stock `scaled_dot_product_attention` path (`_forward_stock`), with Swin's bias and mask folded into one cached
+additive mask per block.
 """
 import math
 
@@ -97,6 +101,21 @@ class _PvtAttention(nn.Module):
             self.norm = nn.LayerNorm(dim)
 
     def forward(self, x, h, w, residual=None):
+        b, n, c = x.shape
+        m = (h // self.sr_ratio) * (w // self.sr_ratio) if self.sr_ratio > 1 else n
+        if not (_infer(x, self.q.weight) and hip.kv_attention_supported(x.dtype, m, c, self.num_heads)):
+            return self._forward_stock(x, h, w, residual)
+        q = _lin(self.q, x)
+        if self.sr_ratio > 1:
+            xr = _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
+            xr = _ln(self.norm, xr)
+        else:
+            xr = x
+        o = hip.kv_attention_cl(q, _lin(self.kv, xr), self.num_heads)       # heads by stride: no view / permute copies
+        return _lin(self.proj, o, residual=residual)
+
+    def _forward_stock(self, x, h, w, residual=None):
+        """stock torch attention: fp32, autograd on, or a key count the library does not take (e.g. 576 keys at 768x768)"""
         b, n, c = x.shape
         nh = self.num_heads
         q = _lin(self.q, x).view(b, n, nh, c // nh).transpose(1, 2)
@@ -287,6 +306,20 @@ class SwinTransformerBlock(nn.Module):
         self.register_buffer("attn_mask", mask)
 
     def forward(self, x):
+        h, w = self.input_resolution
+        b, l, c = x.shape
+        ws, sh, attn = self.window_size, self.shift_size, self.attn
+        if self.training or not (_infer(x, attn.qkv.weight)
+                                 and hip.window_attention_supported(x.dtype, h, w, c, attn.num_heads, ws, sh)):
+            return self._forward_stock(x)
+        # qkv and proj are per-token: they run on the map as it lies, and the kernel gathers its windows through the shift
+        qkv = _lin(attn.qkv, _ln(self.norm1, x)).view(b, h, w, 3 * c)
+        y = hip.window_attention_cl(qkv, _f32(attn.relative_position_bias_table), ws, sh, attn.num_heads)
+        x = _lin(attn.proj, y.view(b, l, c), residual=x)
+        return self.mlp(_ln(self.norm2, x), residual=x)
+
+    def _forward_stock(self, x):
+        """stock torch attention on rolled / partitioned copies: training, fp32, or a shape the library does not take"""
         h, w = self.input_resolution
         b, l, c = x.shape
         ws, sh = self.window_size, self.shift_size

@@ -130,6 +130,8 @@ SIGNATURES = {
     "tramba_grad_norm_workspace": (ctypes.c_size_t, [c_vp, c_int]),
     "tramba_grad_norm": (c_int, [c_vp] * 2 + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "tramba_adam_step_ctl": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp] * 3),
+    "tramba_window_attn_cl": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
+    "tramba_kv_attn_cl": (c_int, [c_vp] * 3 + [c_int, c_i64] + [c_int] * 4 + [c_vp]),
 }
 
 _lib = None
@@ -1370,6 +1372,50 @@ def linear_cl(x, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None):
     _check_epilogue("linear_cl", bias, residual, x.dtype, m, n)
     _check(lib().tramba_linear_cl(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), m, n, k, act, dt(x),
                                   dt(y), _stream()), "linear_cl")
+    return y
+
+
+_ATTN_DTYPES = (torch.bfloat16, torch.float16)
+
+
+def window_attention_supported(dtype, h, w, c, heads, ws, shift):
+    """the argument checks of tramba_window_attn_cl, without the library: can the fused window attention take this shape?"""
+    return (dtype in _ATTN_DTYPES and heads > 0 and c % heads == 0 and c // heads in (32, 64) and h > 0 and w > 0
+            and 1 <= ws and ws * ws <= 256 and h % ws == 0 and w % ws == 0 and 0 <= shift < ws)
+
+
+def kv_attention_supported(dtype, m, c, heads):
+    """the argument checks of tramba_kv_attn_cl, without the library"""
+    return dtype in _ATTN_DTYPES and heads > 0 and c % heads == 0 and c // heads in (32, 64) and 1 <= m <= 256
+
+
+def window_attention_cl(qkv, table, ws, shift, heads):
+    """qkv: (B, H, W, 3 C) as the qkv Linear writes it on the unpermuted map; table: ((2 ws - 1)^2, heads) f32 -> (B, H, W, C):
+    shifted-window attention with the relative-position bias and the shift mask computed in the kernel."""
+    _dev(qkv, table)
+    if heads <= 0 or qkv.dim() != 4 or qkv.shape[-1] % (3 * heads):
+        raise TrambaHipError(f"window_attention_cl: qkv must be (B, H, W, 3 * heads * hd), got {tuple(qkv.shape)}")
+    b, h, w, c3 = qkv.shape
+    if table.dtype != torch.float32 or tuple(table.shape) != ((2 * ws - 1) ** 2, heads):
+        raise TrambaHipError(f"window_attention_cl: table must be float32 ({(2 * ws - 1) ** 2}, {heads}), got {table.dtype} "
+                             f"{tuple(table.shape)}")
+    y = torch.empty((b, h, w, c3 // 3), dtype=qkv.dtype, device=qkv.device)
+    _check(lib().tramba_window_attn_cl(_ptr(qkv), _ptr(table), _ptr(y), b, h, w, heads, c3 // (3 * heads), ws, shift, dt(qkv),
+                                       _stream()), "window_attention_cl")
+    return y
+
+
+def kv_attention_cl(q, kv, heads):
+    """q: (B, N, C); kv: (B, M, 2 C) as the kv Linear writes it -> softmax(q k^T / sqrt(hd)) v, (B, N, C); heads by stride."""
+    _dev(q, kv)
+    if heads <= 0 or q.dim() != 3 or kv.dim() != 3 or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 * q.shape[2] or kv.dtype != q.dtype \
+            or q.shape[2] % heads:
+        raise TrambaHipError(f"kv_attention_cl: need q (B, N, C) and kv (B, M, 2 C) of one dtype, got {tuple(q.shape)} "
+                             f"{tuple(kv.shape)}")
+    b, n, c = q.shape
+    y = torch.empty_like(q)
+    _check(lib().tramba_kv_attn_cl(_ptr(q), _ptr(kv), _ptr(y), b, n, kv.shape[1], heads, c // heads, dt(q), _stream()),
+           "kv_attention_cl")
     return y
 
 
