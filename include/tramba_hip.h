@@ -30,6 +30,8 @@
  *   tramba_window_attn_cl       WindowAttention.forward + roll / window_partition / window_reverse / shift mask
  *                                                               Models/encoder/swin_encoder.py:116-147,213-268
  *   tramba_kv_attn_cl           Attention.forward (after q / kv) Models/encoder/pvtv2_encoder.py:95-116
+ *   tramba_window_attn_bwd_cl / the gradients of the two above (autograd of the same reference lines), softmax rows
+ *   tramba_kv_attn_bwd_cl       recomputed from q and k, nothing saved by the forward
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
  *   tramba_stem_conv_ln_gelu
  *   tramba_resize_table /       get_transform(S, 'Test'): Resize + ToTensor + Normalize
@@ -675,6 +677,36 @@ int tramba_window_attn_cl(const void *qkv, const float *table, void *y, int batc
  * pad keys are kept out of the max, the sum and P), N >= 1. */
 int tramba_kv_attn_cl(const void *q, const void *kv, void *y, int batch, int64_t n, int m, int heads, int hd, int dtype,
                       void *stream);
+
+/* ------------------------------------------------------------------ attention backward (Tramba-S / -P encoders, training) */
+/* Both forms, with S = hd^-0.5 Q K^T (+ bias + mask), P = softmax(S), dO the incoming gradient:
+ *   dP = dO V^T,  D_q = sum_k P_qk dP_qk,  dS = P o (dP - D),  dV = P^T dO,  dQ = hd^-0.5 dS K,  dK = hd^-0.5 dS^T Q.
+ * Nothing is saved by the forward: the row max and row sum are recomputed from q and k (at most 256 keys, K and V whole in
+ * LDS).  Every product runs on MFMA with f32 accumulation; S, P, dP, D and dS stay in f32; hd^-0.5 multiplies accumulated
+ * f32 values; 16-bit roundings happen only where P (for dV) and dS (for dQ / dK) become MFMA operands -- each as the pair
+ * hi = round(x), lo = round(x - hi), two MFMAs, so that the products keep the f32 value -- and once at each output store.  No atomics and a fixed summation order (bitwise reproducible); no allocation or synchronisation
+ * (capturable).  The caller allocates the workspace; its size is a pure function of the shape (tramba_*_attn_bwd_work,
+ * 0 for a shape the entry refuses) and the entry checks what it is given against what it will use.  Arguments are
+ * checked as by the forward entries; bf16 / fp16, hd 32 / 64, tensors 16-byte aligned. */
+/* Backward of tramba_window_attn_cl, i.e. of WindowAttention.forward with the cyclic shift, window_partition /
+ * window_reverse and the shift mask around it (Models/encoder/swin_encoder.py:116-147, 213-232, 236-268).  qkv, table
+ * as the forward's; dy: (B, H, W, C); dqkv: (B, H, W, 3 C), written completely (every token lies in exactly one window:
+ * no zero-fill, no accumulation), through the forward's shift arithmetic.  dtable: ((2 ws - 1)^2, heads) f32,
+ * dtable[e, head] = sum of the f32 dS over batch, windows and the (q, k) pairs of relative index e: per-window sums in
+ * query order, then windows in index order by a second launch.  dtable == NULL skips the table gradient and needs no
+ * workspace (a frozen encoder). */
+size_t tramba_window_attn_bwd_work(int batch, int h, int w, int heads, int hd, int ws);
+int tramba_window_attn_bwd_cl(const void *qkv, const float *table, const void *dy, void *dqkv, float *dtable, void *work,
+                              size_t work_bytes, int batch, int h, int w, int heads, int hd, int ws, int shift, int dtype,
+                              void *stream);
+/* Backward of tramba_kv_attn_cl, i.e. of Attention.forward after its projections (Models/encoder/pvtv2_encoder.py:95-116):
+ * q (B, N, C), kv (B, M, 2 C), dy (B, N, C) -> dq (B, N, C), dkv (B, M, 2 C), read and written through head strides.  The N
+ * queries of a (batch, head) are dealt to about 256 / heads workgroups in runs of 64-query rounds (32 above 160 keys); each writes f32 dK /
+ * dV partials to the workspace and a second launch adds them in run order, scales dK and rounds once.  Rows of kv / dkv
+ * beyond M are neither read nor written. */
+size_t tramba_kv_attn_bwd_work(int batch, int64_t n, int m, int heads, int hd);
+int tramba_kv_attn_bwd_cl(const void *q, const void *kv, const void *dy, void *dq, void *dkv, void *work, size_t work_bytes,
+                          int batch, int64_t n, int m, int heads, int hd, int dtype, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,9 +9,16 @@ the library's HIP kernels, and so does attention in 16-bit inference: the qkv / 
 lies and `hip.window_attention_cl` (Swin: cyclic shift, window gather, relative-position bias and shift mask by index
 arithmetic in the kernel) or `hip.kv_attention_cl` (PVT: heads by stride) reads and writes it in place, so a block is
 LayerNorm, GEMM, attention, GEMM (+ residual), LayerNorm, GEMM, GEMM with no framework op between.  fp32 inference,
-shapes the kernels do not take (more than 256 keys, head dims other than 32 / 64) and everything with autograd on keep
-the stock `scaled_dot_product_attention` path (`_forward_stock`), with Swin's bias and mask folded into one cached
-additive mask per block.
+shapes the kernels do not take (more than 256 keys, head dims other than 32 / 64) and, by default, everything with
+autograd on keep the stock `scaled_dot_product_attention` path (`_forward_stock`), with Swin's bias and mask folded into
+one cached additive mask per block.
+
+Training on the library's attention is opt-in: `set_fused_attention_training(model)` (or `build(name, args)` with
+`args.fused_attention_training`) puts every Swin / PVT block whose activations are 16-bit and whose shape the kernels
+take on `_WindowAttnFn` / `_KvAttnFn` whenever autograd is needed.  Their forward is the inference entry, they save
+only their inputs, and their backward (`hip.window_attention_bwd_cl` / `hip.kv_attention_bwd_cl`) recomputes the softmax
+rows: no roll, window partition, mask or bias tensor exists on that path, and the fp32 relative-position table receives
+its f32 gradient from the kernel.  The Linears and LayerNorms around the attention stay on the stock autograd ops.
 """
 import math
 
@@ -37,6 +44,56 @@ def _ln(m: nn.LayerNorm, x):
     if _infer(x, m.weight):
         return hip.layernorm_cl(x.contiguous(), _f32(m.weight), _f32(m.bias), m.eps)
     return F.layer_norm(x.float(), m.normalized_shape, m.weight.float(), m.bias.float(), m.eps).to(x.dtype)
+
+
+class _WindowAttnFn(torch.autograd.Function):
+    """hip.window_attention_cl with its backward on the library: saves (qkv, table), nothing of the softmax."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, ws, shift, heads):
+        qkv, table = qkv.contiguous(), table.contiguous()
+        ctx.save_for_backward(qkv, table)
+        ctx.geom = (ws, shift, heads)
+        return hip.window_attention_cl(qkv, table, ws, shift, heads)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        qkv, table = ctx.saved_tensors
+        ws, shift, heads = ctx.geom
+        dqkv, dtable = hip.window_attention_bwd_cl(qkv, table, dy.contiguous(), ws, shift, heads,
+                                                   need_table=ctx.needs_input_grad[1])
+        return dqkv, dtable, None, None, None
+
+
+class _KvAttnFn(torch.autograd.Function):
+    """hip.kv_attention_cl with its backward on the library: saves (q, kv)."""
+
+    @staticmethod
+    def forward(ctx, q, kv, heads):
+        q, kv = q.contiguous(), kv.contiguous()
+        ctx.save_for_backward(q, kv)
+        ctx.heads = heads
+        return hip.kv_attention_cl(q, kv, heads)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        q, kv = ctx.saved_tensors
+        dq, dkv = hip.kv_attention_bwd_cl(q, kv, dy.contiguous(), ctx.heads)
+        return dq, dkv, None
+
+
+def set_fused_attention_training(model, enabled=True):
+    """Put the Swin / PVT blocks of `model` on the library's attention backward in 16-bit training (off by default).
+    Returns the number of blocks switched.  A block still keeps the stock path for fp32 activations, for shapes the
+    kernels do not take and when no autograd graph is needed."""
+    count = 0
+    for m in model.modules():
+        if isinstance(m, (SwinTransformerBlock, _PvtAttention)):
+            m.fused_attention_training = bool(enabled)
+            count += 1
+    return count
 
 
 def _conv(m: nn.Conv2d, x):
@@ -88,6 +145,8 @@ class _PvtMlp(nn.Module):
 class _PvtAttention(nn.Module):
     """pvtv2_encoder.py:57-116: spatial-reduction attention (keys / values from an sr x sr strided conv of the map)."""
 
+    fused_attention_training = False       # set_fused_attention_training(); no parameter, not in the state_dict
+
     def __init__(self, dim, num_heads, qkv_bias, sr_ratio):
         super().__init__()
         assert dim % num_heads == 0
@@ -103,7 +162,10 @@ class _PvtAttention(nn.Module):
     def forward(self, x, h, w, residual=None):
         b, n, c = x.shape
         m = (h // self.sr_ratio) * (w // self.sr_ratio) if self.sr_ratio > 1 else n
-        if not (_infer(x, self.q.weight) and hip.kv_attention_supported(x.dtype, m, c, self.num_heads)):
+        infer = _infer(x, self.q.weight)
+        train = (self.fused_attention_training and not infer
+                 and hip.kv_attention_train_supported(x.dtype, m, c, self.num_heads))
+        if not train and not (infer and hip.kv_attention_supported(x.dtype, m, c, self.num_heads)):
             return self._forward_stock(x, h, w, residual)
         q = _lin(self.q, x)
         if self.sr_ratio > 1:
@@ -111,7 +173,10 @@ class _PvtAttention(nn.Module):
             xr = _ln(self.norm, xr)
         else:
             xr = x
-        o = hip.kv_attention_cl(q, _lin(self.kv, xr), self.num_heads)       # heads by stride: no view / permute copies
+        if train:
+            o = _KvAttnFn.apply(q, _lin(self.kv, xr), self.num_heads)
+        else:
+            o = hip.kv_attention_cl(q, _lin(self.kv, xr), self.num_heads)   # heads by stride: no view / permute copies
         return _lin(self.proj, o, residual=residual)
 
     def _forward_stock(self, x, h, w, residual=None):
@@ -280,6 +345,7 @@ class _SwinMlp(nn.Module):
 
 class SwinTransformerBlock(nn.Module):
     """swin_encoder.py:166-273."""
+    fused_attention_training = False       # set_fused_attention_training(); no parameter, not in the state_dict
 
     def __init__(self, dim, input_resolution, num_heads, window_size, shift_size, mlp_ratio, drop_path):
         super().__init__()
@@ -309,6 +375,9 @@ class SwinTransformerBlock(nn.Module):
         h, w = self.input_resolution
         b, l, c = x.shape
         ws, sh, attn = self.window_size, self.shift_size, self.attn
+        if (self.fused_attention_training and not _infer(x, attn.qkv.weight, attn.relative_position_bias_table)
+                and hip.window_attention_train_supported(x.dtype, h, w, c, attn.num_heads, ws, sh)):
+            return self._forward_fused_train(x)
         if self.training or not (_infer(x, attn.qkv.weight)
                                  and hip.window_attention_supported(x.dtype, h, w, c, attn.num_heads, ws, sh)):
             return self._forward_stock(x)
@@ -317,6 +386,22 @@ class SwinTransformerBlock(nn.Module):
         y = hip.window_attention_cl(qkv, _f32(attn.relative_position_bias_table), ws, sh, attn.num_heads)
         x = _lin(attn.proj, y.view(b, l, c), residual=x)
         return self.mlp(_ln(self.norm2, x), residual=x)
+
+    def _forward_fused_train(self, x):
+        """autograd on, 16-bit: the library's attention forward and backward on the unpermuted map (no roll, partition,
+        mask or bias tensor); proj, drop_path and the residuals as in `_forward_stock`"""
+        h, w = self.input_resolution
+        b, l, c = x.shape
+        attn = self.attn
+        qkv = _lin(attn.qkv, _ln(self.norm1, x)).view(b, h, w, 3 * c)
+        y = _WindowAttnFn.apply(qkv, attn.relative_position_bias_table.float(), self.window_size, self.shift_size,
+                                attn.num_heads)
+        y = _lin(attn.proj, y.view(b, l, c))
+        if not self.training:
+            x = x + y
+            return self.mlp(_ln(self.norm2, x), residual=x)
+        x = x + self.drop_path(y)
+        return x + self.drop_path(self.mlp(_ln(self.norm2, x)))
 
     def _forward_stock(self, x):
         """stock torch attention on rolled / partitioned copies: training, fp32, or a shape the library does not take"""

@@ -132,6 +132,10 @@ SIGNATURES = {
     "tramba_adam_step_ctl": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp] * 3),
     "tramba_window_attn_cl": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "tramba_kv_attn_cl": (c_int, [c_vp] * 3 + [c_int, c_i64] + [c_int] * 4 + [c_vp]),
+    "tramba_window_attn_bwd_work": (ctypes.c_size_t, [c_int] * 6),
+    "tramba_window_attn_bwd_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
+    "tramba_kv_attn_bwd_work": (ctypes.c_size_t, [c_int, c_i64, c_int, c_int, c_int]),
+    "tramba_kv_attn_bwd_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t, c_int, c_i64] + [c_int] * 4 + [c_vp]),
 }
 
 _lib = None
@@ -1417,6 +1421,70 @@ def kv_attention_cl(q, kv, heads):
     _check(lib().tramba_kv_attn_cl(_ptr(q), _ptr(kv), _ptr(y), b, n, kv.shape[1], heads, c // heads, dt(q), _stream()),
            "kv_attention_cl")
     return y
+
+
+def window_attention_train_supported(dtype, h, w, c, heads, ws, shift):
+    """can window_attention_bwd_cl take this shape?  The backward covers the forward's whole shape domain."""
+    return window_attention_supported(dtype, h, w, c, heads, ws, shift)
+
+
+def kv_attention_train_supported(dtype, m, c, heads):
+    """can kv_attention_bwd_cl take this shape?  The backward covers the forward's whole shape domain."""
+    return kv_attention_supported(dtype, m, c, heads)
+
+
+def _attn_out(name, what, out, shape, dtype, device):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    _dev(out)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype:
+        raise TrambaHipError(f"{name}: {what} must be {dtype} {tuple(shape)}, got {out.dtype} {tuple(out.shape)}")
+    return out
+
+
+def window_attention_bwd_cl(qkv, table, dy, ws, shift, heads, need_table=True, out=None):
+    """Backward of window_attention_cl from its inputs alone (the softmax rows are recomputed): qkv (B, H, W, 3 C), table
+    ((2 ws - 1)^2, heads) f32, dy (B, H, W, C) -> (dqkv (B, H, W, 3 C), dtable f32 or None).  out: (dqkv, dtable) tensors to
+    write into (dtable may be None); every element of both is written."""
+    _dev(qkv, table, dy)
+    if heads <= 0 or qkv.dim() != 4 or qkv.shape[-1] % (3 * heads):
+        raise TrambaHipError(f"window_attention_bwd_cl: qkv must be (B, H, W, 3 * heads * hd), got {tuple(qkv.shape)}")
+    b, h, w, c3 = qkv.shape
+    if table.dtype != torch.float32 or tuple(table.shape) != ((2 * ws - 1) ** 2, heads):
+        raise TrambaHipError(f"window_attention_bwd_cl: table must be float32 ({(2 * ws - 1) ** 2}, {heads}), got "
+                             f"{table.dtype} {tuple(table.shape)}")
+    if dy.dtype != qkv.dtype or tuple(dy.shape) != (b, h, w, c3 // 3):
+        raise TrambaHipError(f"window_attention_bwd_cl: dy must be {qkv.dtype} {(b, h, w, c3 // 3)}, got {dy.dtype} "
+                             f"{tuple(dy.shape)}")
+    o_qkv, o_table = out if out is not None else (None, None)
+    dqkv = _attn_out("window_attention_bwd_cl", "dqkv", o_qkv, qkv.shape, qkv.dtype, qkv.device)
+    dtable = _attn_out("window_attention_bwd_cl", "dtable", o_table, table.shape, torch.float32, qkv.device) if need_table else None
+    hd = c3 // (3 * heads)
+    nbytes = lib().tramba_window_attn_bwd_work(b, h, w, heads, hd, ws) if need_table else 0
+    work = torch.empty(nbytes, dtype=torch.uint8, device=qkv.device) if nbytes else None
+    _check(lib().tramba_window_attn_bwd_cl(_ptr(qkv), _ptr(table), _ptr(dy), _ptr(dqkv), _ptr(dtable), _ptr(work), nbytes, b, h,
+                                           w, heads, hd, ws, shift, dt(qkv), _stream()), "window_attention_bwd_cl")
+    return dqkv, dtable
+
+
+def kv_attention_bwd_cl(q, kv, dy, heads, out=None):
+    """Backward of kv_attention_cl from its inputs alone: q (B, N, C), kv (B, M, 2 C), dy (B, N, C) -> (dq, dkv).  out: (dq,
+    dkv) tensors to write into."""
+    _dev(q, kv, dy)
+    if heads <= 0 or q.dim() != 3 or kv.dim() != 3 or kv.shape[0] != q.shape[0] or kv.shape[2] != 2 * q.shape[2] or kv.dtype != q.dtype \
+            or q.shape[2] % heads or dy.shape != q.shape or dy.dtype != q.dtype:
+        raise TrambaHipError(f"kv_attention_bwd_cl: need q, dy (B, N, C) and kv (B, M, 2 C) of one dtype, got {tuple(q.shape)} "
+                             f"{tuple(dy.shape)} {tuple(kv.shape)}")
+    b, n, c = q.shape
+    m = kv.shape[1]
+    o_q, o_kv = out if out is not None else (None, None)
+    dq = _attn_out("kv_attention_bwd_cl", "dq", o_q, q.shape, q.dtype, q.device)
+    dkv = _attn_out("kv_attention_bwd_cl", "dkv", o_kv, kv.shape, q.dtype, q.device)
+    nbytes = lib().tramba_kv_attn_bwd_work(b, n, m, heads, c // heads)
+    work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=q.device)
+    _check(lib().tramba_kv_attn_bwd_cl(_ptr(q), _ptr(kv), _ptr(dy), _ptr(dq), _ptr(dkv), _ptr(work), nbytes, b, n, m, heads,
+                                       c // heads, dt(q), _stream()), "kv_attention_bwd_cl")
+    return dq, dkv
 
 
 def linear_dual_ok(x, w):

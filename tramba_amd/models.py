@@ -430,7 +430,11 @@ def build(model_name, args):
         return bulid_model(deep_supervision=True, use_pretrain=bool(path), img_size=args.img_size, dims=128,
                            depths=[2, 2, 2, 2], pretrained_path=path)
     if model_name in ("Tramba-S-TSOD", "Tramba-P-TSOD", "Tramba-R-TSOD", "Tramba-S-SOD", "Tramba-P-SOD", "Tramba-R-SOD"):
-        return bulid_model_enc(enc_type=model_name, deep_supervision=True, img_size=args.img_size)
+        model = bulid_model_enc(enc_type=model_name, deep_supervision=True, img_size=args.img_size)
+        if getattr(args, "fused_attention_training", False):      # opt-in: attention backward on the library
+            from .encoders import set_fused_attention_training
+            set_fused_attention_training(model)
+        return model
     if model_name == "BaseUMamba-SOD":
         raise NotImplementedError("BaseUMamba-SOD is the reference's ablation baseline (out of scope, SURVEY 2 #10)")
     return None
