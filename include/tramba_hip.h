@@ -32,6 +32,9 @@
  *   tramba_kv_attn_cl           Attention.forward (after q / kv) Models/encoder/pvtv2_encoder.py:95-116
  *   tramba_window_attn_bwd_cl / the gradients of the two above (autograd of the same reference lines), softmax rows
  *   tramba_kv_attn_bwd_cl       recomputed from q and k, nothing saved by the forward
+ *   tramba_patch_conv_cl        Attention.sr (kernel = stride)  Models/encoder/pvtv2_encoder.py:76-78,103-106
+ *   tramba_patch_embed_ln       OverlapPatchEmbed (stage 1) / PatchEmbed + their LayerNorm
+ *                                                               Models/encoder/pvtv2_encoder.py:159-199, swin_encoder.py:413-450
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
  *   tramba_stem_conv_ln_gelu
  *   tramba_resize_table /       get_transform(S, 'Test'): Resize + ToTensor + Normalize
@@ -707,6 +710,26 @@ int tramba_window_attn_bwd_cl(const void *qkv, const float *table, const void *d
 size_t tramba_kv_attn_bwd_work(int batch, int64_t n, int m, int heads, int hd);
 int tramba_kv_attn_bwd_cl(const void *q, const void *kv, const void *dy, void *dq, void *dkv, void *work, size_t work_bytes,
                           int batch, int64_t n, int m, int heads, int hd, int dtype, void *stream);
+
+/* ------------------------------------------------------------------ dense convs of the Swin-B / PVTv2-b4 encoders (inference) */
+/* Kernel = stride = r convolution on a channels-last map: the spatial-reduction conv `sr` of Attention.forward
+ * (Models/encoder/pvtv2_encoder.py:76-78,103-106, with the permute / reshape around it).  x (B, Hin, Win, Cin) ->
+ * y (B, Hin / r, Win / r, Cout), floor: trailing rows and columns of a map whose side is no multiple of r are never read.
+ * w is K-major (Cout, r, r, Cin) = reference weight.permute(0,2,3,1), same dtype as x; bias (Cout) f32 or NULL.
+ * bf16 / fp16, 2 <= r <= 8, Cin % 64 == 0, Cout % 8 == 0, tensors 16-byte aligned, the input map below 2^31 bytes.
+ * f32 accumulation on the matrix cores with K split between the waves of a workgroup, the partial sums added in wave
+ * order, one rounding; no atomics, no workspace, no allocation or synchronisation (capturable, bitwise reproducible). */
+int tramba_patch_conv_cl(const void *x, const void *w, const float *bias, void *y, int batch, int hin, int win, int cin,
+                         int cout, int r, int dtype, void *stream);
+/* First-layer patch embedding fused with its LayerNorm: OverlapPatchEmbed.forward of patch_embed1
+ * (Models/encoder/pvtv2_encoder.py:159-199; k 7 / stride 4 / pad 3, Cout 64) and PatchEmbed.forward
+ * (Models/encoder/swin_encoder.py:413-450; k 4 / stride 4 / pad 0, Cout 128); any other form is refused.
+ * img (B, 3, H, W) NCHW in f32 or `dtype`; w (Cout, 3, k, k) f32 reference layout; bias, ln_w, ln_b (Cout) f32;
+ * y (B, Ho, Wo, Cout) bf16 / fp16, Ho = (H + 2 pad - k) / stride + 1 (floor).  Convolution, bias and LayerNorm in f32,
+ * one rounding at the store (the reference rounds the convolution before the LayerNorm). */
+int tramba_patch_embed_ln(const void *img, const float *w, const float *bias, const float *ln_w, const float *ln_b,
+                          void *y, int batch, int h, int wd, int k, int stride, int pad, int cout, float eps,
+                          int img_dtype, int dtype, void *stream);
 
 #ifdef __cplusplus
 }

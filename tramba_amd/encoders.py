@@ -19,6 +19,12 @@ take on `_WindowAttnFn` / `_KvAttnFn` whenever autograd is needed.  Their forwar
 only their inputs, and their backward (`hip.window_attention_bwd_cl` / `hip.kv_attention_bwd_cl`) recomputes the softmax
 rows: no roll, window partition, mask or bias tensor exists on that path, and the fp32 relative-position table receives
 its f32 gradient from the kernel.  The Linears and LayerNorms around the attention stay on the stock autograd ops.
+
+The dense convolutions (PVT's patch embeddings and spatial-reduction convs, Swin's patch embedding) run on `F.conv2d`
+unless `set_library_convolutions(model)` (or `build(name, args)` with `args.library_convolutions`) puts them on the
+library in 16-bit inference: `hip.patch_embed_ln` reads the NCHW image and writes LayerNorm-ed tokens,
+`hip.conv3x3s2_cl` and `hip.patch_conv_cl` read the channels-last token map as it lies.  With the switch on, a Tramba-P
+forward calls no framework convolution and is bitwise reproducible.
 """
 import math
 
@@ -96,6 +102,49 @@ def set_fused_attention_training(model, enabled=True):
     return count
 
 
+def set_library_convolutions(model, enabled=True):
+    """Put the dense convolutions of the Swin / PVT encoder of `model` on the library in 16-bit inference (off by default):
+    PVT's spatial-reduction convs (`hip.patch_conv_cl`), its patch embeddings (`hip.patch_embed_ln` on the image,
+    `hip.conv3x3s2_cl` on the channels-last maps) and Swin's patch embedding (`hip.patch_embed_ln`).  Returns the number of
+    modules switched.  A module still calls `_conv` for fp32 activations, with autograd on and for shapes the kernels do
+    not take."""
+    count = 0
+    for m in model.modules():
+        if isinstance(m, (_OverlapPatchEmbed, _SwinPatchEmbed)) or (isinstance(m, _PvtAttention) and m.sr_ratio > 1):
+            m.library_convolutions = bool(enabled)
+            count += 1
+    return count
+
+
+def _lowp_infer(x, *params):
+    """16-bit activations and no autograd graph: what every library convolution needs"""
+    return x.dtype in (torch.bfloat16, torch.float16) and _infer(x, *params)
+
+
+def _conv_params(m: nn.Conv2d, dtype, kmajor):
+    """(weight, bias) of a conv as the library reads them, derived from the module's own (after prepare_inference: rounded)
+    tensors so that both paths multiply the same numbers: the weight K-major (Cout, kh, kw, Cin) in `dtype`, or in the
+    reference layout in f32; the bias in f32."""
+    def make():
+        w = m.weight.detach()
+        w = w.to(dtype).permute(0, 2, 3, 1).contiguous() if kmajor else w.float().contiguous()
+        return w, None if m.bias is None else m.bias.detach().float().contiguous()
+    return _cache(m).get(("libconv", dtype, kmajor), (m.weight, m.bias), make)
+
+
+def _patch_embed_ln(proj: nn.Conv2d, norm: nn.LayerNorm, x):
+    w, b = _conv_params(proj, x.dtype, kmajor=False)
+    return hip.patch_embed_ln(x.contiguous(), w, b, _f32(norm.weight), _f32(norm.bias), norm.eps, proj.stride[0],
+                              proj.padding[0], x.dtype)
+
+
+def _patch_embed_ln_ok(proj: nn.Conv2d, norm: nn.LayerNorm, x):
+    return (_lowp_infer(x, proj.weight, norm.weight) and proj.bias is not None and proj.in_channels == 3
+            and proj.kernel_size[0] == proj.kernel_size[1] and proj.stride[0] == proj.stride[1]
+            and proj.padding[0] == proj.padding[1] and tuple(norm.normalized_shape) == (proj.out_channels,)
+            and hip.patch_embed_ln_supported(x.dtype, proj.kernel_size[0], proj.stride[0], proj.padding[0], proj.out_channels))
+
+
 def _conv(m: nn.Conv2d, x):
     return F.conv2d(x, m.weight.to(x.dtype), None if m.bias is None else m.bias.to(x.dtype), m.stride, m.padding, 1, m.groups)
 
@@ -146,6 +195,7 @@ class _PvtAttention(nn.Module):
     """pvtv2_encoder.py:57-116: spatial-reduction attention (keys / values from an sr x sr strided conv of the map)."""
 
     fused_attention_training = False       # set_fused_attention_training(); no parameter, not in the state_dict
+    library_convolutions = False           # set_library_convolutions(); likewise
 
     def __init__(self, dim, num_heads, qkv_bias, sr_ratio):
         super().__init__()
@@ -169,8 +219,7 @@ class _PvtAttention(nn.Module):
             return self._forward_stock(x, h, w, residual)
         q = _lin(self.q, x)
         if self.sr_ratio > 1:
-            xr = _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
-            xr = _ln(self.norm, xr)
+            xr = _ln(self.norm, self._reduce(x, h, w))
         else:
             xr = x
         if train:
@@ -178,6 +227,15 @@ class _PvtAttention(nn.Module):
         else:
             o = hip.kv_attention_cl(q, _lin(self.kv, xr), self.num_heads)   # heads by stride: no view / permute copies
         return _lin(self.proj, o, residual=residual)
+
+    def _reduce(self, x, h, w):
+        """the sr x sr / stride sr conv of the token map -> (B, M, C) tokens"""
+        b, n, c = x.shape
+        if (self.library_convolutions and _lowp_infer(x, self.sr.weight)
+                and hip.patch_conv_supported(x.dtype, c, c, self.sr_ratio)):
+            wk, bias = _conv_params(self.sr, x.dtype, kmajor=True)    # kernel = stride: a patch GEMM on the map as it lies
+            return hip.patch_conv_cl(x.contiguous().view(b, h, w, c), wk, bias).view(b, -1, c)
+        return _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
 
     def _forward_stock(self, x, h, w, residual=None):
         """stock torch attention: fp32, autograd on, or a key count the library does not take (e.g. 576 keys at 768x768)"""
@@ -221,8 +279,25 @@ class _OverlapPatchEmbed(nn.Module):
         self.proj = nn.Conv2d(cin, dim, kernel_size=patch, stride=stride, padding=patch // 2)
         self.norm = nn.LayerNorm(dim)
 
-    def forward(self, x):
-        x = _conv(self.proj, x)
+    library_convolutions = False           # set_library_convolutions(); no parameter, not in the state_dict
+
+    def forward(self, x, channels_last=False):
+        """x: the NCHW image or map; channels_last: x is the previous stage's (B, H, W, C) map instead"""
+        proj = self.proj
+        if self.library_convolutions:
+            if not channels_last and _patch_embed_ln_ok(proj, self.norm, x):
+                y = _patch_embed_ln(proj, self.norm, x)                 # conv + bias + LayerNorm, one rounding
+                b, h, w, c = y.shape
+                return y.view(b, h * w, c), h, w
+            if (channels_last and _lowp_infer(x, proj.weight) and proj.kernel_size == (3, 3) and proj.stride == (2, 2)
+                    and proj.padding == (1, 1) and proj.in_channels % 64 == 0 and proj.out_channels % 8 == 0):
+                wk, bias = _conv_params(proj, x.dtype, kmajor=True)
+                y = hip.conv3x3s2_cl(x.contiguous(), wk.view(proj.out_channels, -1), bias)
+                b, h, w, c = y.shape
+                return _ln(self.norm, y.view(b, h * w, c)), h, w
+        if channels_last:
+            x = x.permute(0, 3, 1, 2)                                   # the strided conv reads NCHW (a view)
+        x = _conv(proj, x)
         h, w = x.shape[-2:]
         return _ln(self.norm, x.flatten(2).transpose(1, 2)), h, w
 
@@ -261,13 +336,12 @@ class PyramidVisionTransformerImpr(nn.Module):
         outs = []
         b = x.shape[0]
         for s in range(1, 5):
-            x, h, w = getattr(self, f"patch_embed{s}")(x)
+            x, h, w = getattr(self, f"patch_embed{s}")(x, channels_last=s > 1)
             for blk in getattr(self, f"block{s}"):
                 x = blk(x, h, w)
             x = _ln(getattr(self, f"norm{s}"), x)
             outs.append(x.view(b, h, w, -1))
-            if s < 4:
-                x = outs[-1].permute(0, 3, 1, 2)                        # the next strided conv reads NCHW (a view)
+            x = outs[-1]
         return outs
 
     def forward(self, x):
@@ -466,9 +540,13 @@ class _SwinPatchEmbed(nn.Module):
         self.proj = nn.Conv2d(cin, dim, kernel_size=patch, stride=patch)
         self.norm = nn.LayerNorm(dim)
 
+    library_convolutions = False           # set_library_convolutions(); no parameter, not in the state_dict
+
     def forward(self, x):
         if tuple(x.shape[-2:]) != self.img_size:
             raise RuntimeError(f"Input image size {tuple(x.shape[-2:])} doesn't match model {self.img_size}")
+        if self.library_convolutions and _patch_embed_ln_ok(self.proj, self.norm, x):
+            return _patch_embed_ln(self.proj, self.norm, x).flatten(1, 2)
         return _ln(self.norm, _conv(self.proj, x).flatten(2).transpose(1, 2))
 
 

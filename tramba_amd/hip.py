@@ -136,6 +136,8 @@ SIGNATURES = {
     "tramba_window_attn_bwd_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
     "tramba_kv_attn_bwd_work": (ctypes.c_size_t, [c_int, c_i64, c_int, c_int, c_int]),
     "tramba_kv_attn_bwd_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t, c_int, c_i64] + [c_int] * 4 + [c_vp]),
+    "tramba_patch_conv_cl": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
+    "tramba_patch_embed_ln": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_f, c_int, c_int, c_vp]),
 }
 
 _lib = None
@@ -1800,4 +1802,59 @@ def stem_conv_ln_gelu(img, w, bias, ln_w, ln_b, eps, out_dtype):
     y = torch.empty((bb, (h + 1) // 2, (wd + 1) // 2, 64), dtype=out_dtype, device=img.device)
     _check(lib().tramba_stem_conv_ln_gelu(_ptr(img), _ptr(w), _ptr(bias), _ptr(ln_w), _ptr(ln_b), _ptr(y), bb, h, wd,
                                           eps, _DT[img.dtype], _DT[out_dtype], _stream()), "stem_conv_ln_gelu")
+    return y
+
+
+_PATCH_EMBED_FORMS = ((7, 4, 3, 64), (4, 4, 0, 128))        # PVT patch_embed1, Swin patch_embed
+
+
+def patch_conv_supported(dtype, cin, cout, r):
+    """the argument checks of tramba_patch_conv_cl that depend on the layer, without the library"""
+    return dtype in _ATTN_DTYPES and 2 <= r <= 8 and cin > 0 and cin % 64 == 0 and cout > 0 and cout % 8 == 0
+
+
+def patch_conv_cl(x, w_kmajor, bias):
+    """x: (B, H, W, Cin) bf16/f16; w_kmajor: (Cout, r, r, Cin) = weight.permute(0,2,3,1), same dtype; bias (Cout) f32 or None
+    -> (B, H // r, W // r, Cout): the kernel = stride = r convolution.  Trailing rows / columns beyond r * (H // r) are not
+    read."""
+    _dev(x, w_kmajor, bias)
+    if x.dim() != 4 or w_kmajor.dim() != 4 or w_kmajor.dtype != x.dtype or w_kmajor.shape[1] != w_kmajor.shape[2] \
+            or w_kmajor.shape[3] != x.shape[3]:
+        raise TrambaHipError(f"patch_conv_cl: need x (B, H, W, Cin) and w (Cout, r, r, Cin) of one dtype, got {tuple(x.shape)} "
+                             f"{x.dtype} {tuple(w_kmajor.shape)} {w_kmajor.dtype}")
+    bb, h, wd, cin = x.shape
+    cout, r = w_kmajor.shape[0], w_kmajor.shape[1]
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (cout,)):
+        raise TrambaHipError(f"patch_conv_cl: bias must be float32 ({cout},)")
+    if (bb * h * wd * cin * 2) >= 2 ** 31:
+        raise TrambaHipError("patch_conv_cl: input map beyond 32-bit byte offsets")
+    y = torch.empty((bb, h // max(r, 1), wd // max(r, 1), cout), dtype=x.dtype, device=x.device)
+    _check(lib().tramba_patch_conv_cl(_ptr(x), _ptr(w_kmajor), _ptr(bias), _ptr(y), bb, h, wd, cin, cout, r, dt(x), _stream()),
+           "patch_conv_cl")
+    return y
+
+
+def patch_embed_ln_supported(out_dtype, k, stride, pad, cout):
+    """the argument checks of tramba_patch_embed_ln that depend on the layer, without the library"""
+    return out_dtype in _ATTN_DTYPES and (k, stride, pad, cout) in _PATCH_EMBED_FORMS
+
+
+def patch_embed_ln(img, w, bias, ln_w, ln_b, eps, stride, pad, out_dtype):
+    """img: (B, 3, H, W) NCHW f32 or out_dtype; w: (Cout, 3, k, k) f32; bias, ln_w, ln_b: (Cout) f32 -> LayerNorm(conv(img) +
+    bias) as (B, Ho, Wo, Cout) out_dtype, Ho = (H + 2 pad - k) // stride + 1.  PVT's (k 7, stride 4, pad 3, Cout 64) and Swin's
+    (4, 4, 0, 128) forms only."""
+    _dev(img, w, bias, ln_w, ln_b)
+    if img.dim() != 4 or img.shape[1] != 3 or w.dim() != 4 or w.shape[1] != 3 or w.shape[2] != w.shape[3]:
+        raise TrambaHipError(f"patch_embed_ln: need img (B, 3, H, W) and w (Cout, 3, k, k), got {tuple(img.shape)} {tuple(w.shape)}")
+    bb, _, h, wd = img.shape
+    cout, k = w.shape[0], w.shape[2]
+    for name, t in (("w", w), ("bias", bias), ("ln_w", ln_w), ("ln_b", ln_b)):
+        if t.dtype != torch.float32 or (name != "w" and tuple(t.shape) != (cout,)):
+            raise TrambaHipError(f"patch_embed_ln: {name} must be float32" + ("" if name == "w" else f" ({cout},)"))
+    if out_dtype not in _DT or img.dtype not in _DT:
+        raise TrambaHipError(f"patch_embed_ln: unsupported dtype {img.dtype} -> {out_dtype}")
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    y = torch.empty((bb, max(ho, 0), max(wo, 0), cout), dtype=out_dtype, device=img.device)
+    _check(lib().tramba_patch_embed_ln(_ptr(img), _ptr(w), _ptr(bias), _ptr(ln_w), _ptr(ln_b), _ptr(y), bb, h, wd, k, stride, pad,
+                                       cout, eps, _DT[img.dtype], _DT[out_dtype], _stream()), "patch_embed_ln")
     return y

@@ -434,6 +434,9 @@ def build(model_name, args):
         if getattr(args, "fused_attention_training", False):      # opt-in: attention backward on the library
             from .encoders import set_fused_attention_training
             set_fused_attention_training(model)
+        if getattr(args, "library_convolutions", False):           # opt-in: encoder convs on the library
+            from .encoders import set_library_convolutions
+            set_library_convolutions(model)
         return model
     if model_name == "BaseUMamba-SOD":
         raise NotImplementedError("BaseUMamba-SOD is the reference's ablation baseline (out of scope, SURVEY 2 #10)")
