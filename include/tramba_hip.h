@@ -33,6 +33,8 @@
  *   tramba_window_attn_bwd_cl / the gradients of the two above (autograd of the same reference lines), softmax rows
  *   tramba_kv_attn_bwd_cl       recomputed from q and k, nothing saved by the forward
  *   tramba_patch_conv_cl        Attention.sr (kernel = stride)  Models/encoder/pvtv2_encoder.py:76-78,103-106
+ *   tramba_patch_conv_dgrad_cl / the gradients of the one above (autograd of the same reference lines): input gradient,
+ *   tramba_patch_conv_wgrad_cl  weight + bias gradient
  *   tramba_patch_embed_ln       OverlapPatchEmbed (stage 1) / PatchEmbed + their LayerNorm
  *                                                               Models/encoder/pvtv2_encoder.py:159-199, swin_encoder.py:413-450
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
@@ -721,6 +723,26 @@ int tramba_kv_attn_bwd_cl(const void *q, const void *kv, const void *dy, void *d
  * order, one rounding; no atomics, no workspace, no allocation or synchronisation (capturable, bitwise reproducible). */
 int tramba_patch_conv_cl(const void *x, const void *w, const float *bias, void *y, int batch, int hin, int win, int cin,
                          int cout, int r, int dtype, void *stream);
+/* Backward of tramba_patch_conv_cl, i.e. of the `sr` conv of Attention.forward (Models/encoder/pvtv2_encoder.py:76-78,
+ * 103-106) in 16-bit training.  Same domain as the forward: bf16 / fp16, 2 <= r <= 8, Cin % 64 == 0, Cout % 8 == 0, tensors
+ * 16-byte aligned, every tensor below 2^31 bytes.  With token t = (b, i, j), M = B Ho Wo and k = (di r + dj) Cin + c:
+ *
+ * Input gradient: gx[b, i r + di, j r + dj, c] = sum_co gy[t, co] w[co, k], gy (B, Ho, Wo, Cout) and gx (B, Hin, Win, Cin) in
+ * the activation dtype, w the forward's K-major (Cout, r, r, Cin) copy.  A GEMM over 16-token tiles reduced over Cout on the
+ * matrix cores (the weight tile is staged as it lies and read transposed); one rounding; 16-byte stores into x's layout.
+ * Every element of gx is written exactly once: rows >= r Ho and columns >= r Wo receive zeros. */
+int tramba_patch_conv_dgrad_cl(const void *gy, const void *w, void *gx, int batch, int hin, int win, int cin, int cout, int r,
+                               int dtype, void *stream);
+/* Weight gradient: gw[co, k] = sum_t gy[t, co] x[patch(t), k] and, with want_bias, gb[co] = sum_t gy[t, co], f32, x read in
+ * place.  The 32-token steps of the reduction are dealt in runs to S = tramba_patch_conv_wgrad_split(...) workgroups per
+ * output tile (S depends on the shape alone; 0 for a shape the entry refuses).  `work` receives S slabs of
+ * (Cout K + Cout) floats, slab z = [gw partial (Cout, r, r, Cin) | gb partial (Cout)] of run z; the gradient is their sum in
+ * index order (tramba_slab_sum), and for S == 1 slab 0 is the gradient itself.  Without want_bias the gb part is
+ * zero.  tramba_patch_conv_wgrad_work is the size of `work` in bytes.  No atomics: bitwise reproducible. */
+int tramba_patch_conv_wgrad_split(int batch, int hin, int win, int cin, int cout, int r);
+size_t tramba_patch_conv_wgrad_work(int batch, int hin, int win, int cin, int cout, int r);
+int tramba_patch_conv_wgrad_cl(const void *gy, const void *x, float *work, size_t work_bytes, int batch, int hin, int win,
+                               int cin, int cout, int r, int want_bias, int dtype, void *stream);
 /* First-layer patch embedding fused with its LayerNorm: OverlapPatchEmbed.forward of patch_embed1
  * (Models/encoder/pvtv2_encoder.py:159-199; k 7 / stride 4 / pad 3, Cout 64) and PatchEmbed.forward
  * (Models/encoder/swin_encoder.py:413-450; k 4 / stride 4 / pad 0, Cout 128); any other form is refused.

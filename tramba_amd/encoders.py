@@ -25,6 +25,17 @@ unless `set_library_convolutions(model)` (or `build(name, args)` with `args.libr
 library in 16-bit inference: `hip.patch_embed_ln` reads the NCHW image and writes LayerNorm-ed tokens,
 `hip.conv3x3s2_cl` and `hip.patch_conv_cl` read the channels-last token map as it lies.  With the switch on, a Tramba-P
 forward calls no framework convolution and is bitwise reproducible.
+
+The whole training path moves onto the library with `set_library_training(model)` (or `build(name, args)` with
+`args.library_training`; off by default, and with it off nothing changes).  With autograd on and 16-bit activations every
+Linear runs on `_LinearTrainCL`, every LayerNorm on `_LayerNormCL`, PVT's depth-wise 3x3 on `_DwConvCL` on the token map as
+it lies, its spatial-reduction convs on `_PatchConvFn` (`hip.patch_conv_cl` forward, `hip.patch_conv_dgrad_cl` /
+`hip.patch_conv_wgrad_cl` backward, csrc/patch_conv_bwd.hip), its 3x3 / stride-2 patch embeddings on `_ConvIm2colCL`, and the
+first-layer embeddings on `_LinearTrainCL` over patch rows made by a framework data-movement op (the image needs no
+gradient).  The switch implies the fused attention backward; a block the attention kernels do not take keeps stock SDPA
+for the attention alone.  A 16-bit Tramba-S / -P training step at 384 x 384 then reaches `F.linear`, `F.layer_norm`,
+`F.conv2d` and `F.scaled_dot_product_attention` zero times from this file and captures as one `GraphedTrainStep`.  GELU,
+residual adds, drop-path and the per-call 16-bit casts of the weights stay framework element-wise ops.
 """
 import math
 
@@ -33,14 +44,25 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip
-from .modules import DropPath, _cache, _f32, _infer
+from .modules import (DropPath, _cache, _ConvIm2colCL, _dwconv_train_cl, _f32, _infer, _LayerNormCL, _LinearTrainCL)
+
+_LOWP = (torch.bfloat16, torch.float16)
+
+
+def _lib_train(m, x):
+    """`m` was switched by set_library_training() and `x` is a 16-bit device tensor (the callers have established that
+    autograd is needed): the op runs on the library's autograd Functions"""
+    return getattr(m, "library_training", False) and x.is_cuda and x.dtype in _LOWP
 
 
 def _lin(m: nn.Linear, x, act=hip.ACT_NONE, residual=None):
     if _infer(x, m.weight):
         w = m.weight if m.weight.dtype == x.dtype else _cache(m).get(("w", x.dtype), (m.weight,), lambda: m.weight.to(x.dtype))
         return hip.linear_cl(x.contiguous(), w, None if m.bias is None else _f32(m.bias), residual, act)
-    y = F.linear(x, m.weight.to(x.dtype), None if m.bias is None else m.bias.to(x.dtype))
+    if _lib_train(m, x) and m.in_features % 8 == 0 and m.out_features % 8 == 0:
+        y = _LinearTrainCL.apply(x, m.weight, m.bias)
+    else:
+        y = F.linear(x, m.weight.to(x.dtype), None if m.bias is None else m.bias.to(x.dtype))
     if act == hip.ACT_GELU:
         y = F.gelu(y)
     return y if residual is None else y + residual
@@ -49,7 +71,65 @@ def _lin(m: nn.Linear, x, act=hip.ACT_NONE, residual=None):
 def _ln(m: nn.LayerNorm, x):
     if _infer(x, m.weight):
         return hip.layernorm_cl(x.contiguous(), _f32(m.weight), _f32(m.bias), m.eps)
+    if _lib_train(m, x) and x.shape[-1] % 8 == 0 and x.shape[-1] <= 2048:
+        return _LayerNormCL.apply(x, m.weight, m.bias, m.eps)
     return F.layer_norm(x.float(), m.normalized_shape, m.weight.float(), m.bias.float(), m.eps).to(x.dtype)
+
+
+class _PatchConvFn(torch.autograd.Function):
+    """hip.patch_conv_cl (kernel = stride = r on the channels-last map) with its backward on the library: x (B, H, W, Cin),
+    w (Cout, Cin, r, r) and b (Cout) as the module holds them -> (B, H // r, W // r, Cout).  Saves x and the K-major 16-bit
+    weight the forward read; the f32 weight gradient returns to the parameter's layout with one permute (a copy, so its
+    slab sum cannot be deferred)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x = x.contiguous()
+        wk = w.detach().to(x.dtype).permute(0, 2, 3, 1).contiguous()
+        ctx.save_for_backward(x, wk)
+        ctx.has_bias, ctx.wdtype = b is not None, w.dtype
+        return hip.patch_conv_cl(x, wk, None if b is None else b.detach().float().contiguous())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, wk = ctx.saved_tensors
+        gy = gy.contiguous()
+        if gy.dtype != x.dtype:
+            gy = gy.to(x.dtype)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            gx = hip.patch_conv_dgrad_cl(gy, wk, x.shape)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw, gb = hip.patch_conv_wgrad_cl(gy, x, wk.shape[1], want_bias=ctx.has_bias)
+            gw = gw.permute(0, 3, 1, 2).contiguous().to(ctx.wdtype)          # back to (Cout, Cin, r, r)
+        return gx, gw, gb
+
+
+def _embed_rows_train(proj: nn.Conv2d, x):
+    """First-layer patch embedding on the training path: the image needs no gradient, so the patch rows are made by a
+    framework data-movement op (a permute copy for kernel = stride, F.unfold otherwise) and the product and its weight
+    gradient run on `_LinearTrainCL`, K padded to a multiple of 8.  x (B, 3, H, W) -> ((B, Ho * Wo, Cout), Ho, Wo)."""
+    b, c, h, w = x.shape
+    k, st, pd = proj.kernel_size[0], proj.stride[0], proj.padding[0]
+    ho, wo = (h + 2 * pd - k) // st + 1, (w + 2 * pd - k) // st + 1
+    if k == st and pd == 0:
+        rows = x[:, :, :ho * k, :wo * k].reshape(b, c, ho, k, wo, k).permute(0, 2, 4, 1, 3, 5).reshape(b, ho * wo, c * k * k)
+    else:
+        rows = F.unfold(x, k, padding=pd, stride=st).transpose(1, 2)          # columns (c, ky, kx): the weight's own order
+    # cast first: a 16-bit weight keeps _LinearTrainCL from deferring the slab sum of a gradient that the reshape / pad
+    # backward below it reads; the gradient then returns to f32 through the cast's backward, as on the F.conv2d path
+    w2 = proj.weight.to(x.dtype).reshape(proj.out_channels, -1)
+    pad = -w2.shape[1] % 8
+    if pad:
+        rows, w2 = F.pad(rows, (0, pad)), F.pad(w2, (0, pad))
+    return _LinearTrainCL.apply(rows.contiguous(), w2, proj.bias), ho, wo
+
+
+def _embed_rows_ok(m, proj: nn.Conv2d, x):
+    return (_lib_train(m, x) and not _infer(x, proj.weight) and not x.requires_grad and proj.groups == 1
+            and proj.kernel_size[0] == proj.kernel_size[1] and proj.stride[0] == proj.stride[1]
+            and proj.padding[0] == proj.padding[1] and proj.out_channels % 8 == 0)
 
 
 class _WindowAttnFn(torch.autograd.Function):
@@ -99,6 +179,25 @@ def set_fused_attention_training(model, enabled=True):
         if isinstance(m, (SwinTransformerBlock, _PvtAttention)):
             m.fused_attention_training = bool(enabled)
             count += 1
+    return count
+
+
+def set_library_training(model, enabled=True):
+    """Put the training path of the Swin / PVT encoder of `model` on the library (off by default): with autograd on and
+    16-bit activations every Linear and LayerNorm runs on `_LinearTrainCL` / `_LayerNormCL`, PVT's depth-wise 3x3 on
+    `_DwConvCL`, its spatial-reduction convs on `_PatchConvFn`, its 3x3 / stride-2 patch embeddings on `_ConvIm2colCL`,
+    the first-layer embeddings on `_LinearTrainCL` over framework-made patch rows, and attention on `_WindowAttnFn` /
+    `_KvAttnFn` wherever the kernels take the shape (the switch implies `set_fused_attention_training`; a block they do
+    not take keeps stock SDPA for the attention alone).  fp32 activations and inference are untouched.  Returns the
+    number of modules switched."""
+    count, seen = 0, set()
+    for m in model.modules():
+        if isinstance(m, _LIBRARY_TRAINING_KINDS):
+            for sub in (m, *m.children()):
+                if id(sub) not in seen and (sub is m or isinstance(sub, (nn.Linear, nn.LayerNorm, nn.Conv2d))):
+                    seen.add(id(sub))
+                    sub.library_training = bool(enabled)
+                    count += 1
     return count
 
 
@@ -185,6 +284,8 @@ class _PvtMlp(nn.Module):
         if _infer(y, conv.weight):
             taps = _cache(self).get("taps", (conv.weight,), lambda: conv.weight.detach().float().reshape(-1, 9).t().contiguous())
             y = hip.dwconv_cl(y.view(b, h, w, -1), taps, _f32(conv.bias), hip.ACT_GELU).view(b, n, -1)
+        elif _lib_train(conv, y):
+            y = F.gelu(_dwconv_train_cl(y.view(b, h, w, -1), conv).view(b, n, -1))     # on the token map as it lies
         else:
             y = _conv(conv, y.transpose(1, 2).reshape(b, -1, h, w)).flatten(2).transpose(1, 2)
             y = F.gelu(y)
@@ -196,6 +297,7 @@ class _PvtAttention(nn.Module):
 
     fused_attention_training = False       # set_fused_attention_training(); no parameter, not in the state_dict
     library_convolutions = False           # set_library_convolutions(); likewise
+    library_training = False               # set_library_training(); likewise (implies fused_attention_training)
 
     def __init__(self, dim, num_heads, qkv_bias, sr_ratio):
         super().__init__()
@@ -213,7 +315,7 @@ class _PvtAttention(nn.Module):
         b, n, c = x.shape
         m = (h // self.sr_ratio) * (w // self.sr_ratio) if self.sr_ratio > 1 else n
         infer = _infer(x, self.q.weight)
-        train = (self.fused_attention_training and not infer
+        train = ((self.fused_attention_training or self.library_training) and not infer
                  and hip.kv_attention_train_supported(x.dtype, m, c, self.num_heads))
         if not train and not (infer and hip.kv_attention_supported(x.dtype, m, c, self.num_heads)):
             return self._forward_stock(x, h, w, residual)
@@ -235,7 +337,14 @@ class _PvtAttention(nn.Module):
                 and hip.patch_conv_supported(x.dtype, c, c, self.sr_ratio)):
             wk, bias = _conv_params(self.sr, x.dtype, kmajor=True)    # kernel = stride: a patch GEMM on the map as it lies
             return hip.patch_conv_cl(x.contiguous().view(b, h, w, c), wk, bias).view(b, -1, c)
+        if self._reduce_on_library(x):
+            return _PatchConvFn.apply(x.contiguous().view(b, h, w, c), self.sr.weight, self.sr.bias).view(b, -1, c)
         return _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
+
+    def _reduce_on_library(self, x):
+        """training with the switch on: the sr conv and its backward run on the library"""
+        return (_lib_train(self, x) and not _infer(x, self.sr.weight)
+                and hip.patch_conv_train_supported(x.dtype, x.shape[-1], self.sr.out_channels, self.sr_ratio))
 
     def _forward_stock(self, x, h, w, residual=None):
         """stock torch attention: fp32, autograd on, or a key count the library does not take (e.g. 576 keys at 768x768)"""
@@ -243,7 +352,10 @@ class _PvtAttention(nn.Module):
         nh = self.num_heads
         q = _lin(self.q, x).view(b, n, nh, c // nh).transpose(1, 2)
         if self.sr_ratio > 1:
-            xr = _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
+            if self._reduce_on_library(x):
+                xr = self._reduce(x, h, w)
+            else:
+                xr = _conv(self.sr, x.transpose(1, 2).reshape(b, c, h, w)).flatten(2).transpose(1, 2)
             xr = _ln(self.norm, xr)
         else:
             xr = x
@@ -280,6 +392,7 @@ class _OverlapPatchEmbed(nn.Module):
         self.norm = nn.LayerNorm(dim)
 
     library_convolutions = False           # set_library_convolutions(); no parameter, not in the state_dict
+    library_training = False               # set_library_training(); likewise
 
     def forward(self, x, channels_last=False):
         """x: the NCHW image or map; channels_last: x is the previous stage's (B, H, W, C) map instead"""
@@ -295,6 +408,15 @@ class _OverlapPatchEmbed(nn.Module):
                 y = hip.conv3x3s2_cl(x.contiguous(), wk.view(proj.out_channels, -1), bias)
                 b, h, w, c = y.shape
                 return _ln(self.norm, y.view(b, h * w, c)), h, w
+        if not channels_last and _embed_rows_ok(self, proj, x):
+            y, h, w = _embed_rows_train(proj, x)                        # patch rows by F.unfold, product on the library
+            return _ln(self.norm, y), h, w
+        if (channels_last and _lib_train(self, x) and not _infer(x, proj.weight) and proj.kernel_size == (3, 3)
+                and proj.stride[0] == proj.stride[1] and proj.padding[0] == proj.padding[1] and proj.in_channels % 8 == 0
+                and proj.out_channels % 8 == 0):
+            y = _ConvIm2colCL.apply(x.contiguous(), proj.weight, proj.bias, proj.stride, proj.padding)
+            b, h, w, c = y.shape
+            return _ln(self.norm, y.view(b, h * w, c)), h, w
         if channels_last:
             x = x.permute(0, 3, 1, 2)                                   # the strided conv reads NCHW (a view)
         x = _conv(proj, x)
@@ -420,6 +542,7 @@ class _SwinMlp(nn.Module):
 class SwinTransformerBlock(nn.Module):
     """swin_encoder.py:166-273."""
     fused_attention_training = False       # set_fused_attention_training(); no parameter, not in the state_dict
+    library_training = False               # set_library_training(); likewise (implies fused_attention_training)
 
     def __init__(self, dim, input_resolution, num_heads, window_size, shift_size, mlp_ratio, drop_path):
         super().__init__()
@@ -449,7 +572,8 @@ class SwinTransformerBlock(nn.Module):
         h, w = self.input_resolution
         b, l, c = x.shape
         ws, sh, attn = self.window_size, self.shift_size, self.attn
-        if (self.fused_attention_training and not _infer(x, attn.qkv.weight, attn.relative_position_bias_table)
+        if ((self.fused_attention_training or self.library_training)
+                and not _infer(x, attn.qkv.weight, attn.relative_position_bias_table)
                 and hip.window_attention_train_supported(x.dtype, h, w, c, attn.num_heads, ws, sh)):
             return self._forward_fused_train(x)
         if self.training or not (_infer(x, attn.qkv.weight)
@@ -541,12 +665,15 @@ class _SwinPatchEmbed(nn.Module):
         self.norm = nn.LayerNorm(dim)
 
     library_convolutions = False           # set_library_convolutions(); no parameter, not in the state_dict
+    library_training = False               # set_library_training(); likewise
 
     def forward(self, x):
         if tuple(x.shape[-2:]) != self.img_size:
             raise RuntimeError(f"Input image size {tuple(x.shape[-2:])} doesn't match model {self.img_size}")
         if self.library_convolutions and _patch_embed_ln_ok(self.proj, self.norm, x):
             return _patch_embed_ln(self.proj, self.norm, x).flatten(1, 2)
+        if _embed_rows_ok(self, self.proj, x):
+            return _ln(self.norm, _embed_rows_train(self.proj, x)[0])  # patch rows by a permute copy, product on the library
         return _ln(self.norm, _conv(self.proj, x).flatten(2).transpose(1, 2))
 
 
@@ -586,3 +713,8 @@ class SwinTransformer(nn.Module):
 
     def forward(self, x):
         return [f.permute(0, 3, 1, 2).contiguous() for f in self.features_cl(x)][::-1]
+
+
+# the module kinds set_library_training() flags, together with their direct Linear / LayerNorm / Conv2d children
+_LIBRARY_TRAINING_KINDS = (_PvtDW, _PvtMlp, _PvtAttention, _PvtBlock, _OverlapPatchEmbed, PyramidVisionTransformerImpr,
+                           _WindowAttention, _SwinMlp, SwinTransformerBlock, PatchMerging, _SwinPatchEmbed, SwinTransformer)

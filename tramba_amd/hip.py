@@ -137,6 +137,10 @@ SIGNATURES = {
     "tramba_kv_attn_bwd_work": (ctypes.c_size_t, [c_int, c_i64, c_int, c_int, c_int]),
     "tramba_kv_attn_bwd_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t, c_int, c_i64] + [c_int] * 4 + [c_vp]),
     "tramba_patch_conv_cl": (c_int, [c_vp] * 4 + [c_int] * 7 + [c_vp]),
+    "tramba_patch_conv_dgrad_cl": (c_int, [c_vp] * 3 + [c_int] * 7 + [c_vp]),
+    "tramba_patch_conv_wgrad_split": (c_int, [c_int] * 6),
+    "tramba_patch_conv_wgrad_work": (ctypes.c_size_t, [c_int] * 6),
+    "tramba_patch_conv_wgrad_cl": (c_int, [c_vp] * 3 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
     "tramba_patch_embed_ln": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_f, c_int, c_int, c_vp]),
 }
 
@@ -1832,6 +1836,56 @@ def patch_conv_cl(x, w_kmajor, bias):
     _check(lib().tramba_patch_conv_cl(_ptr(x), _ptr(w_kmajor), _ptr(bias), _ptr(y), bb, h, wd, cin, cout, r, dt(x), _stream()),
            "patch_conv_cl")
     return y
+
+
+def patch_conv_train_supported(dtype, cin, cout, r):
+    """can patch_conv_dgrad_cl / patch_conv_wgrad_cl take this layer?  The forward's domain, with an f32 weight gradient
+    below 2^31 bytes.  A per-layer predicate: the entries also refuse a map or gy of 2^31 bytes and more, and more than
+    65535 x 16 output tokens, which depend on the batch and the map, not on the layer."""
+    return patch_conv_supported(dtype, cin, cout, r) and cout * r * r * cin * 4 < 2 ** 31
+
+
+def _patch_conv_geom(name, gy, x_shape, x_dtype):
+    if gy.dim() != 4 or len(x_shape) != 4 or gy.dtype != x_dtype:
+        raise TrambaHipError(f"{name}: need gy (B, Ho, Wo, Cout) and x (B, H, W, Cin) of one dtype, got {tuple(gy.shape)} "
+                             f"{gy.dtype} {tuple(x_shape)} {x_dtype}")
+    bb, h, wd, cin = x_shape
+    return bb, h, wd, cin, gy.shape[3]
+
+
+def patch_conv_dgrad_cl(gy, w_kmajor, x_shape):
+    """Input gradient of patch_conv_cl: gy (B, H // r, W // r, Cout), w_kmajor (Cout, r, r, Cin) (the forward's copy), x_shape
+    (B, H, W, Cin) -> gx of that shape in gy's dtype, every element written (zeros where no patch reaches)."""
+    _dev(gy, w_kmajor)
+    bb, h, wd, cin, cout = _patch_conv_geom("patch_conv_dgrad_cl", gy, tuple(x_shape), w_kmajor.dtype)
+    r = w_kmajor.shape[1] if w_kmajor.dim() == 4 else 0
+    if w_kmajor.dim() != 4 or tuple(w_kmajor.shape) != (cout, r, r, cin) or r < 1 \
+            or tuple(gy.shape[:3]) != (bb, h // r, wd // r):
+        raise TrambaHipError(f"patch_conv_dgrad_cl: gy {tuple(gy.shape)} and w {tuple(w_kmajor.shape)} do not belong to x "
+                             f"{tuple(x_shape)}")
+    gx = torch.empty((bb, h, wd, cin), dtype=gy.dtype, device=gy.device)
+    _check(lib().tramba_patch_conv_dgrad_cl(_ptr(gy), _ptr(w_kmajor), _ptr(gx), bb, h, wd, cin, cout, r, dt(gy), _stream()),
+           "patch_conv_dgrad_cl")
+    return gx
+
+
+def patch_conv_wgrad_cl(gy, x, r, want_bias=False, defer=False):
+    """Weight gradient of patch_conv_cl: gy (B, H // r, W // r, Cout), x (B, H, W, Cin) -> (gw (Cout, r, r, Cin) f32 K-major,
+    gb (Cout) f32 or None).  The kernel leaves one f32 slab per token run; they are added in index order by slab_sum.
+    defer: inside `deferred_sums()` that sum is recorded for `flush_sums()` (see _SumQueue)."""
+    _dev(gy, x)
+    bb, h, wd, cin, cout = _patch_conv_geom("patch_conv_wgrad_cl", gy, tuple(x.shape), x.dtype)
+    if r < 1 or tuple(gy.shape[:3]) != (bb, h // r, wd // r):
+        raise TrambaHipError(f"patch_conv_wgrad_cl: gy {tuple(gy.shape)} does not belong to x {tuple(x.shape)} with r = {r}")
+    nsplit = lib().tramba_patch_conv_wgrad_split(bb, h, wd, cin, cout, r)
+    nbytes = lib().tramba_patch_conv_wgrad_work(bb, h, wd, cin, cout, r)
+    slab = cout * r * r * cin + cout
+    work = torch.empty((nsplit, slab), dtype=torch.float32, device=gy.device)      # (no slab for a shape the entry refuses)
+    _check(lib().tramba_patch_conv_wgrad_cl(_ptr(gy), _ptr(x), _ptr(work), nbytes, bb, h, wd, cin, cout, r, int(want_bias),
+                                            dt(gy), _stream()), "patch_conv_wgrad_cl")
+    out = slab_sum(work, defer) if nsplit > 1 else work[0]
+    gw = out[:slab - cout].view(cout, r, r, cin)
+    return gw, (out[slab - cout:] if want_bias else None)
 
 
 def patch_embed_ln_supported(out_dtype, k, stride, pad, cout):

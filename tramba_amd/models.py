@@ -437,6 +437,9 @@ def build(model_name, args):
         if getattr(args, "library_convolutions", False):           # opt-in: encoder convs on the library
             from .encoders import set_library_convolutions
             set_library_convolutions(model)
+        if getattr(args, "library_training", False):               # opt-in: encoder training path on the library
+            from .encoders import set_library_training
+            set_library_training(model)
         return model
     if model_name == "BaseUMamba-SOD":
         raise NotImplementedError("BaseUMamba-SOD is the reference's ablation baseline (out of scope, SURVEY 2 #10)")

@@ -715,7 +715,7 @@ def _fold_layernorm(lin, norm, dtype):
 
 class _LayerNormCL(torch.autograd.Function):
     """LayerNorm over the last dim with autograd, both directions HIP (training path): no fp32 round trip of the
-    activation, dgamma / dbeta by in-kernel accumulation + atomics."""
+    activation, dgamma / dbeta as per-workgroup partial rows added in index order (hip.slab_sum): no atomics."""
 
     @staticmethod
     def forward(ctx, x, w, b, eps):
