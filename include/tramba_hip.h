@@ -593,24 +593,24 @@ int tramba_sod_loss_grad(const float *logits, const float *label, const float *c
  * utils/loss.py:39 with k = 15): zero padding, divisor k * k everywhere (count_include_pad, torch's default).  Odd k <= 63, any
  * h, w >= 1 (windows larger than the image included), labels any floats.  Separable sums in LDS, fixed order, plain stores. */
 int tramba_loss_weight_map(const float *label, float *weit, int planes, int h, int w, int k, void *stream);
-/* tramba_sod_loss_sums with a per-pixel weight W and a smoothed BCE target yhat = (1 - eps) y + eps / 2 (utils/loss.py:16-19,
- * 26; eps = 0.001 for structure_loss, 0 for wbce):
- *   part[plane][blk][0..5) = sum of { bce(z, yhat),  W bce(z, yhat),  W,  W sigmoid(z) y,  W (sigmoid(z) + y) }
- * (utils/loss.py:27-28, 30-32; y unsmoothed in the last two, as there).  wmap (planes, hout, wout) f32 is the map of
- * tramba_loss_weight_map (W = wmap) or, with weight_is_raw != 0, the caller's `weight` of utils/loss.py:23-24 (W = 1 + 5 wmap). */
+/* The weighted forms of the three entries above, through the same kernels: arguments, limits, workspace, host arrays by
+ * value and summation order as there.  wmap (planes, hout, wout) f32 is the map of tramba_loss_weight_map (W = wmap) or, with
+ * weight_is_raw != 0, the caller's `weight` of utils/loss.py:23-24 (W = 1 + 5 wmap); the BCE target is smoothed,
+ * yhat = (1 - eps) y + eps / 2 with 0 <= eps < 1 (utils/loss.py:16-19, 26; eps = 0.001 for structure_loss, 0 for wbce).
+ * Sums:   part[plane][blk][0..5) = sum of { bce(z, yhat),  W bce(z, yhat),  W,  W sigmoid(z) y,  W (sigmoid(z) + y) }
+ *         (utils/loss.py:27-28, 30-32; y unsmoothed in the last two, as there). */
 int tramba_sod_wloss_sums(const float *logits, const float *label, const float *wmap, float *part, int planes, int h, int w,
                           int hout, int wout, int nblk, float eps, int weight_is_raw, void *stream);
-/* tramba_sod_loss_finish for the tables above (parts[o]: (planes, nblk[o], 5)).  With I = sum W p y, U = sum W (p + y):
+/* Finish: parts[o]: (planes, nblk[o], 5).  With I = sum W p y, U = sum W (p + y):
  *   loss[0] = sum_o weights[o] * ( BCE term + [with_iou] mean over planes of 1 - (I + 1) / (U - I + 1) )       (utils/loss.py:33-34)
  *   per_pixel == 0: BCE term = sum bce / (planes npix) -- utils/loss.py:27 AS IT EXECUTES: `reduce='none'` is the legacy
  *                   argument and a non-empty string is true, so the call returns the batch mean and W cancels in line 28;
  *   per_pixel != 0: BCE term = mean over planes of (sum W bce) / (sum W) -- lines 27-28 with reduction='none', as published.
  * coefs[o] (planes, 4) f32 = { a, cI, cU, per_pixel } of d loss / d resized logit = a omega (p - yhat) + p (1 - p) W (cI y + cU),
- * omega = W when per_pixel, else 1;  with_iou == 0 (wbce): cI = cU = 0.  Host arrays by value, planes <= 512, as above. */
+ * omega = W when per_pixel, else 1;  with_iou == 0 (wbce): cI = cU = 0. */
 int tramba_sod_wloss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs, int nout,
                             int planes, int64_t npix, int per_pixel, int with_iou, float *loss, void *stream);
-/* tramba_sod_loss_grad for the weighted losses (autograd through utils/loss.py:26-34): the same passes reading the weight map
- * as well, the same device scalar gscale, the same workspace and limits. */
+/* Gradient (autograd through utils/loss.py:26-34): reads the weight map as well; eps / weight_is_raw as given to the sums. */
 size_t tramba_sod_wloss_grad_workspace(int planes, int h, int w, int hout, int wout);
 int tramba_sod_wloss_grad(const float *logits, const float *label, const float *wmap, const float *coef, const float *gscale,
                           float *glogits, void *workspace, size_t workspace_bytes, int planes, int h, int w, int hout, int wout,

@@ -25,7 +25,19 @@
       library, captured twice as well, all replayed alternately in one process.  aa_spread_ms is the round-to-round
       spread of default - default2; capture_spread_ms is the distance between the means of two captures of the same
       code, the larger of the two and the one a difference between libraries or losses is read against.
-      Written to profiles/loss_bench.json, section by section."""
+      Written to profiles/loss_bench.json, section by section.
+
+  python scripts/bench_loss.py --ab [rounds] [out.json]
+      This tree's library against the parent commit's (tramba_amd/_lib_parent/, required), `hip._lib` swapped between them
+      in one process:
+        bits   every LOSS_CASES entry of tests/test_gpu_step_ends.py, hard and soft labels, bce_iou and the four weighted
+               forms through the bindings: `torch.equal` of the loss, the coefficient table and every output's gradient
+               (incoming gradient 0.37) between the two libraries; all_equal says whether every one of them is True
+        loss   forward + backward of bce_iou and structure/reference at the training shapes, captured on each library TWICE
+               and replayed alternately: mean of new - parent per variant against capture_spread_ms, the larger distance
+               between the means of two captures of the same code (within_3x_spread)
+        step   the whole-step section above
+      Written to profiles/loss_unify_ab.json."""
 import json
 import os
 import statistics
@@ -34,6 +46,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "profiles", "loss_bench.json")
+OUT_AB = os.path.join(ROOT, "profiles", "loss_unify_ab.json")
+PARENT = os.path.join(ROOT, "tramba_amd", "_lib_parent", "libtramba_hip.so")
 BATCH, SIZE, OUTS = 8, 384, (24, 48, 96, 384)
 WINDOW_S, GRAPH_LAUNCHES, STEP_REPLAYS = 0.3, 200, 10
 
@@ -174,12 +188,94 @@ def bench_losses(rounds):
     }
 
 
+def ab_bits(rounds):
+    import torch
+    from tramba_amd import hip
+    from ab_lib import load
+    from test_gpu_losses import FORMS, LOSS_CASES, _label
+    import synth
+    libs = {"parent": load(PARENT), "new": hip.lib()}
+    gscale = torch.tensor(0.37, device="cuda")
+
+    def run(lib, form, outs, lab):
+        """(loss, coefs, gradient of every output) of one form through the bindings on one library"""
+        hip._lib = lib
+        if form == "bce_iou":
+            loss, coefs = hip.sod_loss(outs, lab)
+            grads = [hip.sod_loss_grad(o, lab, coefs[i], gscale) for i, o in enumerate(outs)]
+        else:
+            kind, bce = form.split("/")
+            k, eps, iou = FORMS[kind]
+            wmap = hip.loss_weight_map(lab, k)
+            loss, coefs = hip.sod_wloss(outs, lab, wmap, eps=eps, per_pixel=bce == "pixel", with_iou=iou)
+            grads = [hip.sod_wloss_grad(o, lab, wmap, coefs[i], gscale, eps=eps) for i, o in enumerate(outs)]
+        torch.cuda.synchronize()
+        return loss, coefs, grads
+
+    forms = ["bce_iou"] + [f"{kind}/{bce}" for kind in FORMS for bce in ("reference", "pixel")]
+    res = {}
+    try:
+        for name, (b, c, (hh, ww), sizes) in LOSS_CASES.items():
+            outs = [synth.synth_input(f"loss_{name}_{i}", (b, c, h, w), scale=3.0).cuda() for i, (h, w) in enumerate(sizes)]
+            for soft in (False, True):
+                lab = _label(f"wloss_{name}", (b, c, hh, ww), soft).cuda()
+                for form in forms:
+                    (lp, cp, gp), (ln, cn, gn) = (run(libs[k], form, outs, lab) for k in ("parent", "new"))
+                    res[f"{name}/{'soft' if soft else 'hard'}/{form}"] = {
+                        "loss": torch.equal(lp, ln), "coefs": torch.equal(cp, cn),
+                        "grads": [torch.equal(p, n) for p, n in zip(gp, gn)], "loss_value": float(ln)}
+    finally:
+        hip._lib = libs["new"]
+    return {"what": "torch.equal(parent library, this library) of the loss, the coefficient table and each output's gradient",
+            "all_equal": all(v["loss"] and v["coefs"] and all(v["grads"]) for v in res.values()), "cases": res}
+
+
+def ab_loss(rounds):
+    import torch
+    from tramba_amd import hip, train
+    from ab_lib import load
+    libs = {"parent": load(PARENT), "new": hip.lib()}
+    g = torch.Generator().manual_seed(0)
+    outs = [(3.0 * torch.randn(BATCH, 1, s, s, generator=g)).cuda().requires_grad_() for s in OUTS]
+    blobs = torch.nn.functional.avg_pool2d(torch.randn(BATCH, 1, SIZE, SIZE, generator=g), 25, 1, 12)
+    label = (blobs > 0.02).float().cuda()
+    specs = {"bce_iou": train.tramba_loss, "structure/reference": train.SodLoss("structure", "reference")}
+
+    def fwd_bwd(loss_fn):
+        def run():
+            for o in outs:
+                o.grad = None
+            loss_fn(outs, label).backward()
+        return run
+
+    keep = {}
+    try:
+        for tag in ("parent", "new", "parent2", "new2"):          # a graph holds the kernels of the library it was captured on
+            hip._lib = libs[tag.rstrip("2")]
+            for name, fn in specs.items():
+                keep[f"{name}:{tag}"] = graphed(fwd_bwd(fn))
+    finally:
+        hip._lib = libs["new"]
+    t, n = timed(keep, rounds)
+    mean = {k: statistics.mean(v) for k, v in t.items()}
+    res = {"what": f"loss forward + backward captured once per (loss, library, capture) and replayed alternately, batch {BATCH}, "
+                   f"label {SIZE}x{SIZE}, outputs {list(OUTS)}, {rounds} rounds, windows of about {WINDOW_S} s",
+           "ms_per_call": stats((t, n))}
+    for name in specs:
+        m = {tag: mean[f"{name}:{tag}"] for tag in ("parent", "new", "parent2", "new2")}
+        spread = max(abs(m["parent"] - m["parent2"]), abs(m["new"] - m["new2"]))
+        diff = (m["new"] + m["new2"] - m["parent"] - m["parent2"]) / 2
+        res[name] = {"mean_new_minus_parent_ms": diff, "capture_spread_ms": spread, "within_3x_spread": abs(diff) <= 3 * spread,
+                     "not_slower_beyond_3x_spread": diff <= 3 * spread}
+    return res
+
+
 def bench_step(rounds):
     import torch
     import tramba_amd as ta
     from tramba_amd import hip, train
     from ab_lib import load
-    new, parent_path = hip.lib(), os.path.join(ROOT, "tramba_amd", "_lib_parent", "libtramba_hip.so")
+    new, parent_path = hip.lib(), PARENT
     # two captures of the same code differ by more than the rounds of one capture do (where a capture's buffers land), so
     # every library is captured twice, the libraries alternating: capture_spread_ms is what a difference is read against
     variants = [("default", None, new), ("structure", train.SodLoss("structure"), new), ("default2", None, new)]
@@ -221,14 +317,21 @@ def bench_step(rounds):
 
 def main():
     args = sys.argv[1:]
+    ab = args[:1] == ["--ab"]
+    args = args[1:] if ab else args
     rounds = int(args[0]) if args else 8
-    out_path = args[1] if len(args) > 1 else OUT
+    out_path = args[1] if len(args) > 1 else (OUT_AB if ab else OUT)
     import torch
     assert torch.cuda.is_available(), "bench_loss.py measures on the GPU"
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
+    sections = (("losses", bench_losses), ("step", bench_step))
+    if ab:
+        assert os.path.exists(PARENT), f"--ab needs the parent commit's library at {PARENT}"
+        sys.path[:0] = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden")]      # the tests' cases and labels
+        sections = (("bits", ab_bits), ("loss", ab_loss), ("step", bench_step))
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     doc = {}
-    for name, section in (("losses", bench_losses), ("step", bench_step)):
+    for name, section in sections:
         doc[name] = section(rounds)
         print(json.dumps(doc[name], indent=1), flush=True)
         with open(out_path, "w") as f:

@@ -228,6 +228,54 @@ def test_bindings_reject_what_the_kernels_cannot_take():
         hip.loss_weight_map(lab.to(torch.bfloat16), 31)
 
 
+@pytest.mark.parametrize("name", ["ragged", "one_pixel", "planes"])
+@pytest.mark.parametrize("soft", [False, True])
+def test_unit_weights_give_the_unweighted_loss(name, soft):
+    """The unweighted and the weighted loss are two instantiations of the same kernels (3 and 5 sums per block, I and U in
+    other slots).  With W = 1 (a raw weight of zeros, W = 1 + 5 * 0), eps = 0 and the IoU term on they are one function, in
+    either reading of the BCE term: with planes of equal size the mean over planes of sum bce / npix is the batch mean.
+    Each against the fp64 oracle at the bounds of test_loss_value_and_gradients_against_the_oracle (2e-6 max(1, |value|),
+    2e-5 relative L2), among each other at twice those, relative to the fp64 result (triangle inequality); the coefficient
+    tables within 4e-6 relative in a, cI, cU, and the selector exactly 0, 0, 1."""
+    from oracle import ops as oo
+    from tramba_amd import hip
+    b, c, (hh, ww), sizes = LOSS_CASES[name]
+    outs = [synth.synth_input(f"loss_{name}_{i}", (b, c, h, w), scale=3.0) for i, (h, w) in enumerate(sizes)]
+    lab = _label(f"wloss_{name}", (b, c, hh, ww), soft)
+    o64 = [o.double().requires_grad_() for o in outs]
+    want = oo.tramba_loss(o64, lab.double())
+    (want * 0.37).backward()
+    want = float(want.detach())
+    od, labd, gscale = [o.to(DEV) for o in outs], lab.to(DEV), torch.tensor(0.37, device=DEV)
+    zeros = torch.zeros_like(labd)
+    got = {"bce_iou": hip.sod_loss(od, labd)}
+    for per_pixel in (False, True):
+        got[f"w/pixel={per_pixel}"] = hip.sod_wloss(od, labd, zeros, eps=0.0, per_pixel=per_pixel, with_iou=True, weight_is_raw=True)
+    grads = {"bce_iou": [hip.sod_loss_grad(o, labd, got["bce_iou"][1][i], gscale) for i, o in enumerate(od)]}
+    for k in list(got)[1:]:
+        grads[k] = [hip.sod_wloss_grad(o, labd, zeros, got[k][1][i], gscale, eps=0.0, weight_is_raw=True) for i, o in enumerate(od)]
+    for k, (loss, coefs) in got.items():
+        errs = [_rel_l2(g, ref.grad) for g, ref in zip(grads[k], o64)]
+        print(f"{name} soft={soft} {k}: loss {float(loss):.8f} want {want:.8f} err {abs(float(loss) - want):.3e}, "
+              f"gradient rel L2 {['%.2e' % e for e in errs]}")
+        assert loss.dtype == torch.float32 and loss.dim() == 0 and coefs.shape == (len(od), b * c, 4)
+        assert abs(float(loss) - want) < 2e-6 * max(1.0, abs(want)), (k, float(loss), want)
+        for i, (g, e) in enumerate(zip(grads[k], errs)):
+            assert g.shape == od[i].shape
+            assert e < 2e-5, (k, i, e)
+    names = list(got)
+    for x, y in ((0, 1), (0, 2), (1, 2)):
+        (la, ca), (lb, cb) = got[names[x]], got[names[y]]
+        assert abs(float(la) - float(lb)) < 4e-6 * max(1.0, abs(want)), (names[x], names[y], float(la), float(lb))
+        for ga, gb, ref in zip(grads[names[x]], grads[names[y]], o64):
+            assert float((ga.double() - gb.double()).norm().cpu() / ref.grad.norm()) < 4e-5, (names[x], names[y])
+        rel = ((ca[..., :3].double() - cb[..., :3].double()).abs() / cb[..., :3].double().abs()).max()
+        print(f"{name} soft={soft} {names[x]} vs {names[y]}: coefficients max rel {float(rel):.3e}")
+        assert float(rel) <= 4e-6, (names[x], names[y], float(rel))
+    for k, sel in zip(names, (0.0, 0.0, 1.0)):
+        assert bool((got[k][1][..., 3] == sel).all()), k
+
+
 def _small_vss(capturable=True):
     import tramba_amd as ta
     from tramba_amd import train

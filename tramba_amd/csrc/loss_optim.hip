@@ -60,18 +60,72 @@ __device__ __forceinline__ void sig_terms(float z, float &p, float &softplus_tai
 
 constexpr int kLossThreads = 256;
 
-// part[plane][blockIdx.x][3] = { sum bce, sum p*y, sum (p + y) } over this block's pixels of the plane
-template <bool SAME>
+// The per-pixel arithmetic comes in two forms, and every kernel below is written once over them.
+//
+// PlainLoss: binary_cross_entropy_with_logits + iou_loss (train.py:76-85).  Three sums per block and plane,
+//   { sum bce, sum p y, sum (p + y) }, and d loss / d logit = a (p - y) + p (1 - p) (cI y + cU).
+// WeightedLoss: structure_loss / wbce (utils/loss.py:14-42), the same passes with a per-pixel weight W = wadd + wmul * wmap[i]
+//   -- { 0, 1 } for the box-filter map of loss_weight_map_kernel, { 1, 5 } for a caller's `weight` tensor (utils/loss.py:24)
+//   -- and a smoothed BCE target yhat = ysc * y + yadd = (1 - eps) y + eps / 2.  The weight depends on the label only: one map
+//   per loss call, shared by the deep-supervision outputs (12 B per label pixel and output instead of 8).  Five sums,
+//   { sum bce(z, yhat), sum W bce, sum W, sum W p y, sum W (p + y) } (y unsmoothed in the last two), and
+//   d loss / d logit = a omega (p - yhat) + p (1 - p) W (cI y + cU), omega = W in the per-pixel reading of the BCE term, else 1.
+// kI: where a row of sums holds I (U follows it).  `i` counts pixels from the start of the tensor.  Each form keeps its own
+// expressions: W = 1 through the weighted ones rounds differently from the plain ones.
+struct LossCoef {
+    float ca, ci, cu;   // gscale * { a, cI, cU } of the plane
+    bool pixel;         // omega = W (weighted form only)
+};
+struct PlainLoss {
+    static constexpr int kSums = 3, kI = 1;
+    static constexpr bool kWeighted = false;
+    __device__ __forceinline__ void add(float (&s)[kSums], long i, float zz, float y, float p, float tail) const
+    {
+        s[0] += fmaxf(zz, 0.f) - zz * y + tail;
+        s[1] = fmaf(p, y, s[1]);
+        s[2] += p + y;
+    }
+    __device__ __forceinline__ float grad(long i, float y, float p, const LossCoef &c) const
+    {
+        return c.ca * (p - y) + p * (1.f - p) * fmaf(c.ci, y, c.cu);
+    }
+};
+struct WeightedLoss {
+    static constexpr int kSums = 5, kI = 3;
+    static constexpr bool kWeighted = true;
+    const float *wmap;
+    float wadd, wmul, ysc, yadd;
+    __device__ __forceinline__ void add(float (&s)[kSums], long i, float zz, float y, float p, float tail) const
+    {
+        const float wt = fmaf(wmul, wmap[i], wadd);
+        const float bce = fmaxf(zz, 0.f) - zz * fmaf(ysc, y, yadd) + tail;
+        s[0] += bce;
+        s[1] = fmaf(wt, bce, s[1]);
+        s[2] += wt;
+        s[3] = fmaf(wt, p * y, s[3]);
+        s[4] = fmaf(wt, p + y, s[4]);
+    }
+    __device__ __forceinline__ float grad(long i, float y, float p, const LossCoef &c) const
+    {
+        const float wt = fmaf(wmul, wmap[i], wadd);
+        return c.ca * (c.pixel ? wt : 1.f) * (p - fmaf(ysc, y, yadd)) + p * (1.f - p) * wt * fmaf(c.ci, y, c.cu);
+    }
+};
+
+// part[plane][blockIdx.x][FORM::kSums] = the form's sums over this block's pixels of the plane
+template <bool SAME, class FORM>
 __global__ __launch_bounds__(kLossThreads) void sod_loss_sums_kernel(const float *__restrict__ z,
                                                                     const float *__restrict__ label,
-                                                                    float *__restrict__ part, int h, int w, int H, int W)
+                                                                    float *__restrict__ part, int h, int w, int H, int W,
+                                                                    FORM f)
 {
-    __shared__ float red[kLossThreads / kWave][3];
+    constexpr int NS = FORM::kSums;
+    __shared__ float red[kLossThreads / kWave][NS];
     const int plane = blockIdx.y, nblk = gridDim.x;
     const long npix = (long)H * W;
     const float *zp = z + (long)plane * h * w, *yp = label + plane * npix;
     const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    float s[NS] = {};
     for (long i = (long)blockIdx.x * kLossThreads + threadIdx.x; i < npix; i += (long)nblk * kLossThreads) {
         float zz;
         if constexpr (SAME) {
@@ -80,44 +134,43 @@ __global__ __launch_bounds__(kLossThreads) void sod_loss_sums_kernel(const float
             const int Y = (int)(i / W), X = (int)(i - (long)Y * W);
             zz = resized(zp, w, tap(Y, sy, h), tap(X, sx, w));
         }
-        const float y = yp[i];
         float p, tail;
         sig_terms(zz, p, tail);
-        s0 += fmaxf(zz, 0.f) - zz * y + tail;
-        s1 = fmaf(p, y, s1);
-        s2 += p + y;
+        f.add(s, plane * npix + i, zz, yp[i], p, tail);
     }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wv][0] = s0;
-        red[wv][1] = s1;
-        red[wv][2] = s2;
-    }
+#pragma unroll
+    for (int j = 0; j < NS; ++j) s[j] = wave_sum(s[j]);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < NS; ++j) red[wv][j] = s[j];
     __syncthreads();
-    if (threadIdx.x < 3) {
-        float s = 0.f;
-        for (int q = 0; q < kLossThreads / kWave; ++q) s += red[q][threadIdx.x];
-        part[((long)plane * nblk + blockIdx.x) * 3 + threadIdx.x] = s;
+    if (threadIdx.x < NS) {
+        float t = 0.f;
+        for (int q = 0; q < kLossThreads / kWave; ++q) t += red[q][threadIdx.x];
+        part[((long)plane * nblk + blockIdx.x) * NS + threadIdx.x] = t;
     }
 }
 
 constexpr int kLossOutputs = 8, kLossPlanes = 512;
 struct LossFinishArgs {
-    const float *part[kLossOutputs];   // (planes, nblk[i], 3)
-    float *coef[kLossOutputs];         // (planes, 4): { a, cI, cU, 0 }
+    const float *part[kLossOutputs];   // (planes, nblk[i], FORM::kSums)
+    float *coef[kLossOutputs];         // (planes, 4): { a, cI, cU, omega selector }
     int nblk[kLossOutputs];
     float weight[kLossOutputs];
-    int nout, planes;
+    int nout, planes, pixel, iou;      // PlainLoss: pixel = 0, iou = 1
     double npix;
     float *loss;
 };
-// One block.  Per output o and plane q:  I = sum p*y, U = sum (p + y), D = U - I + 1,
-//   loss = sum_o w_o [ sum_q bce_q / (planes * npix) + mean_q (1 - (I + 1) / D) ]
-// and the coefficients of d loss / d logit = a (p - y) + p (1 - p) (cI y + cU):
-//   a = w_o / (planes * npix),  cI = -(w_o / planes) (U + 2) / D^2,  cU = (w_o / planes) (I + 1) / D^2.
+// One block.  Per output o and plane q, with I and U the form's two IoU sums and D = U - I + 1:
+//   BCE term, also the reference's weighted losses as they execute (`reduce='none'` resolves to the mean, the weight
+//             cancels):                                   sum_q bce_q / (planes npix)
+//             per pixel (the weighted losses as published): mean_q (sum W bce)_q / (sum W)_q
+//   IoU term (when on): mean_q (1 - (I + 1) / D)
+//   loss = sum_o w_o (BCE term + IoU term)
+// and the coefficients of d loss / d logit (see the forms above):
+//   a = w_o / (planes npix), c[3] = 0;   per pixel: a = w_o / (planes (sum W)_q), c[3] = 1 (omega = W);
+//   cI = -(w_o / planes) (U + 2) / D^2,  cU = (w_o / planes) (I + 1) / D^2,  both 0 without the IoU term.
 // A wave per (output, plane) adds the partial sums (lanes stride over them, then a shuffle tree: a fixed order).
 __device__ __forceinline__ double wave_sum_f64(double v)
 {
@@ -125,30 +178,31 @@ __device__ __forceinline__ double wave_sum_f64(double v)
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+template <class FORM>
 __global__ __launch_bounds__(1024) void sod_loss_finish_kernel(LossFinishArgs a)
 {
+    constexpr int NS = FORM::kSums;
     __shared__ double term[kLossOutputs][kLossPlanes];
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6, nwave = blockDim.x >> 6;
+    const bool pixel = FORM::kWeighted && a.pixel, iou = !FORM::kWeighted || a.iou;
     for (int item = wv; item < a.nout * a.planes; item += nwave) {
         const int o = item / a.planes, q = item - o * a.planes;
-        const float *p = a.part[o] + (long)q * a.nblk[o] * 3;
-        double bce = 0.0, I = 0.0, U = 0.0;
-        for (int s = lane; s < a.nblk[o]; s += kWave) {
-            bce += (double)p[3 * s];
-            I += (double)p[3 * s + 1];
-            U += (double)p[3 * s + 2];
-        }
-        bce = wave_sum_f64(bce);
-        I = wave_sum_f64(I);
-        U = wave_sum_f64(U);
+        const float *p = a.part[o] + (long)q * a.nblk[o] * NS;
+        double v[NS] = {};
+        for (int s = lane; s < a.nblk[o]; s += kWave)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) v[j] += (double)p[NS * s + j];
+#pragma unroll
+        for (int j = 0; j < NS; ++j) v[j] = wave_sum_f64(v[j]);
         if (lane == 0) {
-            const double w = (double)a.weight[o], D = U - I + 1.0;
-            term[o][q] = w * (bce / ((double)a.planes * a.npix) + (1.0 - (I + 1.0) / D) / (double)a.planes);
+            const double w = (double)a.weight[o], planes = (double)a.planes, I = v[FORM::kI], U = v[FORM::kI + 1], D = U - I + 1.0;
+            const double bce = pixel ? v[1] / v[2] / planes : v[0] / (planes * a.npix);
+            term[o][q] = w * (bce + (iou ? (1.0 - (I + 1.0) / D) / planes : 0.0));
             float *c = a.coef[o] + 4 * (long)q;
-            c[0] = (float)(w / ((double)a.planes * a.npix));
-            c[1] = (float)(-(w / (double)a.planes) * (U + 2.0) / (D * D));
-            c[2] = (float)((w / (double)a.planes) * (I + 1.0) / (D * D));
-            c[3] = 0.f;
+            c[0] = (float)(w / (planes * (pixel ? v[2] : a.npix)));
+            c[1] = iou ? (float)(-(w / planes) * (U + 2.0) / (D * D)) : 0.f;
+            c[2] = iou ? (float)((w / planes) * (I + 1.0) / (D * D)) : 0.f;
+            c[3] = pixel ? 1.f : 0.f;
         }
     }
     __syncthreads();
@@ -160,25 +214,33 @@ __global__ __launch_bounds__(1024) void sod_loss_finish_kernel(LossFinishArgs a)
     }
 }
 
-__device__ __forceinline__ float loss_grad(float zz, float y, float ca, float ci, float cu)
+template <class FORM>
+__device__ __forceinline__ LossCoef loss_coef(const float *__restrict__ coef, const float *__restrict__ gscale, int plane)
+{
+    const float gs = gscale ? *gscale : 1.f;
+    return {gs * coef[4 * plane], gs * coef[4 * plane + 1], gs * coef[4 * plane + 2],
+            FORM::kWeighted && coef[4 * plane + 3] != 0.f};
+}
+template <class FORM>
+__device__ __forceinline__ float loss_grad(const FORM &f, long i, float zz, float y, const LossCoef &c)
 {
     float p, tail;
     sig_terms(zz, p, tail);
-    return ca * (p - y) + p * (1.f - p) * fmaf(ci, y, cu);
+    return f.grad(i, y, p, c);
 }
 
 // same resolution: one thread per pixel
+template <class FORM>
 __global__ __launch_bounds__(256) void sod_loss_grad_same_kernel(const float *__restrict__ z, const float *__restrict__ label,
                                                                 const float *__restrict__ coef,
                                                                 const float *__restrict__ gscale, float *__restrict__ gz,
-                                                                long npix)
+                                                                long npix, FORM f)
 {
     const int plane = blockIdx.y;
-    const float gs = gscale ? *gscale : 1.f;
-    const float ca = gs * coef[4 * plane], ci = gs * coef[4 * plane + 1], cu = gs * coef[4 * plane + 2];
+    const LossCoef c = loss_coef<FORM>(coef, gscale, plane);
     const long base = (long)plane * npix;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x)
-        gz[base + i] = loss_grad(z[base + i], label[base + i], ca, ci, cu);
+        gz[base + i] = loss_grad(f, base + i, z[base + i], label[base + i], c);
 }
 
 // resized output: the adjoint of the bilinear resize is separable, so the gradient at label resolution is formed ONCE per
@@ -196,20 +258,22 @@ __device__ __forceinline__ float tap_weight(const Tap &t, int i)
 }
 constexpr int kGradRows = 4;
 // rows[plane][Y][x] = sum over X of wx(X -> x) g(Y, X)
+template <class FORM>
 __global__ __launch_bounds__(256) void sod_loss_grad_rows_kernel(const float *__restrict__ z, const float *__restrict__ label,
                                                                 const float *__restrict__ coef,
                                                                 const float *__restrict__ gscale, float *__restrict__ rows,
-                                                                int h, int w, int H, int W)
+                                                                int h, int w, int H, int W, FORM f)
 {
     extern __shared__ float band[];               // [kGradRows][W]
     const int plane = blockIdx.y, yb = blockIdx.x * kGradRows;
-    const float gs = gscale ? *gscale : 1.f;
-    const float ca = gs * coef[4 * plane], ci = gs * coef[4 * plane + 1], cu = gs * coef[4 * plane + 2];
+    const LossCoef c = loss_coef<FORM>(coef, gscale, plane);
     const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    const float *zp = z + (long)plane * h * w, *yp = label + (long)plane * H * W;
+    const long base = (long)plane * H * W;
+    const float *zp = z + (long)plane * h * w;
     for (int e = threadIdx.x; e < kGradRows * W; e += blockDim.x) {
         const int r = e / W, X = e - r * W, Y = yb + r;
-        if (Y < H) band[e] = loss_grad(resized(zp, w, tap(Y, sy, h), tap(X, sx, w)), yp[(long)Y * W + X], ca, ci, cu);
+        const long i = base + (long)Y * W + X;
+        if (Y < H) band[e] = loss_grad(f, i, resized(zp, w, tap(Y, sy, h), tap(X, sx, w)), label[i], c);
     }
     __syncthreads();
     for (int e = threadIdx.x; e < kGradRows * w; e += blockDim.x) {
@@ -241,15 +305,11 @@ __global__ __launch_bounds__(256) void sod_loss_grad_cols_kernel(const float *__
     gz[i] = acc;
 }
 
-// ------------------------------------------------------------------------------------------------- weighted losses
-// structure_loss / wbce (utils/loss.py:14-42): the same passes with a per-pixel weight W = 1 + 5 |box_k(y) - y| and a
-// smoothed BCE target yhat = (1 - eps) y + eps / 2.  The weight depends on the label only: one map per loss call, shared by
-// the deep-supervision outputs (12 B per label pixel and output instead of 8, plus the map's own pass).
-//
-// weit = 1 + 5 |avg_pool2d(label, k, stride 1, pad k / 2) - label|, zero padding, divisor k * k (count_include_pad).  A
-// workgroup owns a 32 x 32 tile: the tile with its halo of r = k / 2 goes to LDS (zeros outside the image), row sums of k
-// neighbours into a second LDS band, then column sums of those -- every sum in a fixed order that depends on the pixel's
-// position only.
+// ------------------------------------------------------------------------------------------------- weight map
+// weit = 1 + 5 |avg_pool2d(label, k, stride 1, pad k / 2) - label| (utils/loss.py:22, 39), zero padding, divisor k * k
+// (count_include_pad): what WeightedLoss reads when the caller gives no weight.  A workgroup owns a 32 x 32 tile: the tile
+// with its halo of r = k / 2 goes to LDS (zeros outside the image), row sums of k neighbours into a second LDS band, then
+// column sums of those -- every sum in a fixed order that depends on the pixel's position only.
 constexpr int kWmapTile = 32, kWmapMaxK = 63;
 __global__ __launch_bounds__(256) void loss_weight_map_kernel(const float *__restrict__ label, float *__restrict__ weit, int H,
                                                              int W, int r)
@@ -280,165 +340,6 @@ __global__ __launch_bounds__(256) void loss_weight_map_kernel(const float *__res
         float s = 0.f;
         for (int d = 0; d < k; ++d) s += hs[(y + d) * kWmapTile + x];
         weit[base + (long)Y * W + X] = 1.f + 5.f * fabsf(s / kk - raw[(y + r) * side + x + r]);
-    }
-}
-
-// How the kernels below read the map: W = wadd + wmul * wmap[i] -- { 0, 1 } for the box-filter map above, { 1, 5 } for a
-// caller's `weight` tensor (utils/loss.py:24); and the BCE target yhat = ysc * y + yadd = (1 - eps) y + eps / 2.
-struct WLossForm {
-    float wadd, wmul, ysc, yadd;
-};
-
-// part[plane][blockIdx.x][5] = { sum bce(z, yhat), sum W bce, sum W, sum W p y, sum W (p + y) }  (y unsmoothed in the last two)
-template <bool SAME>
-__global__ __launch_bounds__(kLossThreads) void sod_wloss_sums_kernel(const float *__restrict__ z,
-                                                                     const float *__restrict__ label,
-                                                                     const float *__restrict__ wmap,
-                                                                     float *__restrict__ part, int h, int w, int H, int W,
-                                                                     WLossForm f)
-{
-    __shared__ float red[kLossThreads / kWave][5];
-    const int plane = blockIdx.y, nblk = gridDim.x;
-    const long npix = (long)H * W;
-    const float *zp = z + (long)plane * h * w, *yp = label + plane * npix, *wp = wmap + plane * npix;
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    float s[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (long i = (long)blockIdx.x * kLossThreads + threadIdx.x; i < npix; i += (long)nblk * kLossThreads) {
-        float zz;
-        if constexpr (SAME) {
-            zz = zp[i];
-        } else {
-            const int Y = (int)(i / W), X = (int)(i - (long)Y * W);
-            zz = resized(zp, w, tap(Y, sy, h), tap(X, sx, w));
-        }
-        const float y = yp[i], wt = fmaf(f.wmul, wp[i], f.wadd);
-        float p, tail;
-        sig_terms(zz, p, tail);
-        const float bce = fmaxf(zz, 0.f) - zz * fmaf(f.ysc, y, f.yadd) + tail;
-        s[0] += bce;
-        s[1] = fmaf(wt, bce, s[1]);
-        s[2] += wt;
-        s[3] = fmaf(wt, p * y, s[3]);
-        s[4] = fmaf(wt, p + y, s[4]);
-    }
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        s[j] = wave_sum(s[j]);
-        if (lane == 0) red[wv][j] = s[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        float t = 0.f;
-        for (int q = 0; q < kLossThreads / kWave; ++q) t += red[q][threadIdx.x];
-        part[((long)plane * nblk + blockIdx.x) * 5 + threadIdx.x] = t;
-    }
-}
-
-struct WLossFinishArgs {
-    const float *part[kLossOutputs];   // (planes, nblk[i], 5)
-    float *coef[kLossOutputs];         // (planes, 4): { a, cI, cU, omega selector }
-    int nblk[kLossOutputs];
-    float weight[kLossOutputs];
-    int nout, planes, pixel, iou;
-    double npix;
-    float *loss;
-};
-// One block, as sod_loss_finish_kernel.  Per output o and plane q, with I = sum W p y, U = sum W (p + y), D = U - I + 1:
-//   BCE term, the reference as it executes (`reduce='none'` resolves to the mean, the weight cancels): sum_q bce_q / (planes npix)
-//             per pixel (the published form):                                        mean_q (sum W bce)_q / (sum W)_q
-//   IoU term (when on): mean_q (1 - (I + 1) / D)
-// and the coefficients of d loss / d logit = a omega (p - yhat) + p (1 - p) W (cI y + cU):
-//   reference: omega = 1 (c[3] = 0), a = w_o / (planes npix);   per pixel: omega = W (c[3] = 1), a = w_o / (planes (sum W)_q);
-//   cI = -(w_o / planes) (U + 2) / D^2,  cU = (w_o / planes) (I + 1) / D^2,  both 0 without the IoU term.
-__global__ __launch_bounds__(1024) void sod_wloss_finish_kernel(WLossFinishArgs a)
-{
-    __shared__ double term[kLossOutputs][kLossPlanes];
-    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-    for (int item = wv; item < a.nout * a.planes; item += nwave) {
-        const int o = item / a.planes, q = item - o * a.planes;
-        const float *p = a.part[o] + (long)q * a.nblk[o] * 5;
-        double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int s = lane; s < a.nblk[o]; s += kWave)
-#pragma unroll
-            for (int j = 0; j < 5; ++j) v[j] += (double)p[5 * s + j];
-#pragma unroll
-        for (int j = 0; j < 5; ++j) v[j] = wave_sum_f64(v[j]);
-        if (lane == 0) {
-            const double w = (double)a.weight[o], planes = (double)a.planes, I = v[3], U = v[4], D = U - I + 1.0;
-            const double bce = a.pixel ? v[1] / v[2] / planes : v[0] / (planes * a.npix);
-            term[o][q] = w * (bce + (a.iou ? (1.0 - (I + 1.0) / D) / planes : 0.0));
-            float *c = a.coef[o] + 4 * (long)q;
-            c[0] = (float)(w / (planes * (a.pixel ? v[2] : a.npix)));
-            c[1] = a.iou ? (float)(-(w / planes) * (U + 2.0) / (D * D)) : 0.f;
-            c[2] = a.iou ? (float)((w / planes) * (I + 1.0) / (D * D)) : 0.f;
-            c[3] = a.pixel ? 1.f : 0.f;
-        }
-    }
-    __syncthreads();
-    if (wv == 0) {
-        double s = 0.0;
-        for (int item = lane; item < a.nout * a.planes; item += kWave) s += term[item / a.planes][item % a.planes];
-        s = wave_sum_f64(s);
-        if (lane == 0) *a.loss = (float)s;
-    }
-}
-
-struct WLossCoef {
-    float ca, ci, cu;
-    bool pixel;
-};
-__device__ __forceinline__ WLossCoef wloss_coef(const float *__restrict__ coef, const float *__restrict__ gscale, int plane)
-{
-    const float gs = gscale ? *gscale : 1.f;
-    return {gs * coef[4 * plane], gs * coef[4 * plane + 1], gs * coef[4 * plane + 2], coef[4 * plane + 3] != 0.f};
-}
-__device__ __forceinline__ float wloss_grad(float zz, float y, float wraw, const WLossCoef &c, const WLossForm &f)
-{
-    float p, tail;
-    sig_terms(zz, p, tail);
-    const float wt = fmaf(f.wmul, wraw, f.wadd);
-    return c.ca * (c.pixel ? wt : 1.f) * (p - fmaf(f.ysc, y, f.yadd)) + p * (1.f - p) * wt * fmaf(c.ci, y, c.cu);
-}
-
-// the weighted forms of sod_loss_grad_same_kernel / sod_loss_grad_rows_kernel (the columns kernel serves both)
-__global__ __launch_bounds__(256) void sod_wloss_grad_same_kernel(const float *__restrict__ z, const float *__restrict__ label,
-                                                                 const float *__restrict__ wmap,
-                                                                 const float *__restrict__ coef,
-                                                                 const float *__restrict__ gscale, float *__restrict__ gz,
-                                                                 long npix, WLossForm f)
-{
-    const int plane = blockIdx.y;
-    const WLossCoef c = wloss_coef(coef, gscale, plane);
-    const long base = (long)plane * npix;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x)
-        gz[base + i] = wloss_grad(z[base + i], label[base + i], wmap[base + i], c, f);
-}
-__global__ __launch_bounds__(256) void sod_wloss_grad_rows_kernel(const float *__restrict__ z, const float *__restrict__ label,
-                                                                 const float *__restrict__ wmap,
-                                                                 const float *__restrict__ coef,
-                                                                 const float *__restrict__ gscale, float *__restrict__ rows,
-                                                                 int h, int w, int H, int W, WLossForm f)
-{
-    extern __shared__ float band[];               // [kGradRows][W]
-    const int plane = blockIdx.y, yb = blockIdx.x * kGradRows;
-    const WLossCoef c = wloss_coef(coef, gscale, plane);
-    const float sy = (float)h / (float)H, sx = (float)w / (float)W;
-    const float *zp = z + (long)plane * h * w, *yp = label + (long)plane * H * W, *wp = wmap + (long)plane * H * W;
-    for (int e = threadIdx.x; e < kGradRows * W; e += blockDim.x) {
-        const int r = e / W, X = e - r * W, Y = yb + r;
-        if (Y < H)
-            band[e] = wloss_grad(resized(zp, w, tap(Y, sy, h), tap(X, sx, w)), yp[(long)Y * W + X], wp[(long)Y * W + X], c, f);
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < kGradRows * w; e += blockDim.x) {
-        const int r = e / w, x = e - r * w, Y = yb + r;
-        if (Y >= H) continue;
-        int X0, X1;
-        window(x, sx, W, X0, X1);
-        float acc = 0.f;
-        for (int X = X0; X <= X1; ++X) acc = fmaf(tap_weight(tap(X, sx, w), x), band[r * W + X], acc);
-        rows[((long)plane * H + Y) * w + x] = acc;
     }
 }
 
@@ -802,32 +703,36 @@ static std::vector<std::vector<int>> snake_bins(const int64_t *numel, int count,
 
 using namespace tramba;
 
-extern "C" int tramba_sod_loss_sums(const float *logits, const float *label, float *part, int planes, int h, int w,
-                                    int hout, int wout, int nblk, void *stream)
+// The loss entries come in pairs, tramba_sod_loss_* and tramba_sod_wloss_*: each pair is two wrappers that name themselves
+// (`who`, for the error texts) and pick the form over one implementation.
+template <class FORM>
+static int launch_loss_sums(const char *who, const FORM &f, const float *logits, const float *label, float *part, int planes, int h,
+                     int w, int hout, int wout, int nblk, void *stream)
 {
-    TRAMBA_CHECK(logits && label && part, "sod_loss_sums: null tensor");
-    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0 && hout > 0 && wout > 0 && nblk > 0, "sod_loss_sums: bad shape");
+    TRAMBA_CHECK(logits && label && part, "%s: null tensor", who);
+    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0 && hout > 0 && wout > 0 && nblk > 0, "%s: bad shape", who);
     const dim3 grid((unsigned)nblk, (unsigned)planes);
     if (h == hout && w == wout)
-        hipLaunchKernelGGL(sod_loss_sums_kernel<true>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, part,
-                           h, w, hout, wout);
+        hipLaunchKernelGGL((sod_loss_sums_kernel<true, FORM>), grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label,
+                           part, h, w, hout, wout, f);
     else
-        hipLaunchKernelGGL(sod_loss_sums_kernel<false>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, part,
-                           h, w, hout, wout);
+        hipLaunchKernelGGL((sod_loss_sums_kernel<false, FORM>), grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label,
+                           part, h, w, hout, wout, f);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
 
-extern "C" int tramba_sod_loss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs,
-                                      int nout, int planes, int64_t npix, float *loss, void *stream)
+static int launch_loss_finish(const char *who, bool weighted, const float *const *parts, const int *nblk, const float *weights,
+                       float *const *coefs, int nout, int planes, int64_t npix, int per_pixel, int with_iou, float *loss,
+                       void *stream)
 {
-    TRAMBA_CHECK(parts && nblk && coefs && loss, "sod_loss_finish: null argument");
-    TRAMBA_CHECK(nout > 0 && nout <= kLossOutputs, "sod_loss_finish: 1..%d outputs (got %d)", kLossOutputs, nout);
-    TRAMBA_CHECK(planes > 0 && planes <= kLossPlanes && npix > 0, "sod_loss_finish: 1..%d planes (got %d)", kLossPlanes, planes);
+    TRAMBA_CHECK(parts && nblk && coefs && loss, "%s: null argument", who);
+    TRAMBA_CHECK(nout > 0 && nout <= kLossOutputs, "%s: 1..%d outputs (got %d)", who, kLossOutputs, nout);
+    TRAMBA_CHECK(planes > 0 && planes <= kLossPlanes && npix > 0, "%s: 1..%d planes (got %d)", who, kLossPlanes, planes);
     LossFinishArgs a;
     for (int o = 0; o < kLossOutputs; ++o) {
         const bool on = o < nout;
-        TRAMBA_CHECK(!on || (parts[o] && coefs[o] && nblk[o] > 0), "sod_loss_finish: output %d: null table", o);
+        TRAMBA_CHECK(!on || (parts[o] && coefs[o] && nblk[o] > 0), "%s: output %d: null table", who, o);
         a.part[o] = on ? parts[o] : nullptr;
         a.coef[o] = on ? coefs[o] : nullptr;
         a.nblk[o] = on ? nblk[o] : 0;
@@ -835,9 +740,14 @@ extern "C" int tramba_sod_loss_finish(const float *const *parts, const int *nblk
     }
     a.nout = nout;
     a.planes = planes;
+    a.pixel = per_pixel != 0;
+    a.iou = with_iou != 0;
     a.npix = (double)npix;
     a.loss = loss;
-    hipLaunchKernelGGL(sod_loss_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    if (weighted)
+        hipLaunchKernelGGL(sod_loss_finish_kernel<WeightedLoss>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(sod_loss_finish_kernel<PlainLoss>, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -847,35 +757,56 @@ extern "C" size_t tramba_sod_loss_grad_workspace(int planes, int h, int w, int h
     return (h == hout && w == wout) ? 0 : (size_t)planes * (size_t)hout * (size_t)w * sizeof(float);
 }
 
-extern "C" int tramba_sod_loss_grad(const float *logits, const float *label, const float *coef, const float *gscale,
-                                    float *glogits, void *workspace, size_t workspace_bytes, int planes, int h, int w,
-                                    int hout, int wout, void *stream)
+template <class FORM>
+static int launch_loss_grad(const char *who, const FORM &f, const float *logits, const float *label, const float *coef,
+                     const float *gscale, float *glogits, void *workspace, size_t workspace_bytes, int planes, int h, int w,
+                     int hout, int wout, void *stream)
 {
-    TRAMBA_CHECK(logits && label && coef && glogits, "sod_loss_grad: null tensor");
-    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0, "sod_loss_grad: bad shape");
+    TRAMBA_CHECK(logits && label && coef && glogits, "%s: null tensor", who);
+    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0, "%s: bad shape", who);
     hipStream_t s = (hipStream_t)stream;
     if (h == hout && w == wout) {
         const long npix = (long)h * w;
         const unsigned gx = (unsigned)((npix + 1023) / 1024);
-        hipLaunchKernelGGL(sod_loss_grad_same_kernel, dim3(gx, (unsigned)planes), dim3(256), 0, s, logits, label, coef, gscale,
-                           glogits, npix);
+        hipLaunchKernelGGL(sod_loss_grad_same_kernel<FORM>, dim3(gx, (unsigned)planes), dim3(256), 0, s, logits, label, coef,
+                           gscale, glogits, npix, f);
     } else {
-        TRAMBA_CHECK(hout >= h && wout >= w, "sod_loss_grad: outputs are resized UP to the label (%dx%d -> %dx%d)", h, w, hout, wout);
-        TRAMBA_CHECK(wout <= 4096, "sod_loss_grad: label rows of at most 4096 pixels (got %d)", wout);
+        TRAMBA_CHECK(hout >= h && wout >= w, "%s: outputs are resized UP to the label (%dx%d -> %dx%d)", who, h, w, hout, wout);
+        TRAMBA_CHECK(wout <= 4096, "%s: label rows of at most 4096 pixels (got %d)", who, wout);
         TRAMBA_CHECK(workspace && workspace_bytes >= tramba_sod_loss_grad_workspace(planes, h, w, hout, wout),
-                     "sod_loss_grad: workspace of %zu bytes needed", tramba_sod_loss_grad_workspace(planes, h, w, hout, wout));
+                     "%s: workspace of %zu bytes needed", who, tramba_sod_loss_grad_workspace(planes, h, w, hout, wout));
         float *rows = (float *)workspace;
-        hipLaunchKernelGGL(sod_loss_grad_rows_kernel, dim3((unsigned)((hout + kGradRows - 1) / kGradRows), (unsigned)planes),
+        hipLaunchKernelGGL(sod_loss_grad_rows_kernel<FORM>, dim3((unsigned)((hout + kGradRows - 1) / kGradRows), (unsigned)planes),
                            dim3(256), (size_t)kGradRows * wout * sizeof(float), s, logits, label, coef, gscale, rows, h, w, hout,
-                           wout);
+                           wout, f);
         TRAMBA_LAUNCH_CHECK();
         const long total = (long)planes * h * w;
-        TRAMBA_CHECK((total + 255) / 256 < 2147483647L, "sod_loss_grad: too many workgroups");
+        TRAMBA_CHECK((total + 255) / 256 < 2147483647L, "%s: too many workgroups", who);
         hipLaunchKernelGGL(sod_loss_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows, glogits, h, w,
                            hout, total);
     }
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
+}
+
+extern "C" int tramba_sod_loss_sums(const float *logits, const float *label, float *part, int planes, int h, int w,
+                                    int hout, int wout, int nblk, void *stream)
+{
+    return launch_loss_sums("sod_loss_sums", PlainLoss{}, logits, label, part, planes, h, w, hout, wout, nblk, stream);
+}
+
+extern "C" int tramba_sod_loss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs,
+                                      int nout, int planes, int64_t npix, float *loss, void *stream)
+{
+    return launch_loss_finish("sod_loss_finish", false, parts, nblk, weights, coefs, nout, planes, npix, 0, 1, loss, stream);
+}
+
+extern "C" int tramba_sod_loss_grad(const float *logits, const float *label, const float *coef, const float *gscale,
+                                    float *glogits, void *workspace, size_t workspace_bytes, int planes, int h, int w,
+                                    int hout, int wout, void *stream)
+{
+    return launch_loss_grad("sod_loss_grad", PlainLoss{}, logits, label, coef, gscale, glogits, workspace, workspace_bytes, planes, h, w,
+                     hout, wout, stream);
 }
 
 extern "C" int tramba_loss_weight_map(const float *label, float *weit, int planes, int h, int w, int k, void *stream)
@@ -892,56 +823,29 @@ extern "C" int tramba_loss_weight_map(const float *label, float *weit, int plane
     return TRAMBA_OK;
 }
 
-static bool wloss_form(float eps, int weight_is_raw, WLossForm &f)
+// the form the two weighted entries that read the map are called with
+static int weighted_form(const char *who, const float *wmap, float eps, int weight_is_raw, WeightedLoss &f)
 {
-    if (!(eps >= 0.f && eps < 1.f)) return false;
-    f = weight_is_raw ? WLossForm{1.f, 5.f, 1.f - eps, 0.5f * eps} : WLossForm{0.f, 1.f, 1.f - eps, 0.5f * eps};
-    return true;
+    TRAMBA_CHECK(wmap, "%s: null tensor", who);
+    TRAMBA_CHECK(eps >= 0.f && eps < 1.f, "%s: label smoothing in [0, 1)", who);
+    f = weight_is_raw ? WeightedLoss{wmap, 1.f, 5.f, 1.f - eps, 0.5f * eps} : WeightedLoss{wmap, 0.f, 1.f, 1.f - eps, 0.5f * eps};
+    return TRAMBA_OK;
 }
 
 extern "C" int tramba_sod_wloss_sums(const float *logits, const float *label, const float *wmap, float *part, int planes,
                                      int h, int w, int hout, int wout, int nblk, float eps, int weight_is_raw, void *stream)
 {
-    TRAMBA_CHECK(logits && label && wmap && part, "sod_wloss_sums: null tensor");
-    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0 && hout > 0 && wout > 0 && nblk > 0, "sod_wloss_sums: bad shape");
-    WLossForm f;
-    TRAMBA_CHECK(wloss_form(eps, weight_is_raw, f), "sod_wloss_sums: label smoothing in [0, 1)");
-    const dim3 grid((unsigned)nblk, (unsigned)planes);
-    if (h == hout && w == wout)
-        hipLaunchKernelGGL(sod_wloss_sums_kernel<true>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, wmap,
-                           part, h, w, hout, wout, f);
-    else
-        hipLaunchKernelGGL(sod_wloss_sums_kernel<false>, grid, dim3(kLossThreads), 0, (hipStream_t)stream, logits, label, wmap,
-                           part, h, w, hout, wout, f);
-    TRAMBA_LAUNCH_CHECK();
-    return TRAMBA_OK;
+    WeightedLoss f;
+    if (const int e = weighted_form("sod_wloss_sums", wmap, eps, weight_is_raw, f)) return e;
+    return launch_loss_sums("sod_wloss_sums", f, logits, label, part, planes, h, w, hout, wout, nblk, stream);
 }
 
 extern "C" int tramba_sod_wloss_finish(const float *const *parts, const int *nblk, const float *weights, float *const *coefs,
                                        int nout, int planes, int64_t npix, int per_pixel, int with_iou, float *loss,
                                        void *stream)
 {
-    TRAMBA_CHECK(parts && nblk && coefs && loss, "sod_wloss_finish: null argument");
-    TRAMBA_CHECK(nout > 0 && nout <= kLossOutputs, "sod_wloss_finish: 1..%d outputs (got %d)", kLossOutputs, nout);
-    TRAMBA_CHECK(planes > 0 && planes <= kLossPlanes && npix > 0, "sod_wloss_finish: 1..%d planes (got %d)", kLossPlanes, planes);
-    WLossFinishArgs a;
-    for (int o = 0; o < kLossOutputs; ++o) {
-        const bool on = o < nout;
-        TRAMBA_CHECK(!on || (parts[o] && coefs[o] && nblk[o] > 0), "sod_wloss_finish: output %d: null table", o);
-        a.part[o] = on ? parts[o] : nullptr;
-        a.coef[o] = on ? coefs[o] : nullptr;
-        a.nblk[o] = on ? nblk[o] : 0;
-        a.weight[o] = on ? (weights ? weights[o] : 1.f) : 0.f;
-    }
-    a.nout = nout;
-    a.planes = planes;
-    a.pixel = per_pixel != 0;
-    a.iou = with_iou != 0;
-    a.npix = (double)npix;
-    a.loss = loss;
-    hipLaunchKernelGGL(sod_wloss_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-    TRAMBA_LAUNCH_CHECK();
-    return TRAMBA_OK;
+    return launch_loss_finish("sod_wloss_finish", true, parts, nblk, weights, coefs, nout, planes, npix, per_pixel, with_iou, loss,
+                       stream);
 }
 
 extern "C" size_t tramba_sod_wloss_grad_workspace(int planes, int h, int w, int hout, int wout)
@@ -953,33 +857,10 @@ extern "C" int tramba_sod_wloss_grad(const float *logits, const float *label, co
                                      const float *gscale, float *glogits, void *workspace, size_t workspace_bytes, int planes,
                                      int h, int w, int hout, int wout, float eps, int weight_is_raw, void *stream)
 {
-    TRAMBA_CHECK(logits && label && wmap && coef && glogits, "sod_wloss_grad: null tensor");
-    TRAMBA_CHECK(planes > 0 && planes <= 65535 && h > 0 && w > 0, "sod_wloss_grad: bad shape");
-    WLossForm f;
-    TRAMBA_CHECK(wloss_form(eps, weight_is_raw, f), "sod_wloss_grad: label smoothing in [0, 1)");
-    hipStream_t s = (hipStream_t)stream;
-    if (h == hout && w == wout) {
-        const long npix = (long)h * w;
-        const unsigned gx = (unsigned)((npix + 1023) / 1024);
-        hipLaunchKernelGGL(sod_wloss_grad_same_kernel, dim3(gx, (unsigned)planes), dim3(256), 0, s, logits, label, wmap, coef,
-                           gscale, glogits, npix, f);
-    } else {
-        TRAMBA_CHECK(hout >= h && wout >= w, "sod_wloss_grad: outputs are resized UP to the label (%dx%d -> %dx%d)", h, w, hout, wout);
-        TRAMBA_CHECK(wout <= 4096, "sod_wloss_grad: label rows of at most 4096 pixels (got %d)", wout);
-        TRAMBA_CHECK(workspace && workspace_bytes >= tramba_sod_wloss_grad_workspace(planes, h, w, hout, wout),
-                     "sod_wloss_grad: workspace of %zu bytes needed", tramba_sod_wloss_grad_workspace(planes, h, w, hout, wout));
-        float *rows = (float *)workspace;
-        hipLaunchKernelGGL(sod_wloss_grad_rows_kernel, dim3((unsigned)((hout + kGradRows - 1) / kGradRows), (unsigned)planes),
-                           dim3(256), (size_t)kGradRows * wout * sizeof(float), s, logits, label, wmap, coef, gscale, rows, h, w,
-                           hout, wout, f);
-        TRAMBA_LAUNCH_CHECK();
-        const long total = (long)planes * h * w;
-        TRAMBA_CHECK((total + 255) / 256 < 2147483647L, "sod_wloss_grad: too many workgroups");
-        hipLaunchKernelGGL(sod_loss_grad_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rows, glogits, h, w,
-                           hout, total);
-    }
-    TRAMBA_LAUNCH_CHECK();
-    return TRAMBA_OK;
+    WeightedLoss f;
+    if (const int e = weighted_form("sod_wloss_grad", wmap, eps, weight_is_raw, f)) return e;
+    return launch_loss_grad("sod_wloss_grad", f, logits, label, coef, gscale, glogits, workspace, workspace_bytes, planes, h, w, hout,
+                     wout, stream);
 }
 
 static int adam_step_impl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,

@@ -1108,52 +1108,75 @@ def _loss_nblk(npix):
     return max(1, min(256, (npix + 1023) // 1024))
 
 
-def sod_loss(outputs, label, weights=None):
-    """The deep-supervision loss of train.py:76-85 (every output resized to the label, BCE-with-logits + IoU, summed with
-    `weights`): outputs = fp32 (B, C, h_i, w_i) logit maps, label (B, C, H, W) f32.  Returns (loss 0-dim f32, coefs): coefs[i]
-    (B*C, 4) feeds `sod_loss_grad`.  One launch per output + one finishing block."""
-    _dev(label, *outputs)
-    if label.dtype != torch.float32 or any(o.dtype != torch.float32 for o in outputs):
-        raise TrambaHipError("sod_loss: fp32 logits and labels only")
+def _loss_check(what, tensors, label, maps):
+    """what both forms of the loss ask of their tensors.  maps: (wmap,) for the weighted form, () for the unweighted.
+    Returns planes, H, W of the label."""
+    _dev(label, *maps, *tensors)
+    if any(t.dtype != torch.float32 for t in (label, *maps, *tensors)):
+        raise TrambaHipError(f"{what}: fp32 logits, labels and weights only" if maps else f"{what}: fp32 logits and labels only")
+    for wmap in maps:
+        if wmap.shape != label.shape:
+            raise TrambaHipError(f"{what}: the weight map {tuple(wmap.shape)} does not match the label {tuple(label.shape)}")
     hh, ww = label.shape[-2:]
     planes = label.numel() // (hh * ww)
-    nout = len(outputs)
-    if not 0 < nout <= 8:
-        raise TrambaHipError(f"sod_loss: 1..8 outputs, got {nout}")
-    nblk = _loss_nblk(hh * ww)
-    stream = _stream()
-    parts = torch.empty((nout, planes, nblk, 3), dtype=torch.float32, device=label.device)
-    coefs = torch.empty((nout, planes, 4), dtype=torch.float32, device=label.device)
-    for i, o in enumerate(outputs):
+    for i, o in enumerate(tensors):
         h, w = o.shape[-2:]
         if o.numel() != planes * h * w or h > hh or w > ww:
-            raise TrambaHipError(f"sod_loss: output {i} {tuple(o.shape)} does not match the label {tuple(label.shape)}")
-        _check(lib().tramba_sod_loss_sums(_ptr(o), _ptr(label), parts[i].data_ptr(), planes, h, w, hh, ww, nblk, stream),
-               "sod_loss_sums")
+            raise TrambaHipError(f"{what}: output {i} {tuple(o.shape)} does not match the label {tuple(label.shape)}")
+    return planes, hh, ww
+
+
+def _sod_loss(what, outputs, label, maps, weights, sums_form=(), finish_form=()):
+    """tramba_<what>_sums per output, then tramba_<what>_finish: `sod_loss` with 3 sums per block and plane, `sod_wloss`
+    with 5 and the form arguments its two entries take after the shapes"""
+    nout = len(outputs)
+    if not 0 < nout <= 8:
+        raise TrambaHipError(f"{what}: 1..8 outputs, got {nout}")
+    planes, hh, ww = _loss_check(what, outputs, label, maps)
+    nblk = _loss_nblk(hh * ww)
+    stream = _stream()
+    parts = torch.empty((nout, planes, nblk, 5 if maps else 3), dtype=torch.float32, device=label.device)
+    coefs = torch.empty((nout, planes, 4), dtype=torch.float32, device=label.device)
+    sums, finish = getattr(lib(), f"tramba_{what}_sums"), getattr(lib(), f"tramba_{what}_finish")
+    for i, o in enumerate(outputs):
+        h, w = o.shape[-2:]
+        _check(sums(_ptr(o), _ptr(label), *map(_ptr, maps), parts[i].data_ptr(), planes, h, w, hh, ww, nblk, *sums_form, stream),
+               f"{what}_sums")
     loss = torch.empty((), dtype=torch.float32, device=label.device)
     pp = (ctypes.c_void_p * nout)(*[parts[i].data_ptr() for i in range(nout)])
     cc = (ctypes.c_void_p * nout)(*[coefs[i].data_ptr() for i in range(nout)])
     nb = (ctypes.c_int * nout)(*([nblk] * nout))
     wt = None if weights is None else (ctypes.c_float * nout)(*[float(w) for w in weights])
-    _check(lib().tramba_sod_loss_finish(pp, nb, wt, cc, nout, planes, hh * ww, _ptr(loss), stream), "sod_loss_finish")
+    _check(finish(pp, nb, wt, cc, nout, planes, hh * ww, *finish_form, _ptr(loss), stream), f"{what}_finish")
     return loss, coefs
+
+
+def _sod_loss_grad(what, output, label, maps, coef, gscale, form=()):
+    """tramba_<what> for `sod_loss_grad` and `sod_wloss_grad`, the latter with its weight map and form arguments"""
+    planes, hh, ww = _loss_check(what, (output,), label, maps)
+    _dev(coef, gscale)
+    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1):
+        raise TrambaHipError(f"{what}: the incoming gradient must be one fp32 scalar")
+    h, w = output.shape[-2:]
+    g = torch.empty_like(output)
+    nbytes = getattr(lib(), f"tramba_{what}_workspace")(planes, h, w, hh, ww)
+    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=output.device) if nbytes else None
+    _check(getattr(lib(), f"tramba_{what}")(_ptr(output), _ptr(label), *map(_ptr, maps), _ptr(coef), _ptr(gscale), _ptr(g),
+                                            _ptr(ws), nbytes, planes, h, w, hh, ww, *form, _stream()), what)
+    return g
+
+
+def sod_loss(outputs, label, weights=None):
+    """The deep-supervision loss of train.py:76-85 (every output resized to the label, BCE-with-logits + IoU, summed with
+    `weights`): outputs = fp32 (B, C, h_i, w_i) logit maps, label (B, C, H, W) f32.  Returns (loss 0-dim f32, coefs): coefs[i]
+    (B*C, 4) feeds `sod_loss_grad`.  One launch per output + one finishing block."""
+    return _sod_loss("sod_loss", outputs, label, (), weights)
 
 
 def sod_loss_grad(output, label, coef, gscale=None):
     """d loss / d output for one output of `sod_loss` (coef = its row of the coefficient table), times the device scalar
     `gscale` (the gradient arriving at the loss)."""
-    _dev(output, label, coef, gscale)
-    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1):
-        raise TrambaHipError("sod_loss_grad: the incoming gradient must be one fp32 scalar")
-    hh, ww = label.shape[-2:]
-    h, w = output.shape[-2:]
-    planes = label.numel() // (hh * ww)
-    g = torch.empty_like(output)
-    nbytes = lib().tramba_sod_loss_grad_workspace(planes, h, w, hh, ww)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=output.device) if nbytes else None
-    _check(lib().tramba_sod_loss_grad(_ptr(output), _ptr(label), _ptr(coef), _ptr(gscale), _ptr(g), _ptr(ws), nbytes, planes, h, w,
-                                      hh, ww, _stream()), "sod_loss_grad")
-    return g
+    return _sod_loss_grad("sod_loss_grad", output, label, (), coef, gscale)
 
 
 def loss_weight_map(label, k):
@@ -1169,62 +1192,18 @@ def loss_weight_map(label, k):
     return weit
 
 
-def _wloss_check(what, tensors, label, wmap):
-    _dev(label, wmap, *tensors)
-    if label.dtype != torch.float32 or wmap.dtype != torch.float32 or any(o.dtype != torch.float32 for o in tensors):
-        raise TrambaHipError(f"{what}: fp32 logits, labels and weights only")
-    if wmap.shape != label.shape:
-        raise TrambaHipError(f"{what}: the weight map {tuple(wmap.shape)} does not match the label {tuple(label.shape)}")
-
-
 def sod_wloss(outputs, label, wmap, weights=None, eps=0.0, per_pixel=False, with_iou=True, weight_is_raw=False):
     """`sod_loss` for the weighted losses of utils/loss.py:14-42 (structure_loss: eps = 0.001, with_iou; wbce: eps = 0, no IoU
     term): wmap (B, C, H, W) f32 from `loss_weight_map`, or the caller's `weight` tensor with weight_is_raw (W = 1 + 5 wmap).
     per_pixel: the BCE term weighted pixel by pixel (the published form) instead of the reference as it executes (batch-mean
     BCE).  Returns (loss, coefs) as `sod_loss`; coefs feeds `sod_wloss_grad`."""
-    _wloss_check("sod_wloss", outputs, label, wmap)
-    hh, ww = label.shape[-2:]
-    planes = label.numel() // (hh * ww)
-    nout = len(outputs)
-    if not 0 < nout <= 8:
-        raise TrambaHipError(f"sod_wloss: 1..8 outputs, got {nout}")
-    nblk = _loss_nblk(hh * ww)
-    stream = _stream()
-    parts = torch.empty((nout, planes, nblk, 5), dtype=torch.float32, device=label.device)
-    coefs = torch.empty((nout, planes, 4), dtype=torch.float32, device=label.device)
-    for i, o in enumerate(outputs):
-        h, w = o.shape[-2:]
-        if o.numel() != planes * h * w or h > hh or w > ww:
-            raise TrambaHipError(f"sod_wloss: output {i} {tuple(o.shape)} does not match the label {tuple(label.shape)}")
-        _check(lib().tramba_sod_wloss_sums(_ptr(o), _ptr(label), _ptr(wmap), parts[i].data_ptr(), planes, h, w, hh, ww, nblk,
-                                           float(eps), int(bool(weight_is_raw)), stream), "sod_wloss_sums")
-    loss = torch.empty((), dtype=torch.float32, device=label.device)
-    pp = (ctypes.c_void_p * nout)(*[parts[i].data_ptr() for i in range(nout)])
-    cc = (ctypes.c_void_p * nout)(*[coefs[i].data_ptr() for i in range(nout)])
-    nb = (ctypes.c_int * nout)(*([nblk] * nout))
-    wt = None if weights is None else (ctypes.c_float * nout)(*[float(w) for w in weights])
-    _check(lib().tramba_sod_wloss_finish(pp, nb, wt, cc, nout, planes, hh * ww, int(bool(per_pixel)), int(bool(with_iou)),
-                                         _ptr(loss), stream), "sod_wloss_finish")
-    return loss, coefs
+    return _sod_loss("sod_wloss", outputs, label, (wmap,), weights, (float(eps), int(bool(weight_is_raw))),
+                     (int(bool(per_pixel)), int(bool(with_iou))))
 
 
 def sod_wloss_grad(output, label, wmap, coef, gscale=None, eps=0.0, weight_is_raw=False):
     """d loss / d output for one output of `sod_wloss` (the same eps / weight_is_raw), times the device scalar `gscale`."""
-    _wloss_check("sod_wloss_grad", (output,), label, wmap)
-    _dev(coef, gscale)
-    if gscale is not None and (gscale.dtype != torch.float32 or gscale.numel() != 1):
-        raise TrambaHipError("sod_wloss_grad: the incoming gradient must be one fp32 scalar")
-    hh, ww = label.shape[-2:]
-    h, w = output.shape[-2:]
-    planes = label.numel() // (hh * ww)
-    if output.numel() != planes * h * w or h > hh or w > ww:
-        raise TrambaHipError(f"sod_wloss_grad: output {tuple(output.shape)} does not match the label {tuple(label.shape)}")
-    g = torch.empty_like(output)
-    nbytes = lib().tramba_sod_wloss_grad_workspace(planes, h, w, hh, ww)
-    ws = torch.empty((nbytes // 4,), dtype=torch.float32, device=output.device) if nbytes else None
-    _check(lib().tramba_sod_wloss_grad(_ptr(output), _ptr(label), _ptr(wmap), _ptr(coef), _ptr(gscale), _ptr(g), _ptr(ws), nbytes,
-                                       planes, h, w, hh, ww, float(eps), int(bool(weight_is_raw)), _stream()), "sod_wloss_grad")
-    return g
+    return _sod_loss_grad("sod_wloss_grad", output, label, (wmap,), coef, gscale, (float(eps), int(bool(weight_is_raw))))
 
 
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay=0.0):

@@ -49,20 +49,31 @@ def _resize_bilinear(o, size):
 class _SodLossHIP(torch.autograd.Function):
     """The whole loss of train.py:76-85 in the library: three sums per image and output in one pass each (the resized logit
     map is never stored), one finishing block, and in the backward one gather per output that lands on the output's own
-    resolution.  ~10 launches where the framework issued ~140."""
+    resolution.  ~10 launches where the framework issued ~140.
+    With a weight map the weighted losses through the same passes (five sums): `wmap` is the caller's (one launch per loss
+    call, shared by the outputs) and form = (eps, per_pixel, with_iou, weight_is_raw).  wmap None: no map is formed or read."""
 
     @staticmethod
-    def forward(ctx, label, weights, *outs):
-        loss, coefs = hip.sod_loss(outs, label, weights)
-        ctx.save_for_backward(label, coefs, *outs)
+    def forward(ctx, label, wmap, weights, form, *outs):
+        if wmap is None:
+            loss, coefs = hip.sod_loss(outs, label, weights)
+        else:
+            eps, per_pixel, with_iou, raw = form
+            loss, coefs = hip.sod_wloss(outs, label, wmap, weights, eps, per_pixel, with_iou, raw)
+            ctx.form = (eps, raw)
+        ctx.save_for_backward(label, wmap, coefs, *outs)
         return loss
 
     @staticmethod
     def backward(ctx, gl):
-        label, coefs, *outs = ctx.saved_tensors
+        label, wmap, coefs, *outs = ctx.saved_tensors
         gl = gl.to(torch.float32).contiguous()
-        return (None, None) + tuple(hip.sod_loss_grad(o, label, coefs[i], gl) if ctx.needs_input_grad[2 + i] else None
-                                    for i, o in enumerate(outs))
+
+        def grad(o, coef):
+            if wmap is None:
+                return hip.sod_loss_grad(o, label, coef, gl)
+            return hip.sod_wloss_grad(o, label, wmap, coef, gl, *ctx.form)
+        return (None,) * 4 + tuple(grad(o, coefs[i]) if ctx.needs_input_grad[4 + i] else None for i, o in enumerate(outs))
 
 
 def _loss_on_device(outputs, label):
@@ -74,25 +85,36 @@ def _loss_on_device(outputs, label):
             and (label.shape[-1] <= 4096 or all(o.shape[-2:] == label.shape[-2:] for o in outputs)))
 
 
+def _device_loss(outputs, label, wmap, loss_weights, form=None):
+    weights = None if loss_weights is None else tuple(float(w) for w in loss_weights)
+    return _SodLossHIP.apply(label, wmap, weights, form, *[o.float().contiguous() for o in outputs])
+
+
+def _composed_loss(outputs, label, dtype, loss_weights, term):
+    """host tensors / shapes the kernels refuse: term(output in `dtype`, at label size), summed with the loss weights"""
+    h, w = label.shape[-2:]
+    total = None
+    for i, o in enumerate(outputs):
+        o = o.to(dtype)
+        if o.shape[-2:] != (h, w):
+            o = _resize_bilinear(o, (h, w))
+        t = term(o)
+        if loss_weights is not None:
+            t = t * loss_weights[i]
+        total = t if total is None else total + t
+    return total
+
+
 def tramba_loss(outputs, label, loss_weights=None):
     """Sum over the deep-supervision outputs (3 for Tramba-R, 4 otherwise) of BCE-with-logits + IoU."""
     outputs = list(outputs)
     if loss_weights is not None and len(loss_weights) != len(outputs):
         raise ValueError(f"tramba_loss: {len(loss_weights)} loss weights for {len(outputs)} outputs")
     if _loss_on_device(outputs, label):
-        weights = None if loss_weights is None else tuple(float(w) for w in loss_weights)
-        return _SodLossHIP.apply(label.float().contiguous(), weights, *[o.float().contiguous() for o in outputs])
-    h, w = label.shape[-2:]
-    total = None
-    for i, o in enumerate(outputs):
-        o = o.float()
-        if o.shape[-2:] != (h, w):
-            o = _resize_bilinear(o, (h, w))
-        term = F.binary_cross_entropy_with_logits(o, label) + iou_loss(o, label)
-        if loss_weights is not None:
-            term = term * loss_weights[i]
-        total = term if total is None else total + term
-    return total
+        return _device_loss(outputs, label.float().contiguous(), None, loss_weights)
+    # the outputs in fp32 against the label as it is
+    return _composed_loss(outputs, label, torch.float32, loss_weights,
+                          lambda o: F.binary_cross_entropy_with_logits(o, label) + iou_loss(o, label))
 
 
 # ----------------------------------------------------------------------------- structure loss / weighted BCE
@@ -102,27 +124,6 @@ def tramba_loss(outputs, label, loss_weights=None):
 # bce="pixel" weights the BCE pixel by pixel, the loss as published (F3Net).
 _WLOSS_KINDS = {"structure": (31, 0.001, True), "wbce": (15, 0.0, False)}      # kind: (box window, label smoothing, IoU term)
 _WLOSS_READINGS = ("reference", "pixel")
-
-
-class _SodWLossHIP(torch.autograd.Function):
-    """`_SodLossHIP` for the weighted losses: five sums per image and output in one pass each, one finishing block, one
-    gradient pass per output; the weight map is the caller's (one launch per loss call, shared by the outputs)."""
-
-    @staticmethod
-    def forward(ctx, label, wmap, form, *outs):
-        weights, eps, per_pixel, with_iou, raw = form
-        loss, coefs = hip.sod_wloss(outs, label, wmap, weights, eps, per_pixel, with_iou, raw)
-        ctx.save_for_backward(label, wmap, coefs, *outs)
-        ctx.form = (eps, raw)
-        return loss
-
-    @staticmethod
-    def backward(ctx, gl):
-        label, wmap, coefs, *outs = ctx.saved_tensors
-        gl = gl.to(torch.float32).contiguous()
-        eps, raw = ctx.form
-        return (None, None, None) + tuple(hip.sod_wloss_grad(o, label, wmap, coefs[i], gl, eps, raw)
-                                          if ctx.needs_input_grad[3 + i] else None for i, o in enumerate(outs))
 
 
 def _weighted_term(o, label, weit, eps, with_iou, per_pixel):
@@ -153,29 +154,17 @@ def _weighted_loss(kind, bce, outputs, label, weight=None, loss_weights=None):
     if _loss_on_device(outputs, label) and (weight is None or (weight.is_cuda and weight.shape == label.shape)):
         lab = label.float().contiguous()
         wmap = hip.loss_weight_map(lab, k) if weight is None else weight.detach().float().contiguous()
-        form = (None if loss_weights is None else tuple(float(w) for w in loss_weights), eps, per_pixel, with_iou,
-                weight is not None)
-        return _SodWLossHIP.apply(lab, wmap, form, *[o.float().contiguous() for o in outputs])
+        return _device_loss(outputs, lab, wmap, loss_weights, (eps, per_pixel, with_iou, weight is not None))
     # host tensors / shapes the kernels refuse: the reference's own composition.  The LABEL picks the precision, as
     # tramba_loss's .float() does: fp64 only when the label is fp64 (fp64 logits against an fp32 label compute in fp32),
     # fp32 for every other label dtype, bf16 logits included
     dtype = torch.float64 if label.dtype == torch.float64 else torch.float32
     label = label.to(dtype)
-    h, w = label.shape[-2:]
     if weight is None:
         weit = 1 + 5 * torch.abs(F.avg_pool2d(label, kernel_size=k, stride=1, padding=k // 2) - label)
     else:
         weit = 1 + 5 * weight.to(dtype)
-    total = None
-    for i, o in enumerate(outputs):
-        o = o.to(dtype)
-        if o.shape[-2:] != (h, w):
-            o = _resize_bilinear(o, (h, w))
-        term = _weighted_term(o, label, weit, eps, with_iou, per_pixel)
-        if loss_weights is not None:
-            term = term * loss_weights[i]
-        total = term if total is None else total + term
-    return total
+    return _composed_loss(outputs, label, dtype, loss_weights, lambda o: _weighted_term(o, label, weit, eps, with_iou, per_pixel))
 
 
 def structure_loss(pred, mask, weight=None, bce="reference"):
