@@ -37,6 +37,10 @@
  *   tramba_patch_conv_wgrad_cl  weight + bias gradient
  *   tramba_patch_embed_ln       OverlapPatchEmbed (stage 1) / PatchEmbed + their LayerNorm
  *                                                               Models/encoder/pvtv2_encoder.py:159-199, swin_encoder.py:413-450
+ *   tramba_conv_affine_cl       Bottleneck conv + bn (+ shortcut, ReLU), downsample conv + bn
+ *                                                               Models/encoder/resnet_encoder.py:62-110
+ *   tramba_stem7_affine_relu_pool  ResNet conv1 + bn1 + relu + max_pool2d
+ *                                                               Models/encoder/resnet_encoder.py:62-110
  *   tramba_conv3x3s2_cl /       patch_embed + downsample convs  Models/vmamba.py:454,481-486
  *   tramba_stem_conv_ln_gelu
  *   tramba_resize_table /       get_transform(S, 'Test'): Resize + ToTensor + Normalize
@@ -752,6 +756,30 @@ int tramba_patch_conv_wgrad_cl(const void *gy, const void *x, float *work, size_
 int tramba_patch_embed_ln(const void *img, const float *w, const float *bias, const float *ln_w, const float *ln_b,
                           void *y, int batch, int h, int wd, int k, int stride, int pad, int cout, float eps,
                           int img_dtype, int dtype, void *stream);
+
+/* ------------------------------------------------------------------ convolutions of the ResNet-50 encoder (inference) */
+/* A bottleneck convolution with its eval-mode batch norm, shortcut and ReLU in one launch: conv1 / conv2 / conv3 of
+ * Bottleneck.forward and the `downsample` branch (Models/encoder/resnet_encoder.py:62-110).  With t = (b, oi, oj) and
+ * k = (di ksize + dj) Cin + c:
+ *     y[t, co] = act( scale[co] * sum_k X[t, k] w[co, k] + shift[co] + residual[t, co] )
+ * x (B, Hin, Win, Cin) channels-last; w K-major (Cout, ksize, ksize, Cin) = reference weight.permute(0,2,3,1), same dtype as
+ * x and NOT rescaled; scale / shift (Cout) f32 or NULL (1 / 0), for a batch norm scale = gamma / sqrt(var + eps) and
+ * shift = beta - mean * scale; residual (B, Ho, Wo, Cout) in dtype or NULL; relu 0 / 1; ksize 1 or 3, stride 1 or 2,
+ * pad = ksize / 2, Ho = (Hin + 2 pad - ksize) / stride + 1.  bf16 / fp16, Cin % 64 == 0, Cout % 8 == 0, x / w / residual / y
+ * 16-byte aligned, the input map below 2^31 bytes.  f32 accumulation on the matrix cores and an f32 epilogue, one rounding
+ * at the store.  Two forms chosen from (M, K): waves own row blocks (tall maps), or the waves of a workgroup split K and
+ * their partial sums are added in wave order (short, deep maps).  No atomics, no workspace, no allocation or
+ * synchronisation (capturable, bitwise reproducible). */
+int tramba_conv_affine_cl(const void *x, const void *w, const float *scale, const float *shift, const void *residual, void *y,
+                          int batch, int hin, int win, int cin, int cout, int ksize, int stride, int relu, int dtype,
+                          void *stream);
+/* The ResNet stem: conv1 (7x7 / stride 2 / pad 3, 3 -> 64, no bias) + bn1 + ReLU + max_pool2d(3, 2, 1) of ResNet.forward
+ * (Models/encoder/resnet_encoder.py:62-110).  img (B, 3, H, W) NCHW in f32 or `dtype`; w (64, 3, 7, 7) f32 reference layout;
+ * scale / shift (64) f32 (the folded batch norm); y (B, Hp, Wp, 64) channels-last bf16 / fp16 with Hc = (H - 1) / 2 + 1,
+ * Hp = (Hc - 1) / 2 + 1.  The half-resolution map is never written; the pool's padding is excluded from the max.
+ * Convolution, affine and max in f32, one rounding at the store. */
+int tramba_stem7_affine_relu_pool(const void *img, const float *w, const float *scale, const float *shift, void *y, int batch,
+                                  int h, int wd, int img_dtype, int dtype, void *stream);
 
 #ifdef __cplusplus
 }

@@ -206,10 +206,12 @@ def set_library_convolutions(model, enabled=True):
     PVT's spatial-reduction convs (`hip.patch_conv_cl`), its patch embeddings (`hip.patch_embed_ln` on the image,
     `hip.conv3x3s2_cl` on the channels-last maps) and Swin's patch embedding (`hip.patch_embed_ln`).  Returns the number of
     modules switched.  A module still calls `_conv` for fp32 activations, with autograd on and for shapes the kernels do
-    not take."""
+    not take.  A Tramba-R model's `ResNet` encoder counts as one module: its stem runs on `hip.stem7_affine_relu_pool` and
+    the bottlenecks of layer1..3 on `hip.conv_affine_cl` (models.ResNet.features_cl)."""
+    from .models import ResNet
     count = 0
     for m in model.modules():
-        if isinstance(m, (_OverlapPatchEmbed, _SwinPatchEmbed)) or (isinstance(m, _PvtAttention) and m.sr_ratio > 1):
+        if isinstance(m, (_OverlapPatchEmbed, _SwinPatchEmbed, ResNet)) or (isinstance(m, _PvtAttention) and m.sr_ratio > 1):
             m.library_convolutions = bool(enabled)
             count += 1
     return count

@@ -142,6 +142,8 @@ SIGNATURES = {
     "tramba_patch_conv_wgrad_work": (ctypes.c_size_t, [c_int] * 6),
     "tramba_patch_conv_wgrad_cl": (c_int, [c_vp] * 3 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
     "tramba_patch_embed_ln": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_f, c_int, c_int, c_vp]),
+    "tramba_conv_affine_cl": (c_int, [c_vp] * 6 + [c_int] * 9 + [c_vp]),
+    "tramba_stem7_affine_relu_pool": (c_int, [c_vp] * 5 + [c_int] * 5 + [c_vp]),
 }
 
 _lib = None
@@ -1890,4 +1892,76 @@ def patch_embed_ln(img, w, bias, ln_w, ln_b, eps, stride, pad, out_dtype):
     y = torch.empty((bb, max(ho, 0), max(wo, 0), cout), dtype=out_dtype, device=img.device)
     _check(lib().tramba_patch_embed_ln(_ptr(img), _ptr(w), _ptr(bias), _ptr(ln_w), _ptr(ln_b), _ptr(y), bb, h, wd, k, stride, pad,
                                        cout, eps, _DT[img.dtype], _DT[out_dtype], _stream()), "patch_embed_ln")
+    return y
+
+
+# ----------------------------------------------------------------------------- ResNet-50 encoder convolutions
+def conv_out_size(n, ksize, stride):
+    """output extent of a convolution with pad = ksize // 2 along an axis of n pixels"""
+    return (n + 2 * (ksize // 2) - ksize) // stride + 1
+
+
+def stem7_pool_out_size(n):
+    """output extent of conv(7, stride 2, pad 3) followed by max_pool(3, stride 2, pad 1) along an axis of n pixels"""
+    return (conv_out_size(n, 7, 2) - 1) // 2 + 1
+
+
+def conv_affine_supported(dtype, h, w, cin, cout, ksize, stride):
+    """the argument checks of tramba_conv_affine_cl that depend on the layer and its map (batch 1), without the library"""
+    return (dtype in _ATTN_DTYPES and ksize in (1, 3) and stride in (1, 2) and h > 0 and w > 0 and cin > 0 and cin % 64 == 0
+            and cout > 0 and cout % 8 == 0 and h * w * cin * 2 < 2 ** 31 and cout * ksize * ksize * cin * 2 < 2 ** 31
+            and (cout + 63) // 64 <= 65535)
+
+
+def conv_affine_cl(x, w_kmajor, scale, shift, residual=None, relu=True, ksize=None, stride=1):
+    """x: (B, H, W, Cin) bf16/f16; w_kmajor: (Cout, k, k, Cin) = weight.permute(0,2,3,1), same dtype, not rescaled; scale, shift:
+    (Cout) f32 or None (1 / 0); residual: (B, Ho, Wo, Cout) in x's dtype or None -> act(scale * conv(x) + shift + residual) as
+    (B, Ho, Wo, Cout), pad = k // 2, Ho = (H + 2 pad - k) // stride + 1; f32 throughout, one rounding."""
+    _dev(x, w_kmajor, scale, shift, residual)
+    if x.dim() != 4 or w_kmajor.dim() != 4 or w_kmajor.dtype != x.dtype or w_kmajor.shape[1] != w_kmajor.shape[2] \
+            or w_kmajor.shape[3] != x.shape[3] or (ksize is not None and ksize != w_kmajor.shape[1]):
+        raise TrambaHipError(f"conv_affine_cl: need x (B, H, W, Cin) and w (Cout, k, k, Cin) of one dtype"
+                             f"{'' if ksize is None else f' with k = {ksize}'}, got {tuple(x.shape)} {x.dtype} "
+                             f"{tuple(w_kmajor.shape)} {w_kmajor.dtype}")
+    bb, h, wd, cin = x.shape
+    cout, k = w_kmajor.shape[0], w_kmajor.shape[1]
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (cout,)):
+            raise TrambaHipError(f"conv_affine_cl: {name} must be float32 ({cout},)")
+    if k not in (1, 3) or stride not in (1, 2):
+        raise TrambaHipError(f"conv_affine_cl: ksize = {k} must be 1 or 3 and stride = {stride} 1 or 2")
+    ho, wo = conv_out_size(h, k, stride), conv_out_size(wd, k, stride)
+    if residual is not None and (residual.dtype != x.dtype or tuple(residual.shape) != (bb, ho, wo, cout)):
+        raise TrambaHipError(f"conv_affine_cl: residual must be {x.dtype} {(bb, ho, wo, cout)}, got {residual.dtype} "
+                             f"{tuple(residual.shape)}")
+    if (bb * h * wd * cin * 2) >= 2 ** 31:
+        raise TrambaHipError("conv_affine_cl: input map beyond 32-bit byte offsets")
+    y = torch.empty((bb, ho, wo, cout), dtype=x.dtype, device=x.device)
+    _check(lib().tramba_conv_affine_cl(_ptr(x), _ptr(w_kmajor), _ptr(scale), _ptr(shift), _ptr(residual), _ptr(y), bb, h, wd,
+                                       cin, cout, k, stride, int(bool(relu)), dt(x), _stream()), "conv_affine_cl")
+    return y
+
+
+def stem7_pool_supported(out_dtype, h, w):
+    """the argument checks of tramba_stem7_affine_relu_pool that depend on the image size, without the library"""
+    return out_dtype in _ATTN_DTYPES and h > 0 and w > 0 and (stem7_pool_out_size(h) + 3) // 4 <= 65535 and 3 * h * w < 9e18
+
+
+def stem7_affine_relu_pool(img, w, scale, shift, out_dtype):
+    """img: (B, 3, H, W) NCHW f32 or out_dtype; w: (64, 3, 7, 7) f32; scale, shift: (64) f32 -> max_pool(relu(scale * conv(img)
+    + shift), 3, 2, 1) as (B, Hp, Wp, 64) out_dtype, the 7x7 / stride 2 / pad 3 convolution; f32 throughout, one rounding."""
+    _dev(img, w, scale, shift)
+    if img.dim() != 4 or img.shape[1] != 3 or tuple(w.shape) != (64, 3, 7, 7):
+        raise TrambaHipError(f"stem7_affine_relu_pool: need img (B, 3, H, W) and w (64, 3, 7, 7), got {tuple(img.shape)} "
+                             f"{tuple(w.shape)}")
+    for name, t in (("w", w), ("scale", scale), ("shift", shift)):
+        if t.dtype != torch.float32 or (name != "w" and tuple(t.shape) != (64,)):
+            raise TrambaHipError(f"stem7_affine_relu_pool: {name} must be float32" + ("" if name == "w" else " (64,)"))
+    if out_dtype not in _DT or img.dtype not in _DT:
+        raise TrambaHipError(f"stem7_affine_relu_pool: unsupported dtype {img.dtype} -> {out_dtype}")
+    bb, _, h, wd = img.shape
+    y = torch.empty((bb, max(stem7_pool_out_size(h), 0), max(stem7_pool_out_size(wd), 0), 64), dtype=out_dtype,
+                    device=img.device)
+    _check(lib().tramba_stem7_affine_relu_pool(_ptr(img), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), bb, h, wd,
+                                               _DT[img.dtype], _DT[out_dtype], _stream()), "stem7_affine_relu_pool")
     return y

@@ -13,8 +13,8 @@ import torch.nn.functional as F
 
 from . import hip
 from .modules import (FinalPatchExpand_X4, FreqBlockv6, LayerNorm2d, Linear2d, MultiScaleDecoderBlock, PatchExpand,
-                      VSSMEncoder, _infer, _init_weights, _run_blocks, model_mask_pool, _need_device, from_cl, load_pretrained_Base,
-                      to_cl)
+                      VSSMEncoder, _cache, _infer, _init_weights, _run_blocks, model_mask_pool, _need_device, from_cl,
+                      load_pretrained_Base, to_cl)
 from .ops import CrossMerge_Line, CrossScan_Line
 
 
@@ -282,8 +282,57 @@ def bulid_model(deep_supervision=True, use_pretrain=True, img_size=384, dims=128
 
 
 # ----------------------------------------------------------------------------- Tramba-R (ResNet50 encoder)
+def _bn_affine(bn: nn.BatchNorm2d, dtype=torch.float32):
+    """(scale, shift) of an eval-mode batch norm, computed in `dtype`: bn(x) = scale * x + shift with
+    scale = gamma / sqrt(var + eps), shift = beta - mean * scale"""
+    var, mean = bn.running_var.detach().to(dtype), bn.running_mean.detach().to(dtype)
+    scale = 1.0 / torch.sqrt(var + bn.eps)
+    if bn.weight is not None:
+        scale = bn.weight.detach().to(dtype) * scale
+    shift = -mean * scale
+    if bn.bias is not None:
+        shift = bn.bias.detach().to(dtype) + shift
+    return scale.contiguous(), shift.contiguous()
+
+
+def _conv_bn_params(owner: nn.Module, name, conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype, kmajor=True):
+    """(weight, scale, shift) of a conv + batch-norm pair as the library reads them: derived copies in `owner`'s pack cache,
+    built in f32 from the module's own (after prepare_inference: rounded) tensors, so that both paths multiply the same
+    16-bit weights.  The weight K-major (Cout, k, k, Cin) in `dtype`, or in the reference layout in f32."""
+    def make():
+        w = conv.weight.detach()
+        w = w.to(dtype).permute(0, 2, 3, 1).contiguous() if kmajor else w.float().contiguous()
+        return (w,) + _bn_affine(bn)
+    return _cache(owner).get(("conv_affine", name, dtype, kmajor),
+                             (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make)
+
+
+def _conv_bn_ok(conv: nn.Conv2d, bn: nn.BatchNorm2d, x_cl):
+    """can hip.conv_affine_cl take this conv + batch norm on this channels-last map?"""
+    k, s = conv.kernel_size[0], conv.stride[0]
+    return (conv.bias is None and conv.groups == 1 and conv.dilation == (1, 1) and conv.kernel_size == (k, k)
+            and conv.stride == (s, s) and conv.padding == (k // 2, k // 2) and bn.track_running_stats
+            and bn.running_mean is not None
+            and hip.conv_affine_supported(x_cl.dtype, x_cl.shape[1], x_cl.shape[2], conv.in_channels, conv.out_channels, k, s)
+            and x_cl.numel() * 2 < 2 ** 31)
+
+
+def _conv_bn_cl(owner, name, conv, bn, x_cl, residual=None, relu=True):
+    """act(bn(conv(x)) + residual) on a channels-last map: one library launch, or stock ops for a shape it does not take"""
+    if _conv_bn_ok(conv, bn, x_cl):
+        w, scale, shift = _conv_bn_params(owner, name, conv, bn, x_cl.dtype)
+        return hip.conv_affine_cl(x_cl, w, scale, shift, residual, relu, ksize=conv.kernel_size[0], stride=conv.stride[0])
+    y = F.conv2d(from_cl(x_cl), conv.weight.to(x_cl.dtype), None, conv.stride, conv.padding, conv.dilation, conv.groups)
+    y = F.batch_norm(y, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps)
+    if residual is not None:
+        y = y + from_cl(residual)
+    return to_cl(F.relu(y) if relu else y)
+
+
 class Bottleneck(nn.Module):
-    """resnet_encoder.py:62-79.  Stock conv/BN: runs on MIOpen (SURVEY 2 #12: out of kernel scope)."""
+    """resnet_encoder.py:62-79.  `forward` is stock conv / BN on MIOpen; `forward_cl` is the 16-bit inference path behind
+    `ResNet.library_convolutions`: each conv with its folded batch norm, shortcut and ReLU is one `hip.conv_affine_cl`
+    launch on the channels-last map (csrc/resnet_conv.hip)."""
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, dilation=1):
         super().__init__()
@@ -304,11 +353,22 @@ class Bottleneck(nn.Module):
             x = self.downsample(x)
         return F.relu(out + x, inplace=True)
 
+    def forward_cl(self, x):
+        """x (B, H, W, Cin) channels-last, eval mode, 16-bit, no autograd -> (B, Ho, Wo, 4 planes): 3 launches, 4 with the
+        downsample branch"""
+        out = _conv_bn_cl(self, "conv1", self.conv1, self.bn1, x)
+        out = _conv_bn_cl(self, "conv2", self.conv2, self.bn2, out)
+        if self.downsample is not None:
+            x = _conv_bn_cl(self, "downsample", self.downsample[0], self.downsample[1], x, relu=False)
+        return _conv_bn_cl(self, "conv3", self.conv3, self.bn3, out, residual=x)
+
 
 class ResNet(nn.Module):
     """resnet_encoder.py:81-110 (ResNet50 trunk; returns out5..out1 like the reference).  The
     reference loads a hard-coded checkpoint path in __init__ (:113); here weights come from
     ``load_state_dict`` / ``pretrained_path`` instead."""
+
+    library_convolutions = False           # encoders.set_library_convolutions(); no parameter, not in the state_dict
 
     def __init__(self, cfg=None, pretrained_path=None):
         super().__init__()
@@ -340,6 +400,34 @@ class ResNet(nn.Module):
         out4 = self.layer3(out3)
         out5 = self.layer4(out4)
         return out5, out4, out3, out2, out1
+
+    def _library_path(self, x):
+        from .encoders import _lowp_infer
+        return self.library_convolutions and not self.training and _lowp_infer(x, self.conv1.weight, self.bn1.weight)
+
+    def features_cl(self, x):
+        """x (B, 3, H, W) -> [out2, out3, out4] channels-last, what the decoder reads (Trambav6_enc.py:212-213).  With
+        `library_convolutions` on, in eval mode with 16-bit activations and no autograd: the stem is one
+        `hip.stem7_affine_relu_pool` launch and the 13 bottlenecks of layer1..3 are 42 `hip.conv_affine_cl` launches;
+        `layer4`, whose output the decoder never reads, is not run.  Otherwise the stock forward."""
+        if not self._library_path(x):
+            outs = self.forward(x.contiguous(memory_format=torch.channels_last))
+            return [to_cl(o) for o in outs[1:-1][::-1]]
+        bn = self.bn1
+        if (hip.stem7_pool_supported(x.dtype, x.shape[2], x.shape[3]) and bn.track_running_stats
+                and bn.running_mean is not None):
+            w, scale, shift = _conv_bn_params(self, "stem", self.conv1, bn, x.dtype, kmajor=False)
+            out = hip.stem7_affine_relu_pool(x.contiguous(), w, scale, shift, x.dtype)
+        else:
+            out = F.conv2d(x, self.conv1.weight.to(x.dtype), None, self.conv1.stride, self.conv1.padding)
+            out = F.relu(F.batch_norm(out, bn.running_mean, bn.running_var, bn.weight, bn.bias, False, 0.0, bn.eps))
+            out = to_cl(F.max_pool2d(out, kernel_size=3, stride=2, padding=1))
+        feats = []
+        for layer in (self.layer1, self.layer2, self.layer3):
+            for blk in layer:
+                out = blk.forward_cl(out)
+            feats.append(out)
+        return feats
 
 
 class BaseUMambaEnc(nn.Module):
@@ -378,7 +466,9 @@ class BaseUMambaEnc(nn.Module):
             model_mask_pool(self).begin_step()
         if self.compute_dtype is not None:
             x = x.to(self.compute_dtype)
-        if self.kind == "R":
+        if self.kind == "R" and self.encoder.library_convolutions:
+            feats = self.encoder.features_cl(x)                      # opt-in: encoder convs on the library
+        elif self.kind == "R":
             outs = self.encoder(x.contiguous(memory_format=torch.channels_last))
             feats = [to_cl(o) for o in outs[1:-1][::-1]]              # Trambav6_enc.py:212-213
         elif self.kind == "S":
@@ -434,7 +524,7 @@ def build(model_name, args):
         if getattr(args, "fused_attention_training", False):      # opt-in: attention backward on the library
             from .encoders import set_fused_attention_training
             set_fused_attention_training(model)
-        if getattr(args, "library_convolutions", False):           # opt-in: encoder convs on the library (DESIGN 19)
+        if getattr(args, "library_convolutions", False):           # opt-in: encoder convs on the library (DESIGN 19, 21)
             from .encoders import set_library_convolutions
             set_library_convolutions(model)
         if getattr(args, "library_training", False):               # opt-in: encoder training path on the library
