@@ -781,6 +781,66 @@ int tramba_conv_affine_cl(const void *x, const void *w, const float *scale, cons
 int tramba_stem7_affine_relu_pool(const void *img, const float *w, const float *scale, const float *shift, void *y, int batch,
                                   int h, int wd, int img_dtype, int dtype, void *stream);
 
+/* Backward of tramba_conv_affine_cl's convolution (scale / shift NULL, no ReLU: the raw convolution that the training path
+ * hands to its batch norm), i.e. of conv1 / conv2 / conv3 / downsample[0] of Bottleneck.forward under autograd
+ * (Models/encoder/resnet_encoder.py:62-110).  ksize 1 or 3, stride 1 or 2, pad = ksize / 2, bf16 / fp16, tensors 16-byte
+ * aligned, every tensor below 2^31 bytes.  With t = (b, oi, oj), M = B Ho Wo and k = (di ksize + dj) Cin + c:
+ *
+ * Input gradient: gx[b, p, q, c] = sum over (di, dj, co) of gy[b, oi, oj, co] w[co, di, dj, c] where oi stride = p + pad - di
+ * and oj stride = q + pad - dj have a solution inside the output map.  gy (B, Ho, Wo, Cout), gx (B, Hin, Win, Cin); wt is
+ * the TRANSPOSED weight copy (Cin, ksize, ksize, Cout) = reference weight.permute(1,2,3,0), taps not mirrored.  Cout % 64 == 0
+ * and Cin % 8 == 0; 1x1 / stride 1 is the plain product gy wt^T and runs on tramba_linear_cl (Cout % 8 == 0 there).  The
+ * implicit GEMM of the forward over (tap, co) with its two forms; no zero-inserted map is built.  f32 accumulation, one
+ * rounding; EVERY element of gx is written, pixels that no output reaches receive 0. */
+int tramba_conv_dgrad_cl(const void *gy, const void *wt, void *gx, int batch, int hin, int win, int cin, int cout, int ksize,
+                         int stride, int dtype, void *stream);
+/* Weight gradient: gw[co, k] = sum_t gy[t, co] x[pixel(t, di, dj), c], f32 K-major (Cout, ksize, ksize, Cin), x read in place:
+ * padding taps are predicated out, no column matrix is built, and the trailing pixels of x that a stride-2 convolution
+ * never reaches are never read.  Cin % 64 == 0, Cout % 8 == 0.  The 32-token steps of the reduction are dealt in runs to
+ * S = tramba_conv_wgrad_split(...) workgroups per output tile (S depends on the shape alone; 0 for a shape the entry
+ * refuses).  `work` receives S slabs of Cout K floats; the gradient is their sum in index order (tramba_slab_sum), and for
+ * S == 1 slab 0 is the gradient itself.  tramba_conv_wgrad_work is the size of `work` in bytes.  No atomics. */
+int tramba_conv_wgrad_split(int batch, int hin, int win, int cin, int cout, int ksize, int stride);
+size_t tramba_conv_wgrad_work(int batch, int hin, int win, int cin, int cout, int ksize, int stride);
+int tramba_conv_wgrad_cl(const void *gy, const void *x, float *work, size_t work_bytes, int batch, int hin, int win, int cin,
+                         int cout, int ksize, int stride, int dtype, void *stream);
+
+/* ------------------------------------------------------------------ batch norm and max pool of the ResNet-50 encoder (training) */
+/* Training-mode nn.BatchNorm2d (+ shortcut + ReLU) and the stem's max_pool2d(3, 2, 1) of Bottleneck.forward / ResNet.forward
+ * (Models/encoder/resnet_encoder.py:62-110) on channels-last maps (M = B H W, C): bf16 / fp16, C % 8 == 0, maps 16-byte
+ * aligned, f32 arithmetic, one rounding at a 16-bit store.  No atomics: every sum across workgroups goes through f32
+ * partials of P = tramba_bn_parts(m, c) contiguous row runs in the caller's workspace of tramba_bn_work(m, c) bytes, added
+ * in index order, so every result is a fixed function of the inputs (bitwise reproducible, capturable: no allocation, no
+ * synchronisation).  The workspace holds 2 P + 2 rows of C rounded up to 64 floats and carries nothing between calls.
+ *
+ * Statistics: mean[c] = sum_t x[t, c] / M and rstd[c] = 1 / sqrt(var[c] + eps) with the biased variance
+ * var[c] = sum_t (x[t, c] - mean[c])^2 / M, in two passes over x (never E[x^2] - E[x]^2).  running_mean / running_var (C) f32
+ * or NULL: updated in place on the device, running = (1 - momentum) running + momentum new, where the new variance is the
+ * unbiased var M / (M - 1).  M == 1 is refused, as F.batch_norm refuses it in training.  num_batches_tracked is the caller's. */
+int tramba_bn_parts(int64_t m, int c);
+size_t tramba_bn_work(int64_t m, int c);
+int tramba_bn_stats_cl(const void *x, float *mean, float *rstd, float *running_mean, float *running_var, void *work,
+                       size_t work_bytes, int64_t m, int c, float eps, float momentum, int dtype, void *stream);
+/* y[t, c] = act( gamma[c] (x[t, c] - mean[c]) rstd[c] + beta[c] + residual[t, c] ).  gamma / beta (C) f32 or NULL (1 / 0);
+ * residual (M, C) in dtype or NULL; relu 0 / 1. */
+int tramba_bn_act_cl(const void *x, const float *mean, const float *rstd, const float *gamma, const float *beta,
+                     const void *residual, void *y, int64_t m, int c, int relu, int dtype, void *stream);
+/* Backward of tramba_bn_act_cl through the batch statistics.  With dy' = dy where y > 0 and 0 elsewhere (relu; y is read for
+ * this mask alone and may be NULL without relu) and xh = (x - mean) rstd:
+ *     dbeta[c] = sum_t dy'[t, c]      dgamma[c] = sum_t dy'[t, c] xh[t, c]
+ *     dx[t, c] = gamma[c] rstd[c] ( dy'[t, c] - dbeta[c] / M - xh[t, c] dgamma[c] / M )      dres = dy'
+ * dx (M, C) in dtype is always written; dres (M, C) in dtype, dgamma, dbeta (C) f32 may each be NULL (no shortcut; a frozen
+ * affine, whose dx is bitwise the unfrozen one).  Three launches: partial sums per row run, their sum, dx. */
+int tramba_bn_act_bwd_cl(const void *dy, const void *x, const void *y, const float *mean, const float *rstd, const float *gamma,
+                         void *dx, void *dres, float *dgamma, float *dbeta, void *work, size_t work_bytes, int64_t m, int c,
+                         int relu, int dtype, void *stream);
+/* max_pool2d(kernel 3, stride 2, padding 1) on x (B, H, W, C) -> y (B, Ho, Wo, C), Ho = (H - 1) / 2 + 1.  Padding is never
+ * looked at; among equal values the FIRST of the window in row-major order is the maximum, a NaN replaces it (the framework's
+ * rule).  Backward in gather form: gx (B, H, W, C), every element written; an input pixel visits the at most 4 windows that
+ * cover it, recomputes their arg-max from x and adds gy where it is the arg-max itself (f32, one rounding). */
+int tramba_maxpool3s2_cl(const void *x, void *y, int batch, int h, int w, int c, int dtype, void *stream);
+int tramba_maxpool3s2_bwd_cl(const void *gy, const void *x, void *gx, int batch, int h, int w, int c, int dtype, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,18 @@
 //     sits in LDS tap-major, beside the image patch of the workgroup's 4 x 8 pooled pixels.  A group of 16 lanes computes the
 //     3 x 5 block of convolution outputs under the pool windows of two neighbouring pooled pixels in registers (the one-pixel
 //     halo included) and pools from there: the half-resolution map is never written, neither to memory nor to LDS.
+// (c) tramba_conv_dgrad_cl / tramba_conv_wgrad_cl: the backward of (a)'s convolution in 16-bit training
+//     (encoders.set_library_training), where (a) itself runs with NULL scale / shift and no ReLU as the raw convolution.
+//     Input gradient: gx[b, p, q, c] = sum over taps (di, dj) and co of gy[b, oi, oj, co] w[co, di, dj, c] with
+//     oi stride = p + pad - di (likewise oj): the implicit GEMM of (a) with rows = INPUT pixels, the reduction over (tap, co)
+//     and the transposed weight copy (Cin, k, k, Cout) as the K-major operand -- the same tile arithmetic, both forms, with
+//     the tap predicate "p + pad - di is a multiple of the stride and the quotient lies in the output map" in place of the
+//     padding test.  No zero-inserted map; a pixel that no output reaches keeps its zero accumulator: every gx is written.
+//     Weight gradient: gw[co, (di, dj, c)] = sum_t gy[t, co] x[pixel(t, di, dj), c], the reduction over tokens, the slow
+//     index of both operands: the structure of patch_conv_wgrad_kernel (patch_conv_bwd.hip) -- [32 t][64 k] of x, read in
+//     place with padding taps staged as zeros and never addressed, and [32 t][64 co] of gy go through LDS and all fragments are
+//     transposed reads.  Grid (K / 64, Cout / 64, S): the token steps are dealt in runs to S workgroups, run z writes f32
+//     slab z of the caller's workspace and the caller adds the slabs in index order.  No column matrix, no atomics.
 #include "common.h"
 
 namespace tramba {
@@ -221,6 +233,237 @@ static void launch_conv_affine(CaPlan p, const void *x, const void *w, const flo
 #undef TRAMBA_CA_LAUNCH
 }
 
+// ---- backward of the bottleneck convolutions ----
+// step t of the input gradient covers reduction indices 64 t .. 64 t + 63 = tap (di, dj), output channels 64 rem .. + 63.
+// r.iy0 / r.ix0 hold p + pad / q + pad of this lane's input pixel, r.img the image of gy.
+template <typename T>
+__device__ __forceinline__ void cd_load(CaStep &f, const CaRow<T> &r, const T *__restrict__ wcol, int t, int cs, int ks,
+                                        int stride, int Ho, int Wo, int Cout, unsigned wsub, const bool (&colok)[kCaSub])
+{
+    const int tap = t / cs, rem = t - tap * cs;
+    const int di = tap / ks, dj = tap - di * ks;
+    const int ny = r.iy0 - di, nx = r.ix0 - dj;                       // = oi stride, oj stride
+    bool in = ny >= 0 && nx >= 0;
+    int oy = ny, ox = nx;
+    if (stride == 2) {
+        in = in && ((ny | nx) & 1) == 0;                              // the tap reaches this pixel from no output otherwise
+        oy = ny >> 1;
+        ox = nx >> 1;
+    }
+    in = in && oy < Ho && ox < Wo;
+    const unsigned goff = in ? ((unsigned)oy * Wo + ox) * Cout + 64u * rem : 0u;
+    const ca_frag8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        f.a[h] = in ? *reinterpret_cast<const ca_frag8 *>(r.img + goff + 32 * h) : z;
+#pragma unroll
+        for (int j = 0; j < kCaSub; ++j)
+            f.b[h][j] = colok[j] ? *reinterpret_cast<const ca_frag8 *>(wcol + (size_t)j * wsub + 64u * t + 32 * h) : z;
+    }
+}
+
+// grid and forms as conv_affine_kernel; M = B H W input pixels, columns = Cin, K = ks ks Cout; wt (Cin, ks, ks, Cout)
+template <typename T, int NW, bool SPLITK>
+__global__ __launch_bounds__(NW * 64) void conv_dgrad_kernel(const T *__restrict__ gy, const T *__restrict__ wt,
+                                                            T *__restrict__ gx, int M, int H, int W, int Cin, int Cout, int ks,
+                                                            int stride, int Ho, int Wo)
+{
+    __shared__ __attribute__((aligned(16))) float red[NW][kCaRows][kCaCols];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n0 = blockIdx.y * kCaCols;
+    const long m0 = (long)blockIdx.x * (SPLITK ? kCaRows : kCaRows * NW) + (SPLITK ? 0 : kCaRows * wave);
+    const int cs = Cout >> 6, K = ks * ks * Cout, steps = K >> 6, pad = ks >> 1;
+
+    long pix = m0 + (lane & 15);
+    pix = pix < M ? pix : M - 1;
+    const int q = (int)(pix % W);
+    const long t2 = pix / W;
+    const int p = (int)(t2 % H), b = (int)(t2 / H);
+    CaRow<T> row;
+    row.img = gy + (size_t)b * Ho * Wo * Cout + 8 * (lane >> 4);
+    row.iy0 = p + pad;
+    row.ix0 = q + pad;
+    bool colok[kCaSub];
+#pragma unroll
+    for (int s = 0; s < kCaSub; ++s) colok[s] = n0 + 16 * s + (lane & 15) < Cin;
+    const T *wcol = wt + (size_t)(n0 + (lane & 15)) * K + 8 * (lane >> 4);
+    const unsigned wsub = 16u * (unsigned)K;
+
+    ca_acc4 acc[kCaSub];
+#pragma unroll
+    for (int s = 0; s < kCaSub; ++s) acc[s] = ca_acc4{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int kInc = SPLITK ? NW : 1;
+    int t = SPLITK ? wave : 0;
+    CaStep cur, nxt;
+    if (t < steps) cd_load(cur, row, wcol, t, cs, ks, stride, Ho, Wo, Cout, wsub, colok);
+    nxt = cur;
+    while (t < steps) {
+        const int tn = t + kInc;
+        if (tn < steps) cd_load(nxt, row, wcol, tn, cs, ks, stride, Ho, Wo, Cout, wsub, colok);
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int s = 0; s < kCaSub; ++s) acc[s] = CaMfma<T>::run(cur.a[h], cur.b[h][s], acc[s]);
+        cur = nxt;
+        t = tn;
+    }
+
+#pragma unroll
+    for (int s = 0; s < kCaSub; ++s)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) red[wave][4 * (lane >> 4) + e][16 * s + (lane & 15)] = acc[s][e];
+    __syncthreads();
+
+    if (SPLITK) {
+        if (threadIdx.x < kCaRows * (kCaCols / 8)) {
+            const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * 8;
+            float o[8];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) o[v] = red[0][r][c0 + v];
+#pragma unroll 4
+            for (int pp = 1; pp < NW; ++pp)
+#pragma unroll
+                for (int v = 0; v < 8; ++v) o[v] += red[pp][r][c0 + v];
+            ca_finish<T>(o, m0 + r, n0 + c0, M, Cin, nullptr, nullptr, nullptr, gx, 0);
+        }
+    } else {
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int idx = lane + 64 * it, r = idx >> 3, c0 = (idx & 7) * 8;
+            float o[8];
+#pragma unroll
+            for (int v = 0; v < 8; ++v) o[v] = red[wave][r][c0 + v];
+            ca_finish<T>(o, m0 + r, n0 + c0, M, Cin, nullptr, nullptr, nullptr, gx, 0);
+        }
+    }
+}
+
+template <typename T>
+static void launch_conv_dgrad(CaPlan p, const void *gy, const void *wt, void *gx, long m, int h, int wd, int cin, int cout,
+                              int ks, int stride, int ho, int wo, hipStream_t s)
+{
+    const long rows = p.splitk ? kCaRows : (long)kCaRows * p.nw;
+    dim3 grid((unsigned)((m + rows - 1) / rows), (unsigned)((cin + kCaCols - 1) / kCaCols));
+#define TRAMBA_CD_LAUNCH(NW, SPLIT)                                                                                         \
+    hipLaunchKernelGGL((conv_dgrad_kernel<T, NW, SPLIT>), grid, dim3(NW * 64), 0, s, (const T *)gy, (const T *)wt, (T *)gx,  \
+                       (int)m, h, wd, cin, cout, ks, stride, ho, wo)
+    if (p.splitk) {
+        if (p.nw == 16) TRAMBA_CD_LAUNCH(16, true);
+        else if (p.nw == 8) TRAMBA_CD_LAUNCH(8, true);
+        else TRAMBA_CD_LAUNCH(4, true);
+    } else {
+        if (p.nw == 4) TRAMBA_CD_LAUNCH(4, false);
+        else TRAMBA_CD_LAUNCH(2, false);
+    }
+#undef TRAMBA_CD_LAUNCH
+}
+
+// weight gradient: staged 16-bit tiles of 32 tokens x 64 columns, rows kCwStride bytes apart (a multiple of 16)
+typedef __attribute__((ext_vector_type(4))) short cw_frag4;
+constexpr int kCwDepth = 32, kCwCols = 64, kCwWaves = 4, kCwStride = kCwCols * 2 + 16;
+constexpr int kCwTarget = 512, kCwMaxSplit = 64;
+
+// Elements [row0 + j][col0 + (lane & 15)], j = 0..7, of a staged tile: two transposed reads (patch_conv_bwd.hip, pb_tr_pair).
+// Every address is 8-byte aligned and the callers' control flow is wave-uniform, so EXEC is all ones.
+__device__ __forceinline__ ca_frag8 cw_tr_pair(const unsigned char *img, int row0, int col0, int li)
+{
+    typedef __attribute__((address_space(3))) cw_frag4 lds_frag4;
+    const unsigned char *p = img + (row0 + (li >> 2)) * kCwStride + (col0 + 4 * (li & 3)) * 2;
+    const cw_frag4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_frag4 *)p);
+    const cw_frag4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_frag4 *)(p + 4 * kCwStride));
+    return ca_frag8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+
+// grid (K / 64, ceil(Cout / 64), S), 256 threads: wave w owns co 16 w .. 16 w + 15 of the block's 64; the block's 64 k lie in
+// ONE tap (Cin % 64 == 0)
+template <typename T>
+__global__ __launch_bounds__(kCwWaves * 64) void conv_wgrad_kernel(const T *__restrict__ gy, const T *__restrict__ x,
+                                                                  float *__restrict__ part, int M, int H, int W, int Cin,
+                                                                  int Cout, int ks, int stride, int Ho, int Wo,
+                                                                  int steps_per_split)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char x_lds[kCwDepth * kCwStride];
+    __shared__ __attribute__((aligned(16))) unsigned char g_lds[kCwDepth * kCwStride];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int K = ks * ks * Cin, pad = ks >> 1;
+    const int n0 = blockIdx.x * kCwCols, c0 = blockIdx.y * kCwCols;
+    const int tap = n0 / Cin, rem = n0 - tap * Cin;
+    const int di = tap / ks, dj = tap - di * ks;
+    const int steps_all = (M + kCwDepth - 1) / kCwDepth;
+    const int s0 = blockIdx.z * steps_per_split;
+    const int s1 = s0 + steps_per_split < steps_all ? s0 + steps_per_split : steps_all;
+    // staging: thread = (token row of the step, 16-byte chunk) of both tiles
+    const int srow = threadIdx.x >> 3, sch = 8 * (threadIdx.x & 7);
+    const bool co_ok = c0 + sch < Cout;             // Cout % 8 == 0
+    const ca_frag8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+
+    ca_acc4 acc[kCwCols / 16];
+#pragma unroll
+    for (int s = 0; s < kCwCols / 16; ++s) acc[s] = ca_acc4{0.f, 0.f, 0.f, 0.f};
+
+    ca_frag8 xv, gv;
+    auto load = [&](int s) {
+        const int t = s * kCwDepth + srow;          // tokens past M and padding taps add zeros; their address is never formed
+        xv = zero;
+        gv = zero;
+        if (t < M) {
+            const int oj = t % Wo, t2 = t / Wo, oi = t2 % Ho, b = t2 / Ho;
+            const int iy = oi * stride - pad + di, ix = oj * stride - pad + dj;
+            if (iy >= 0 && iy < H && ix >= 0 && ix < W)
+                xv = *reinterpret_cast<const ca_frag8 *>(x + (((size_t)b * H + iy) * W + ix) * Cin + rem + sch);
+            if (co_ok) gv = *reinterpret_cast<const ca_frag8 *>(gy + (size_t)t * Cout + c0 + sch);
+        }
+    };
+    load(s0);
+    for (int s = s0; s < s1; ++s) {
+        __syncthreads();
+        *reinterpret_cast<ca_frag8 *>(x_lds + srow * kCwStride + sch * 2) = xv;
+        *reinterpret_cast<ca_frag8 *>(g_lds + srow * kCwStride + sch * 2) = gv;
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+        const ca_frag8 bf = cw_tr_pair(g_lds, 8 * (lane >> 4), 16 * wave, lane & 15);
+#pragma unroll
+        for (int c = 0; c < kCwCols / 16; ++c) {
+            const ca_frag8 af = cw_tr_pair(x_lds, 8 * (lane >> 4), 16 * c, lane & 15);
+            acc[c] = CaMfma<T>::run(af, bf, acc[c]);
+        }
+    }
+
+    // accumulator element e of lane l: k = n0 + 16 c + 4 (l >> 4) + e, co = c0 + 16 wave + (l & 15)
+    float *slab = part + (size_t)blockIdx.z * ((size_t)Cout * K);
+    const int co = c0 + 16 * wave + (lane & 15);
+    if (co < Cout) {
+#pragma unroll
+        for (int c = 0; c < kCwCols / 16; ++c)
+            *reinterpret_cast<float4 *>(slab + (size_t)co * K + n0 + 16 * c + 4 * (lane >> 4)) =
+                make_float4(acc[c][0], acc[c][1], acc[c][2], acc[c][3]);
+    }
+}
+
+// steps of 32 tokens per split, and the number of splits: functions of the shape alone
+static void cw_plan(long m, int k, int cout, int &steps_per_split, int &nsplit)
+{
+    const long steps = (m + kCwDepth - 1) / kCwDepth;
+    const long base = (long)(k / kCwCols) * ((cout + kCwCols - 1) / kCwCols);
+    long want = kCwTarget / (base > 0 ? base : 1);
+    want = want < 1 ? 1 : (want > kCwMaxSplit ? kCwMaxSplit : want);
+    want = want > steps ? steps : want;
+    steps_per_split = (int)((steps + want - 1) / want);
+    nsplit = (int)((steps + steps_per_split - 1) / steps_per_split);
+}
+
+// the shape checks shared by the two backward entries and the sizing entries
+static bool cb_shape_ok(int batch, int hin, int win, int cin, int cout, int ksize, int stride)
+{
+    if (!((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2) && batch > 0 && cin > 0 && cout > 0 && hin > 0 && win > 0))
+        return false;
+    const int pad = ksize / 2;
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1;
+    return (double)batch * hin * win * cin * 2.0 < 2147483648.0 && (double)batch * ho * wo * cout * 2.0 < 2147483648.0 &&
+           (double)cout * ksize * ksize * cin * 4.0 < 2147483648.0 && (double)batch * hin * win < 2147483647.0;
+}
+
 // ---- stem: 7x7 / 2 convolution + affine + ReLU + 3x3 / 2 max pool ----
 // A workgroup owns a tile of 4 x 8 pooled pixels.  16 lanes share a PAIR of pooled pixels (ph, 2 q) and (ph, 2 q + 1), 4 output
 // channels each, and keep the 3 x 5 block of convolution outputs under the two pool windows in registers (60 f32
@@ -370,6 +613,82 @@ extern "C" int tramba_conv_affine_cl(const void *x, const void *w, const float *
     else
         launch_conv_affine<__half>(plan, x, w, scale, shift, residual, y, m, hin, win, cin, cout, ksize, stride, ho, wo,
                                    relu != 0, s);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+#define TRAMBA_CB_SHAPE_CHECKS(NAME)                                                                                     \
+    TRAMBA_CHECK(dtype == TRAMBA_BF16 || dtype == TRAMBA_F16, NAME ": bf16/f16 only");                                   \
+    TRAMBA_CHECK(ksize == 1 || ksize == 3, NAME ": ksize = %d must be 1 or 3", ksize);                                   \
+    TRAMBA_CHECK(stride == 1 || stride == 2, NAME ": stride = %d must be 1 or 2", stride);                               \
+    TRAMBA_CHECK(batch > 0 && cin > 0 && cout > 0 && hin > 0 && win > 0, NAME ": empty shape");                          \
+    TRAMBA_CHECK(cin % 8 == 0 && cout % 8 == 0, NAME ": Cin=%d and Cout=%d must be multiples of 8", cin, cout);          \
+    TRAMBA_CHECK(cb_shape_ok(batch, hin, win, cin, cout, ksize, stride), NAME ": map, gradient or weight beyond 32-bit byte offsets")
+
+extern "C" int tramba_conv_dgrad_cl(const void *gy, const void *wt, void *gx, int batch, int hin, int win, int cin, int cout,
+                                    int ksize, int stride, int dtype, void *stream)
+{
+    TRAMBA_CHECK(gy && wt && gx, "conv_dgrad_cl: null tensor");
+    TRAMBA_CB_SHAPE_CHECKS("conv_dgrad_cl");
+    const bool gemm = ksize == 1 && stride == 1;       // gx = gy wt^T, a plain (M, Cout) x (Cout, Cin) product
+    TRAMBA_CHECK(gemm || cout % 64 == 0, "conv_dgrad_cl: Cout=%d must be a multiple of 64 (except 1x1 / stride 1)", cout);
+    TRAMBA_CHECK((cin + kCaCols - 1) / kCaCols <= 65535, "conv_dgrad_cl: too many channels");
+    TRAMBA_CHECK(aligned16(gy) && aligned16(wt) && aligned16(gx), "conv_dgrad_cl: tensors must be 16-byte aligned");
+    const long m = (long)batch * hin * win;
+    if (gemm) return tramba_linear_cl(gy, wt, nullptr, nullptr, gx, m, cin, cout, TRAMBA_ACT_NONE, dtype, dtype, stream);
+    const int pad = ksize / 2;
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1;
+    const CaPlan plan = ca_plan(m, cin, ksize * ksize * cout);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == TRAMBA_BF16)
+        launch_conv_dgrad<__hip_bfloat16>(plan, gy, wt, gx, m, hin, win, cin, cout, ksize, stride, ho, wo, s);
+    else
+        launch_conv_dgrad<__half>(plan, gy, wt, gx, m, hin, win, cin, cout, ksize, stride, ho, wo, s);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_conv_wgrad_split(int batch, int hin, int win, int cin, int cout, int ksize, int stride)
+{
+    if (!cb_shape_ok(batch, hin, win, cin, cout, ksize, stride) || cin % 64 != 0 || cout % 8 != 0) return 0;
+    const int pad = ksize / 2;
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1;
+    int sps, nsplit;
+    cw_plan((long)batch * ho * wo, ksize * ksize * cin, cout, sps, nsplit);
+    return nsplit;
+}
+
+extern "C" size_t tramba_conv_wgrad_work(int batch, int hin, int win, int cin, int cout, int ksize, int stride)
+{
+    const int nsplit = tramba_conv_wgrad_split(batch, hin, win, cin, cout, ksize, stride);
+    return (size_t)nsplit * ((size_t)cout * ksize * ksize * cin) * sizeof(float);
+}
+
+extern "C" int tramba_conv_wgrad_cl(const void *gy, const void *x, float *work, size_t work_bytes, int batch, int hin, int win,
+                                    int cin, int cout, int ksize, int stride, int dtype, void *stream)
+{
+    TRAMBA_CHECK(gy && x, "conv_wgrad_cl: null tensor");
+    TRAMBA_CB_SHAPE_CHECKS("conv_wgrad_cl");
+    TRAMBA_CHECK(cin % 64 == 0, "conv_wgrad_cl: Cin=%d must be a multiple of 64", cin);
+    TRAMBA_CHECK((cout + kCwCols - 1) / kCwCols <= 65535, "conv_wgrad_cl: too many channels");
+    TRAMBA_CHECK(aligned16(gy) && aligned16(x) && aligned16(work), "conv_wgrad_cl: tensors must be 16-byte aligned");
+    const size_t need = tramba_conv_wgrad_work(batch, hin, win, cin, cout, ksize, stride);
+    TRAMBA_CHECK(work && work_bytes >= need, "conv_wgrad_cl: workspace of %zu bytes needed, %zu given", need,
+                 work ? work_bytes : (size_t)0);
+    const int pad = ksize / 2;
+    const int ho = (hin + 2 * pad - ksize) / stride + 1, wo = (win + 2 * pad - ksize) / stride + 1;
+    const long m = (long)batch * ho * wo;
+    const int k = ksize * ksize * cin;
+    int sps, nsplit;
+    cw_plan(m, k, cout, sps, nsplit);
+    dim3 grid((unsigned)(k / kCwCols), (unsigned)((cout + kCwCols - 1) / kCwCols), (unsigned)nsplit);
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == TRAMBA_BF16)
+        hipLaunchKernelGGL((conv_wgrad_kernel<__hip_bfloat16>), grid, dim3(kCwWaves * 64), 0, s, (const __hip_bfloat16 *)gy,
+                           (const __hip_bfloat16 *)x, work, (int)m, hin, win, cin, cout, ksize, stride, ho, wo, sps);
+    else
+        hipLaunchKernelGGL((conv_wgrad_kernel<__half>), grid, dim3(kCwWaves * 64), 0, s, (const __half *)gy, (const __half *)x,
+                           work, (int)m, hin, win, cin, cout, ksize, stride, ho, wo, sps);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -189,9 +189,23 @@ def set_library_training(model, enabled=True):
     the first-layer embeddings on `_LinearTrainCL` over framework-made patch rows, and attention on `_WindowAttnFn` /
     `_KvAttnFn` wherever the kernels take the shape (the switch implies `set_fused_attention_training`; a block they do
     not take keeps stock SDPA for the attention alone).  fp32 activations and inference are untouched.  Returns the
-    number of modules switched."""
+    number of modules switched.
+
+    A Tramba-R model's `ResNet` encoder and each of its 16 `Bottleneck`s count as one module each (17).  In train mode, with
+    16-bit activations and autograd on, `ResNet.features_cl` then runs conv1 as patch rows on `_LinearTrainCL`, every batch
+    norm of the stem and layer1..3 on batch statistics (`hip.bn_stats_cl`, which updates the running buffers in place on the
+    device, + `hip.bn_act_cl`), every bottleneck convolution as the raw `hip.conv_affine_cl` and the pool on
+    `hip.maxpool3s2_cl`, each with its backward on the library (resnet_train).  `layer4`, which the decoder never
+    reads, is not run: its parameters get no gradient on either path, but its running statistics and num_batches_tracked
+    stay as they were, the one intended difference from the stock step.  fp32 activations, eval mode, a batch norm with
+    track_running_stats=False or momentum=None and a dilated convolution keep the stock path."""
+    from .models import Bottleneck, ResNet
     count, seen = 0, set()
     for m in model.modules():
+        if isinstance(m, (ResNet, Bottleneck)):
+            m.library_training = bool(enabled)
+            count += 1
+            continue
         if isinstance(m, _LIBRARY_TRAINING_KINDS):
             for sub in (m, *m.children()):
                 if id(sub) not in seen and (sub is m or isinstance(sub, (nn.Linear, nn.LayerNorm, nn.Conv2d))):

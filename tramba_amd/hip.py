@@ -144,6 +144,17 @@ SIGNATURES = {
     "tramba_patch_embed_ln": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_f, c_int, c_int, c_vp]),
     "tramba_conv_affine_cl": (c_int, [c_vp] * 6 + [c_int] * 9 + [c_vp]),
     "tramba_stem7_affine_relu_pool": (c_int, [c_vp] * 5 + [c_int] * 5 + [c_vp]),
+    "tramba_conv_dgrad_cl": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
+    "tramba_conv_wgrad_split": (c_int, [c_int] * 7),
+    "tramba_conv_wgrad_work": (ctypes.c_size_t, [c_int] * 7),
+    "tramba_conv_wgrad_cl": (c_int, [c_vp] * 3 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
+    "tramba_bn_parts": (c_int, [c_i64, c_int]),
+    "tramba_bn_work": (ctypes.c_size_t, [c_i64, c_int]),
+    "tramba_bn_stats_cl": (c_int, [c_vp] * 6 + [ctypes.c_size_t, c_i64, c_int, c_f, c_f, c_int, c_vp]),
+    "tramba_bn_act_cl": (c_int, [c_vp] * 7 + [c_i64, c_int, c_int, c_int, c_vp]),
+    "tramba_bn_act_bwd_cl": (c_int, [c_vp] * 11 + [ctypes.c_size_t, c_i64, c_int, c_int, c_int, c_vp]),
+    "tramba_maxpool3s2_cl": (c_int, [c_vp] * 2 + [c_int] * 5 + [c_vp]),
+    "tramba_maxpool3s2_bwd_cl": (c_int, [c_vp] * 3 + [c_int] * 5 + [c_vp]),
 }
 
 _lib = None
@@ -1965,3 +1976,200 @@ def stem7_affine_relu_pool(img, w, scale, shift, out_dtype):
     _check(lib().tramba_stem7_affine_relu_pool(_ptr(img), _ptr(w), _ptr(scale), _ptr(shift), _ptr(y), bb, h, wd,
                                                _DT[img.dtype], _DT[out_dtype], _stream()), "stem7_affine_relu_pool")
     return y
+
+
+# ----------------------------------------------------------------------------- ResNet-50 encoder: batch norm and max pool (training)
+def bn_parts(m, c):
+    """the row runs a (m, c) channels-last map is dealt in (the rule of csrc/batchnorm.hip, bn_split), without the library"""
+    return min(max(m // 128, 1), 64) if m > 0 and c > 0 else 0
+
+
+def bn_work_floats(m, c):
+    """f32 elements of the workspace of bn_stats_cl / bn_act_bwd_cl: 2 partial tables of bn_parts rows and 2 rows of sums, a
+    row being c rounded up to 64"""
+    return (2 * bn_parts(m, c) + 2) * ((c + 63) // 64 * 64) if m > 0 and c > 0 else 0
+
+
+def bn_supported(dtype, m, c):
+    """the argument checks of tramba_bn_stats_cl / _act_cl / _act_bwd_cl that depend on the map, without the library"""
+    return dtype in _ATTN_DTYPES and c > 0 and c % 8 == 0 and 2 <= m < 2 ** 31 - 1 and (c + 63) // 64 <= 65535
+
+
+def _bn_map(name, x, **same):
+    if x.dim() < 2 or x.dtype not in _ATTN_DTYPES:
+        raise TrambaHipError(f"{name}: need a channels-last (..., C) bf16 / fp16 map, got {tuple(x.shape)} {x.dtype}")
+    c = x.shape[-1]
+    for key, t in same.items():
+        if t is not None and (t.dtype != x.dtype or t.shape != x.shape):
+            raise TrambaHipError(f"{name}: {key} must be {x.dtype} {tuple(x.shape)}, got {t.dtype} {tuple(t.shape)}")
+    return x.numel() // max(c, 1), c
+
+
+def _bn_vec(name, c, **vecs):
+    for key, t in vecs.items():
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (c,)):
+            raise TrambaHipError(f"{name}: {key} must be float32 ({c},)")
+
+
+def _bn_workspace(m, c, device):
+    nbytes = lib().tramba_bn_work(m, c)
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), nbytes
+
+
+def bn_stats_cl(x, eps, running_mean=None, running_var=None, momentum=0.1):
+    """x: (..., C) bf16/f16 channels-last -> (mean, rstd) f32 (C) over all leading axes: the batch mean and
+    1 / sqrt(biased variance + eps), two passes.  running_mean / running_var (C) f32 are updated IN PLACE on the device
+    (running = (1 - momentum) running + momentum new, the variance unbiased), so a captured graph updates them per replay."""
+    _dev(x, running_mean, running_var)
+    m, c = _bn_map("bn_stats_cl", x)
+    _bn_vec("bn_stats_cl", c, running_mean=running_mean, running_var=running_var)
+    if m == 1:
+        raise TrambaHipError("bn_stats_cl: expected more than 1 value per channel when training")
+    mean = torch.empty(c, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(c, dtype=torch.float32, device=x.device)
+    work, nbytes = _bn_workspace(m, c, x.device)
+    _check(lib().tramba_bn_stats_cl(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var), _ptr(work), nbytes,
+                                    m, c, float(eps), float(momentum), dt(x), _stream()), "bn_stats_cl")
+    return mean, rstd
+
+
+def bn_act_cl(x, mean, rstd, gamma=None, beta=None, residual=None, relu=False):
+    """y = act(gamma (x - mean) rstd + beta + residual) on a channels-last map; mean, rstd, gamma, beta (C) f32 (gamma / beta
+    may be None: 1 / 0), residual in x's shape and dtype or None; f32 throughout, one rounding."""
+    _dev(x, mean, rstd, gamma, beta, residual)
+    m, c = _bn_map("bn_act_cl", x, residual=residual)
+    _bn_vec("bn_act_cl", c, mean=mean, rstd=rstd, gamma=gamma, beta=beta)
+    if mean is None or rstd is None:
+        raise TrambaHipError("bn_act_cl: mean and rstd are required")
+    y = torch.empty_like(x)
+    _check(lib().tramba_bn_act_cl(_ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(residual), _ptr(y), m, c,
+                                  int(bool(relu)), dt(x), _stream()), "bn_act_cl")
+    return y
+
+
+def bn_act_bwd_cl(dy, x, y, mean, rstd, gamma=None, relu=False, want_dres=False, want_affine=True):
+    """Backward of bn_act_cl through the batch statistics -> (dx, dres or None, dgamma or None, dbeta or None).  y is read
+    for the ReLU mask y > 0 alone (None without relu); dres is the masked dy, the shortcut's gradient; dgamma / dbeta f32.
+    dx does not depend on want_affine."""
+    _dev(dy, x, y, mean, rstd, gamma)
+    m, c = _bn_map("bn_act_bwd_cl", x, dy=dy, y=y)
+    _bn_vec("bn_act_bwd_cl", c, mean=mean, rstd=rstd, gamma=gamma)
+    if mean is None or rstd is None or dy is None or (relu and y is None):
+        raise TrambaHipError("bn_act_bwd_cl: dy, mean, rstd and (with relu) y are required")
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if want_dres else None
+    dgamma = torch.empty(c, dtype=torch.float32, device=x.device) if want_affine else None
+    dbeta = torch.empty(c, dtype=torch.float32, device=x.device) if want_affine else None
+    work, nbytes = _bn_workspace(m, c, x.device)
+    _check(lib().tramba_bn_act_bwd_cl(_ptr(dy), _ptr(x), _ptr(y), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(dx), _ptr(dres),
+                                      _ptr(dgamma), _ptr(dbeta), _ptr(work), nbytes, m, c, int(bool(relu)), dt(x), _stream()),
+           "bn_act_bwd_cl")
+    return dx, dres, dgamma, dbeta
+
+
+def maxpool3s2_supported(dtype, h, w, c):
+    """the argument checks of tramba_maxpool3s2_cl / _bwd_cl that depend on the map (batch 1), without the library"""
+    return dtype in _ATTN_DTYPES and h > 0 and w > 0 and c > 0 and c % 8 == 0 and h * w * (c // 8) < (2 ** 31 - 1) * 256
+
+
+def _pool_map(name, x):
+    if x.dim() != 4 or x.dtype not in _ATTN_DTYPES:
+        raise TrambaHipError(f"{name}: need a channels-last (B, H, W, C) bf16 / fp16 map, got {tuple(x.shape)} {x.dtype}")
+    return x.shape
+
+
+def maxpool3s2_cl(x):
+    """max_pool2d(3, 2, 1) on x (B, H, W, C) bf16/f16 -> (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C); ties go to the first maximum
+    of a window in row-major order, padding never wins"""
+    _dev(x)
+    bb, h, w, c = _pool_map("maxpool3s2_cl", x)
+    y = torch.empty((bb, max((h - 1) // 2 + 1, 0), max((w - 1) // 2 + 1, 0), c), dtype=x.dtype, device=x.device)
+    _check(lib().tramba_maxpool3s2_cl(_ptr(x), _ptr(y), bb, h, w, c, dt(x), _stream()), "maxpool3s2_cl")
+    return y
+
+
+def maxpool3s2_bwd_cl(gy, x):
+    """Backward of maxpool3s2_cl: gy (B, Ho, Wo, C) and the saved input x (B, H, W, C) -> gx in x's shape, every element
+    written; the arg-max is recomputed from x (gather form, nothing scattered)."""
+    _dev(gy, x)
+    bb, h, w, c = _pool_map("maxpool3s2_bwd_cl", x)
+    if gy.dtype != x.dtype or tuple(gy.shape) != (bb, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c):
+        raise TrambaHipError(f"maxpool3s2_bwd_cl: gy {tuple(gy.shape)} {gy.dtype} does not belong to x {tuple(x.shape)} {x.dtype}")
+    gx = torch.empty_like(x)
+    _check(lib().tramba_maxpool3s2_bwd_cl(_ptr(gy), _ptr(x), _ptr(gx), bb, h, w, c, dt(x), _stream()), "maxpool3s2_bwd_cl")
+    return gx
+
+
+# ----------------------------------------------------------------------------- ResNet-50 encoder: backward of the bottleneck convolutions
+def conv_train_supported(dtype, h, w, cin, cout, ksize, stride):
+    """can conv_affine_cl (as the raw convolution), conv_dgrad_cl and conv_wgrad_cl take this layer on this map (batch 1)?
+    The forward's domain with Cout % 64 == 0 for the input gradient's reduction (1x1 / stride 1 is a plain product and needs
+    Cout % 8 only) and gy and the f32 weight gradient below 2^31 bytes."""
+    if not conv_affine_supported(dtype, h, w, cin, cout, ksize, stride):
+        return False
+    ho, wo = conv_out_size(h, ksize, stride), conv_out_size(w, ksize, stride)
+    return ((cout % 64 == 0 or (ksize == 1 and stride == 1)) and ho > 0 and wo > 0 and ho * wo * cout * 2 < 2 ** 31
+            and cout * ksize * ksize * cin * 4 < 2 ** 31 and h * w < 2 ** 31 - 1 and (cin + 63) // 64 <= 65535)
+
+
+def conv_wgrad_steps(m):
+    """32-token steps of conv_wgrad_cl's reduction over m output pixels"""
+    return (m + 31) // 32
+
+
+def conv_wgrad_split(batch, h, w, cin, cout, ksize, stride):
+    """the number of f32 slabs conv_wgrad_cl leaves (the rule of csrc/resnet_conv.hip, cw_plan), without the library"""
+    m = batch * conv_out_size(h, ksize, stride) * conv_out_size(w, ksize, stride)
+    steps = conv_wgrad_steps(m)
+    base = (ksize * ksize * cin // 64) * ((cout + 63) // 64)
+    want = min(max(512 // max(base, 1), 1), 64, steps)
+    per = (steps + want - 1) // want
+    return (steps + per - 1) // per
+
+
+def conv_transposed_weight(w_kmajor):
+    """(Cout, k, k, Cin) -> the (Cin, k, k, Cout) copy conv_dgrad_cl reads (a framework data-movement op; cache it per weight)"""
+    return w_kmajor.permute(3, 1, 2, 0).contiguous()
+
+
+def _conv_bwd_geom(name, gy, x_shape, x_dtype, ksize, stride):
+    if gy.dim() != 4 or len(x_shape) != 4 or gy.dtype != x_dtype or gy.dtype not in _ATTN_DTYPES:
+        raise TrambaHipError(f"{name}: need gy (B, Ho, Wo, Cout) and x (B, H, W, Cin) of one 16-bit dtype, got {tuple(gy.shape)} "
+                             f"{gy.dtype} {tuple(x_shape)} {x_dtype}")
+    if ksize not in (1, 3) or stride not in (1, 2):
+        raise TrambaHipError(f"{name}: ksize = {ksize} must be 1 or 3 and stride = {stride} 1 or 2")
+    bb, h, wd, cin = x_shape
+    if tuple(gy.shape[:3]) != (bb, conv_out_size(h, ksize, stride), conv_out_size(wd, ksize, stride)):
+        raise TrambaHipError(f"{name}: gy {tuple(gy.shape)} does not belong to x {tuple(x_shape)} with ksize = {ksize}, "
+                             f"stride = {stride}")
+    return bb, h, wd, cin, gy.shape[3]
+
+
+def conv_dgrad_cl(gy, wt, x_shape, stride=1):
+    """Input gradient of the raw convolution of conv_affine_cl: gy (B, Ho, Wo, Cout), wt (Cin, k, k, Cout) =
+    conv_transposed_weight(w_kmajor), x_shape (B, H, W, Cin) -> gx of that shape in gy's dtype, every element written (zeros
+    where no output reaches)."""
+    _dev(gy, wt)
+    k = wt.shape[1] if wt.dim() == 4 else 0
+    bb, h, wd, cin, cout = _conv_bwd_geom("conv_dgrad_cl", gy, tuple(x_shape), wt.dtype, k, stride)
+    if tuple(wt.shape) != (cin, k, k, cout):
+        raise TrambaHipError(f"conv_dgrad_cl: wt must be (Cin, k, k, Cout) = {(cin, k, k, cout)}, got {tuple(wt.shape)}")
+    gx = torch.empty((bb, h, wd, cin), dtype=gy.dtype, device=gy.device)
+    _check(lib().tramba_conv_dgrad_cl(_ptr(gy), _ptr(wt), _ptr(gx), bb, h, wd, cin, cout, k, stride, dt(gy), _stream()),
+           "conv_dgrad_cl")
+    return gx
+
+
+def conv_wgrad_cl(gy, x, ksize, stride=1):
+    """Weight gradient of the raw convolution of conv_affine_cl: gy (B, Ho, Wo, Cout), x (B, H, W, Cin) -> gw (Cout, k, k, Cin)
+    f32 K-major.  The kernel leaves one f32 slab per token run; they are added in index order by slab_sum (at once: the
+    caller permutes the result, so the sum cannot be deferred)."""
+    _dev(gy, x)
+    bb, h, wd, cin, cout = _conv_bwd_geom("conv_wgrad_cl", gy, tuple(x.shape), x.dtype, ksize, stride)
+    nsplit = lib().tramba_conv_wgrad_split(bb, h, wd, cin, cout, ksize, stride)
+    nbytes = lib().tramba_conv_wgrad_work(bb, h, wd, cin, cout, ksize, stride)
+    work = torch.empty((nsplit, cout * ksize * ksize * cin), dtype=torch.float32, device=gy.device)   # (none for a refused shape)
+    _check(lib().tramba_conv_wgrad_cl(_ptr(gy), _ptr(x), _ptr(work), nbytes, bb, h, wd, cin, cout, ksize, stride, dt(gy),
+                                      _stream()), "conv_wgrad_cl")
+    out = slab_sum(work) if nsplit > 1 else work[0]
+    return out.view(cout, ksize, ksize, cin)

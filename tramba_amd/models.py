@@ -332,7 +332,11 @@ def _conv_bn_cl(owner, name, conv, bn, x_cl, residual=None, relu=True):
 class Bottleneck(nn.Module):
     """resnet_encoder.py:62-79.  `forward` is stock conv / BN on MIOpen; `forward_cl` is the 16-bit inference path behind
     `ResNet.library_convolutions`: each conv with its folded batch norm, shortcut and ReLU is one `hip.conv_affine_cl`
-    launch on the channels-last map (csrc/resnet_conv.hip)."""
+    launch on the channels-last map (csrc/resnet_conv.hip).  Switched by `encoders.set_library_training`, in train
+    mode with 16-bit activations and autograd on, `forward_cl` is the training path instead: raw convolutions, batch norms on
+    batch statistics and their backward on the library (resnet_train.bottleneck_train_cl)."""
+
+    library_training = False               # encoders.set_library_training(); no parameter, not in the state_dict
 
     def __init__(self, inplanes, planes, stride=1, downsample=None, dilation=1):
         super().__init__()
@@ -355,7 +359,10 @@ class Bottleneck(nn.Module):
 
     def forward_cl(self, x):
         """x (B, H, W, Cin) channels-last, eval mode, 16-bit, no autograd -> (B, Ho, Wo, 4 planes): 3 launches, 4 with the
-        downsample branch"""
+        downsample branch.  With `library_training`, in train mode, 16-bit and with autograd on: the training path."""
+        from . import resnet_train
+        if resnet_train.train_path(self, x) and resnet_train.block_trainable(self):
+            return resnet_train.bottleneck_train_cl(self, x)
         out = _conv_bn_cl(self, "conv1", self.conv1, self.bn1, x)
         out = _conv_bn_cl(self, "conv2", self.conv2, self.bn2, out)
         if self.downsample is not None:
@@ -369,6 +376,7 @@ class ResNet(nn.Module):
     ``load_state_dict`` / ``pretrained_path`` instead."""
 
     library_convolutions = False           # encoders.set_library_convolutions(); no parameter, not in the state_dict
+    library_training = False               # encoders.set_library_training(); likewise
 
     def __init__(self, cfg=None, pretrained_path=None):
         super().__init__()
@@ -405,11 +413,34 @@ class ResNet(nn.Module):
         from .encoders import _lowp_infer
         return self.library_convolutions and not self.training and _lowp_infer(x, self.conv1.weight, self.bn1.weight)
 
+    def _train_path(self, x):
+        """the training path on the library: switched, train mode, 16-bit activations, autograd on, and no layer of a form
+        that keeps the stock path (a batch norm without running statistics or with momentum None, a dilated convolution)"""
+        from . import resnet_train
+        return (resnet_train.train_path(self, x) and resnet_train._bn_trainable(self.bn1)
+                and all(isinstance(b, Bottleneck) and b.library_training and resnet_train.block_trainable(b)
+                        for layer in (self.layer1, self.layer2, self.layer3) for b in layer))
+
     def features_cl(self, x):
         """x (B, 3, H, W) -> [out2, out3, out4] channels-last, what the decoder reads (Trambav6_enc.py:212-213).  With
         `library_convolutions` on, in eval mode with 16-bit activations and no autograd: the stem is one
         `hip.stem7_affine_relu_pool` launch and the 13 bottlenecks of layer1..3 are 42 `hip.conv_affine_cl` launches;
-        `layer4`, whose output the decoder never reads, is not run.  Otherwise the stock forward."""
+        `layer4`, whose output the decoder never reads, is not run.  Otherwise the stock forward.
+
+        With `library_training` on, in train mode with 16-bit activations and autograd on: the training path on the library
+        (resnet_train) -- conv1 as patch rows on `_LinearTrainCL`, 43 batch norms on batch statistics (which update
+        the running buffers on the device), 42 raw convolutions and the pool, each with its backward.  `layer4` is NOT run
+        here either: its parameters receive no gradient on either path, but unlike the stock forward its running statistics
+        and num_batches_tracked stay as they were -- the one intended difference from stock."""
+        if self._train_path(x):
+            from . import resnet_train
+            out = resnet_train.stem_train_cl(self, x)
+            feats = []
+            for layer in (self.layer1, self.layer2, self.layer3):
+                for blk in layer:
+                    out = blk.forward_cl(out)
+                feats.append(out)
+            return feats
         if not self._library_path(x):
             outs = self.forward(x.contiguous(memory_format=torch.channels_last))
             return [to_cl(o) for o in outs[1:-1][::-1]]
@@ -466,8 +497,8 @@ class BaseUMambaEnc(nn.Module):
             model_mask_pool(self).begin_step()
         if self.compute_dtype is not None:
             x = x.to(self.compute_dtype)
-        if self.kind == "R" and self.encoder.library_convolutions:
-            feats = self.encoder.features_cl(x)                      # opt-in: encoder convs on the library
+        if self.kind == "R" and (self.encoder.library_convolutions or self.encoder.library_training):
+            feats = self.encoder.features_cl(x)                      # opt-in: encoder on the library
         elif self.kind == "R":
             outs = self.encoder(x.contiguous(memory_format=torch.channels_last))
             feats = [to_cl(o) for o in outs[1:-1][::-1]]              # Trambav6_enc.py:212-213
@@ -527,7 +558,7 @@ def build(model_name, args):
         if getattr(args, "library_convolutions", False):           # opt-in: encoder convs on the library
             from .encoders import set_library_convolutions
             set_library_convolutions(model)
-        if getattr(args, "library_training", False):               # opt-in: encoder training path on the library (DESIGN 20)
+        if getattr(args, "library_training", False):               # opt-in: encoder training path on the library (DESIGN 20, 22)
             from .encoders import set_library_training
             set_library_training(model)
         return model
