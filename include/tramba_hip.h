@@ -162,6 +162,8 @@ int tramba_scan_table_inverse(const int32_t *table, int k, int l, int32_t *inv_p
  * ckpt: (B, KD, nchunk, N) f32 chunk-end states for the backward, or NULL;
  * nchunk = tramba_selective_scan_nchunk(L, io_dtype). */
 int tramba_selective_scan_nchunk(int l, int io_dtype);
+/* the largest d_state tramba_selective_scan_fwd / _bwd accept (16) */
+int tramba_selective_scan_max_dstate(void);
 int tramba_selective_scan_fwd(const void *u, const void *delta, const float *A, const void *Bm,
                               const void *Cm, const float *D, const float *delta_bias, void *out,
                               float *ckpt, int batch, int kd, int k, int n, int l, int io_dtype,
@@ -169,7 +171,9 @@ int tramba_selective_scan_fwd(const void *u, const void *delta, const float *A, 
 /* du, ddelta: (B, KD, L) io_dtype; dA (KD,N), dD, ddelta_bias (KD): f32, ACCUMULATED into
  * (caller zeroes);  dB, dC: (ncopy, B, K, N, L) f32, accumulated into (caller zeroes) -- the rows of a
  * direction group spread their atomic adds over `ncopy` private copies which the caller sums.
- * Both directions: d_state N = 1 (everything Tramba builds), 2 and 4. */
+ * Both directions: d_state N = 1 .. 16 (tramba_selective_scan_max_dstate()); outside that range the call returns an
+ * error that names d_state and the limit.  N = 1 (everything Tramba builds), 2 and 4 run kernels with N a compile-time
+ * constant; every other N runs a state-looped pair with the same chunking, checkpoints and layouts. */
 int tramba_selective_scan_bwd(const void *u, const void *delta, const float *A, const void *Bm,
                               const void *Cm, const float *D, const float *delta_bias,
                               const float *dout, const float *ckpt, void *du, void *ddelta,

@@ -18,12 +18,22 @@
 //   * state in fp32; softplus threshold 20 like the reference; exp via v_exp_f32.
 // Chunk-end states go to `ckpt` for the backward (same chunking), which replays each chunk
 // forward from its checkpoint and runs the adjoint recurrence right-to-left.
+//
+// d_state.  N = 1, 2, 4 run the templates below with N a compile-time constant (operand ring of B[N] / C[N]
+// packs).  Every other N up to 16 runs the state-looped pair selective_scan_{fwd,bwd}_nloop_kernel further down: same
+// chunking, checkpoints and layouts, u / delta (and dout) fetched once per chunk, the state index a run-time loop
+// (in the forward with the B / C rows of the next state in flight under the current one).  What is per (row, state) -- the chunk
+// carry, A, the adjoint carries -- lives in ONE register spread over the row's lanes (lane n of a row holds state
+// n; N <= 16 <= LPR) and is read with a cross-lane broadcast, so the register count does not grow with N.
+// No kernel in this file waits on another wave: there are no spin-waits, mailboxes or inter-wave dependencies, and
+// every loop is bounded by nchunk, N or a constant, so none of them can hang by construction.
 #include "common.h"
 
 namespace tramba {
 
 constexpr int kE = 8;        // elements per lane per chunk
-constexpr int kMaxN = 4;     // d_state supported by the generic path (Tramba uses 1)
+constexpr int kMaxN = 4;     // d_state of the compile-time-N templates, instantiated for 1, 2, 4 (Tramba uses 1)
+constexpr int kMaxDState = 16;  // d_state served in all: the others run the state-looped pair (lane n holds state n)
 constexpr int kWavesPerBlock = 4;
 
 __host__ __device__ inline int lanes_per_row(int l)
@@ -500,6 +510,486 @@ static int launch_fwd(const void *u, const void *delta, const float *A, const vo
     return TRAMBA_OK;
 }
 
+// ------------------------------------------------------------------------------------ state-looped pair (N = 3, 5..16)
+// Same chunking, checkpoints and layouts as the pair above; N is a kernel argument.  Per-(row, state) values are spread
+// over the lanes of the row: lane `sub == n` holds state n's chunk carry (forward), A, and the adjoint carries
+// (backward); row_bcast reads them.  The n loop is a plain run-time loop, so registers and code size do not grow with N.
+
+// the value lane n of this lane's row holds (n wave-uniform)
+template <int LPR>
+__device__ __forceinline__ float row_bcast(float v, int n)
+{
+    if constexpr (LPR == 64)
+        return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), n));
+    else
+        return __shfl(v, n, LPR);
+}
+
+template <typename T> struct BCRaw {
+    Pack<T, kE> B, C;
+};
+
+// B / C of (chunk, state n) for this lane, raw.  Always in bounds: the chunk is clamped to the row's first / last one;
+// 16-byte path: lanes past the row end re-read the row's tail (masked on use: dt, u and dout are 0 there); scalar path:
+// elements past the row end are not loaded and read as 0.
+template <typename T, int LPR, bool VEC>
+__device__ __forceinline__ void fetch_bc(const T *__restrict__ Br, const T *__restrict__ Cr, int chunk, int n, int sub,
+                                         int L, int nchunk, BCRaw<T> &o)
+{
+    if (chunk < 0) chunk = 0;
+    if (chunk > nchunk - 1) chunk = nchunk - 1;
+    const int lb = chunk * (LPR * kE) + sub * kE;
+    const T *bp = Br + (long)n * L, *cp = Cr + (long)n * L;
+    if constexpr (VEC) {
+        const int lmax = L >= kE ? L - kE : 0;
+        const int l0 = lb > lmax ? lmax : lb;
+        o.B = *reinterpret_cast<const Pack<T, kE> *>(bp + l0);
+        o.C = *reinterpret_cast<const Pack<T, kE> *>(cp + l0);
+    } else {
+        const T zero = Cvt<T>::from_f(0.f);
+#pragma unroll
+        for (int j = 0; j < kE; ++j) {
+            const bool ok = lb + j < L;
+            o.B.v[j] = ok ? bp[lb + j] : zero;
+            o.C.v[j] = ok ? cp[lb + j] : zero;
+        }
+    }
+}
+
+template <typename T, typename TO, int LPR, bool VEC>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves_per_eu(4))) void selective_scan_fwd_nloop_kernel(
+    const T *__restrict__ u, const T *__restrict__ delta, const float *__restrict__ A,
+    const T *__restrict__ Bm, const T *__restrict__ Cm, const float *__restrict__ Dskip,
+    const float *__restrict__ dbias, TO *__restrict__ out, float *__restrict__ ckpt, int rows_total,
+    int kd, int K, int N, int L, int nchunk, int softplus)
+{
+    constexpr int RPW = kWave / LPR;  // rows per wave
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int sub = lane % LPR;
+    const int row = wave * RPW + lane / LPR;  // rows_total is an int: so is every row index
+    const bool row_ok = row < rows_total;
+    const int rrow = row_ok ? row : 0;
+    const int b = rrow / kd, d = rrow % kd;
+    const int k = d / (kd / K);
+
+    // The row's 64-bit offsets are formed where they are used, from two ints the compiler may not look through: formed
+    // here, the per-lane pointers derived from them would all be live across the chunk loop (and spilled).
+    const int row_i = rrow, group_i = b * K + k;
+    auto offsets = [&](long &ro, long &bc, int &ri) {
+        ri = row_i;
+        int gi = group_i;
+        asm volatile("" : "+v"(ri), "+v"(gi));
+        ro = (long)ri * L;
+        bc = (long)gi * N * L;
+    };
+
+    // lane n of the row: A[d, n] * log2(e) (decay = exp2(dt * A2)) and the chunk carry of state n
+    const float A2v = sub < N ? A[(long)d * N + sub] * 1.44269504088896f : 0.f;
+    float carry = 0.f;
+    const float bias = dbias ? dbias[d] : 0.f;
+    const float skip = Dskip ? Dskip[d] : 0.f;
+
+    // u / delta: the two-stage raw ring of the kernel above (converted on use), the chunk loop unrolled by 2
+    struct Stage {
+        Pack<T, kE> u, d;
+    };
+    Stage ring[2];
+    const int lmax = L >= kE ? L - kE : 0;
+    auto fetch = [&](long ro, int chunk, Stage &st) {
+        const T *ur = u + ro, *dr = delta + ro;
+        const int cc = chunk < nchunk ? chunk : nchunk - 1;
+        if constexpr (VEC) {
+            int l0 = cc * (LPR * kE) + sub * kE;
+            if (l0 > lmax) l0 = lmax;  // lanes past the row end re-read the tail; their results are masked
+            st.u = *reinterpret_cast<const Pack<T, kE> *>(ur + l0);
+            st.d = *reinterpret_cast<const Pack<T, kE> *>(dr + l0);
+        } else {
+            const int lb = cc * (LPR * kE) + sub * kE;
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                const int l = lb + j < L ? lb + j : L - 1;
+                st.u.v[j] = ur[l];
+                st.d.v[j] = dr[l];
+            }
+        }
+    };
+    BCRaw<T> nxt;  // B / C of the state the loop computes next: one state ahead, across the chunk boundary too
+    {
+        long ro, bc;
+        int ri;
+        offsets(ro, bc, ri);
+        fetch(ro, 0, ring[0]);
+        fetch_bc<T, LPR, VEC>(Bm + bc, Cm + bc, 0, 0, sub, L, nchunk, nxt);
+    }
+
+    for (int c0 = 0; c0 < nchunk; c0 += 2) {
+#pragma unroll
+        for (int si = 0; si < 2; ++si) {
+            const int chunk = c0 + si;
+            if (chunk >= nchunk) break;  // wave-uniform
+            long ro, bc;
+            int ri;
+            offsets(ro, bc, ri);
+            const T *Br = Bm + bc, *Cr = Cm + bc;
+            TO *yr = out + ro;
+            fetch(ro, chunk + 1, ring[si ^ 1]);
+            const Stage &st = ring[si];
+            const int l0 = chunk * (LPR * kE) + sub * kE;
+            const bool ragged = (chunk + 1) * (LPR * kE) > L;  // wave-uniform; dt = 0 is the identity (a = 1, b = 0)
+            float cu[kE], dt[kE], dtu[kE], y[kE];
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                cu[j] = Cvt<T>::to_f(st.u.v[j]);
+                const float x = Cvt<T>::to_f(st.d.v[j]) + bias;
+                dt[j] = softplus ? softplus_lean(x) : x;
+            }
+            if (ragged) {
+#pragma unroll
+                for (int j = 0; j < kE; ++j)
+                    if (l0 + j >= L) dt[j] = 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                dtu[j] = dt[j] * cu[j];
+                y[j] = skip * cu[j];
+            }
+#pragma clang loop unroll(disable)
+            for (int n = 0; n < N; ++n) {
+                const BCRaw<T> cur = nxt;
+                const bool last = n + 1 == N;
+                fetch_bc<T, LPR, VEC>(Br, Cr, last ? chunk + 1 : chunk, last ? 0 : n + 1, sub, L, nchunk, nxt);
+                const float a2 = row_bcast<LPR>(A2v, n);
+                const float cin = row_bcast<LPR>(carry, n);
+                float a[kE], bb[kE];
+                float pa = 1.f, ph = 0.f;
+#pragma unroll
+                for (int j = 0; j < kE; ++j) {
+                    a[j] = __builtin_amdgcn_exp2f(dt[j] * a2);
+                    bb[j] = dtu[j] * Cvt<T>::to_f(cur.B.v[j]);
+                    ph = fmaf(a[j], ph, bb[j]);
+                    pa *= a[j];
+                }
+                row_scan<LPR>(pa, ph, sub);
+                // exclusive prefix for this lane, then fold in the chunk carry
+                float ea, eh, la, lh;
+                if constexpr (LPR == 64) {
+                    ea = dpp_move<0x138, 0xf>(1.f, pa);  // wave_shr:1, lane 0 keeps the identity
+                    eh = dpp_move<0x138, 0xf>(0.f, ph);
+                    la = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pa), 63));
+                    lh = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ph), 63));
+                } else {
+                    ea = __shfl_up(pa, 1, LPR);
+                    eh = __shfl_up(ph, 1, LPR);
+                    if (sub == 0) { ea = 1.f; eh = 0.f; }
+                    la = __shfl(pa, LPR - 1, LPR);
+                    lh = __shfl(ph, LPR - 1, LPR);
+                }
+                float h = fmaf(ea, cin, eh);
+                // new chunk carry = inclusive prefix of the row's last lane applied to the old carry; lane n keeps it
+                if (sub == n) carry = fmaf(la, cin, lh);
+#pragma unroll
+                for (int j = 0; j < kE; ++j) {
+                    h = fmaf(a[j], h, bb[j]);
+                    y[j] = fmaf(Cvt<T>::to_f(cur.C.v[j]), h, y[j]);
+                }
+            }
+            // the chunk-end states of the row, one per lane: N consecutive floats
+            if (ckpt && row_ok && sub < N) ckpt[((long)ri * nchunk + chunk) * N + sub] = carry;
+            if (row_ok) {
+                if constexpr (VEC) {
+                    if (l0 + kE <= L) store_pack<TO, kE>(yr + l0, y);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < kE; ++j)
+                        if (l0 + j < L) yr[l0 + j] = Cvt<TO>::from_f(y[j]);
+                }
+            }
+        }
+    }
+}
+
+// Backward: the adjoint of the kernel above, chunk by chunk from the right as selective_scan_bwd_kernel.  u, delta and dout
+// are fetched once per chunk; per state: the forward replay from the checkpoint, the mirrored adjoint scan, the two sums
+// du and d dt are made of accumulated per lane, the dB / dC contributions through the wave's LDS transpose buffer (reused
+// per state) as coalesced 256-byte atomics.  dA: a row sum per state and chunk, kept by lane n; one add per row and state
+// at the end, as dD and d delta_bias.
+// Registers: both kernels are built for four waves per SIMD (128 VGPRs).  What the state loop does not touch is kept out
+// of registers across it: the row's addresses are re-formed per chunk, u and delta are read a second time after the loop,
+// and the backward's two per-position accumulators live in LDS.
+template <typename T, int LPR, bool VEC>
+__global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves_per_eu(4))) void selective_scan_bwd_nloop_kernel(
+    const T *__restrict__ u, const T *__restrict__ delta, const float *__restrict__ A,
+    const T *__restrict__ Bm, const T *__restrict__ Cm, const float *__restrict__ Dskip,
+    const float *__restrict__ dbias, const float *__restrict__ dout, const float *__restrict__ ckpt,
+    T *__restrict__ du, T *__restrict__ ddelta, float *__restrict__ dA, float *__restrict__ dB,
+    float *__restrict__ dC, float *__restrict__ dD, float *__restrict__ ddbias, int rows_total, int kd,
+    int K, int N, int L, int nchunk, int softplus, int ncopy, long copy_stride)
+{
+    constexpr int RPW = kWave / LPR;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int sub = lane % LPR;
+    const int row = wave * RPW + lane / LPR;  // rows_total is an int: so is every row index
+    const bool row_ok = row < rows_total;
+    const int rrow = row_ok ? row : 0;
+    const int b = rrow / kd, d = rrow % kd;
+    const int k = d / (kd / K);
+
+    // what the row's 64-bit offsets are formed from, per chunk (see there): three ints
+    const int row_i = rrow, group_i = b * K + k;
+    const int copy_i = d % ncopy;  // this row's private dB / dC copy
+    const float bias = dbias ? dbias[d] : 0.f;
+    const float skip = Dskip ? Dskip[d] : 0.f;
+
+    __shared__ float tr[kWavesPerBlock][2][kWave * kE];
+    // the two per-position sums over the states (gB, gA below): slot [.][j][thread] is read and written by its lane only,
+    // consecutive lanes in consecutive banks; parked here because they are touched once per state, at the very end
+    __shared__ float acc[2][kE][kWavesPerBlock * kWave];
+    float *trB = tr[threadIdx.x >> 6][0], *trC = tr[threadIdx.x >> 6][1];
+    float *gB = &acc[0][0][threadIdx.x], *gA = &acc[1][0][threadIdx.x];
+    constexpr int kAcc = kWavesPerBlock * kWave;  // stride between a lane's slots
+
+    // lane n of the row: A[d, n]; g / a of the first element of the chunk to the right, state n
+    const float Av = sub < N ? A[(long)d * N + sub] : 0.f;
+    float g_carry = 0.f, a_carry = 1.f, accA = 0.f;  // accA: lane n holds dA[d, n] summed over the row so far
+    float accD = 0.f, accBias = 0.f;
+
+    for (int chunk = nchunk - 1; chunk >= 0; --chunk) {
+        const int l0 = chunk * (LPR * kE) + sub * kE;
+        // The row's offsets and addresses are formed here, per chunk, from three ints the compiler may not look through:
+        // hoisted out of the loop, the 64-bit per-lane offsets and pointers would be live across it (about 20 registers,
+        // which it then spills).  Four 64-bit multiplies per chunk instead.
+        int ri = row_i, gi = group_i, ci = copy_i;
+        asm volatile("" : "+v"(ri), "+v"(gi), "+v"(ci));
+        const long ro = (long)ri * L;
+        const long bc = (long)gi * N * L;
+        const long pc = (long)ci * copy_stride;
+        const T *ur = u + ro;
+        const T *dr = delta + ro;
+        const float *gr = dout + ro;
+        const T *Br = Bm + bc;
+        const T *Cr = Cm + bc;
+        // u and delta of this lane's 8 positions (0 past the row end)
+        // (16-byte path: L % 8 == 0, so a lane's 8 positions are all inside the row or all outside)
+        auto load_ud = [&](const T *ur, const T *dr, float (&cu)[kE], float (&cd)[kE]) {
+            if constexpr (VEC) {
+                const int lc = l0 + kE <= L ? l0 : 0;
+                load_pack<T, kE>(ur + lc, cu);
+                load_pack<T, kE>(dr + lc, cd);
+                if (l0 + kE > L) {
+#pragma unroll
+                    for (int j = 0; j < kE; ++j) cu[j] = cd[j] = 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kE; ++j) {
+                    const bool ok = l0 + j < L;
+                    cu[j] = ok ? Cvt<T>::to_f(ur[l0 + j]) : 0.f;
+                    cd[j] = ok ? Cvt<T>::to_f(dr[l0 + j]) : 0.f;
+                }
+            }
+        };
+        float go[kE], dt[kE], dtu[kE];
+        {
+            float cu[kE], cd[kE];
+            load_ud(ur, dr, cu, cd);
+            if constexpr (VEC) {
+                load_pack<float, kE>(gr + (l0 + kE <= L ? l0 : 0), go);
+                if (l0 + kE > L) {
+#pragma unroll
+                    for (int j = 0; j < kE; ++j) go[j] = 0.f;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kE; ++j) go[j] = l0 + j < L ? gr[l0 + j] : 0.f;
+            }
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                const float raw = cd[j] + bias;
+                dt[j] = softplus ? softplus20(raw) : raw;
+                if (l0 + j >= L) dt[j] = 0.f;
+                dtu[j] = dt[j] * cu[j];
+                accD = fmaf(go[j], cu[j], accD);
+            }
+        }
+        // the state entering this chunk, lane n of the row holds state n
+        const float hin = (chunk > 0 && sub < N) ? ckpt[((long)ri * nchunk + chunk - 1) * N + sub] : 0.f;
+        // Summed over the states (in LDS): gB = sum_n g_n B_n and gA = sum_n g_n h_{l-1} a_l A_n, from which
+        //     d u = dout D + dt gB        d dt = gA + u gB
+        // so that u and the raw delta are not needed inside the state loop; they are read again after it (from cache).
+        // Positions past the row end need no mask inside the loop: dout and dt (so dt u) are 0 there, and every term that
+        // leaves the loop carries one of them as a factor (B / C there are in-bounds re-reads or 0, see fetch_bc).
+#pragma unroll
+        for (int j = 0; j < kE; ++j) gB[j * kAcc] = gA[j * kAcc] = 0.f;
+#pragma clang loop unroll(disable)
+        for (int n = 0; n < N; ++n) {
+            BCRaw<T> cur;
+            fetch_bc<T, LPR, VEC>(Br, Cr, chunk, n, sub, L, nchunk, cur);
+            const float An = row_bcast<LPR>(Av, n);
+            const float hstart = row_bcast<LPR>(hin, n);
+            const float gc = row_bcast<LPR>(g_carry, n);
+            const float ac = row_bcast<LPR>(a_carry, n);
+            float cB[kE];
+#pragma unroll
+            for (int j = 0; j < kE; ++j) cB[j] = Cvt<T>::to_f(cur.B.v[j]);
+            float a[kE];
+            float pa = 1.f, ph = 0.f;
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                a[j] = __expf(dt[j] * An);
+                ph = fmaf(a[j], ph, dtu[j] * cB[j]);
+                pa *= a[j];
+            }
+            // forward replay from the checkpoint: state entering this lane
+            row_scan<LPR>(pa, ph, sub);
+            float ea = __shfl_up(pa, 1, LPR), eh = __shfl_up(ph, 1, LPR);
+            if (sub == 0) { ea = 1.f; eh = 0.f; }
+            float h = fmaf(ea, hstart, eh);
+            float ha[kE];  // h_{l-1} a_l
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                ha[j] = h * a[j];
+                h = fmaf(a[j], h, dtu[j] * cB[j]);
+                trC[lane * kE + j] = go[j] * h;
+            }
+            // adjoint scan: element j carries (a_{j+1}, C_j dout_j)
+            float cg[kE];
+#pragma unroll
+            for (int j = 0; j < kE; ++j) cg[j] = Cvt<T>::to_f(cur.C.v[j]) * go[j];
+            float a_right = __shfl_down(a[0], 1, LPR);  // first a of the lane to the right
+            if (sub == LPR - 1) a_right = ac;
+            float qa = 1.f, qg = 0.f;
+#pragma unroll
+            for (int j = kE - 1; j >= 0; --j) {
+                const float an = j + 1 < kE ? a[j + 1] : a_right;
+                qg = fmaf(an, qg, cg[j]);
+                qa *= an;
+            }
+            row_scan_rev<LPR>(qa, qg, sub);
+            float xa = __shfl_down(qa, 1, LPR), xg = __shfl_down(qg, 1, LPR);  // exclusive suffix
+            if (sub == LPR - 1) { xa = 1.f; xg = 0.f; }
+            float g = fmaf(xa, gc, xg);
+            // carries for the chunk to the left: full-row suffix applied to the old carry; lane n keeps them
+            const float fa = __shfl(qa, 0, LPR), fg = __shfl(qg, 0, LPR);
+            const float a_first = __shfl(a[0], 0, LPR);
+            if (sub == n) {
+                g_carry = fmaf(fa, gc, fg);
+                a_carry = a_first;
+            }
+            float sA = 0.f;
+#pragma unroll
+            for (int j = kE - 1; j >= 0; --j) {
+                const float an = j + 1 < kE ? a[j + 1] : a_right;
+                g = fmaf(an, g, cg[j]);  // g_j
+                const float gh = g * ha[j];
+                gB[j * kAcc] = fmaf(g, cB[j], gB[j * kAcc]);
+                gA[j * kAcc] = fmaf(gh, An, gA[j * kAcc]);
+                sA = fmaf(gh, dt[j], sA);
+                trB[lane * kE + j] = g * dtu[j];
+            }
+            sA = row_sum<LPR>(sA);
+            if (sub == n) accA += sA;
+            __builtin_amdgcn_wave_barrier();
+            if (row_ok) {
+                // lane i, step j -> element (lane/LPR)*LPR*kE + j*LPR + sub of the wave's staging area, i.e.
+                // position chunk*LPR*kE + j*LPR + sub of the row: consecutive lanes, consecutive addresses
+                const int rbase = (lane / LPR) * (LPR * kE) + sub;
+                const int lfirst = chunk * (LPR * kE) + sub;
+                float *pB = dB + pc + bc + (long)n * L + lfirst;  // one base each, the steps are constant offsets
+                float *pC = dC + pc + bc + (long)n * L + lfirst;
+#pragma unroll
+                for (int j = 0; j < kE; ++j) {
+                    if (lfirst + j * LPR < L) {
+                        atomicAdd(pB + j * LPR, trB[rbase + j * LPR]);
+                        atomicAdd(pC + j * LPR, trC[rbase + j * LPR]);
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        float odu[kE], odd[kE];
+        {
+            // read again, not kept: through an offset the compiler cannot prove equal to `ro`, or it would merge this
+            // read with the one before the loop and hold its 16 registers across it
+            int ri2 = row_i;
+            asm volatile("" : "+v"(ri2));
+            const long ro2 = (long)ri2 * L;
+            float cu[kE], cd[kE];
+            load_ud(u + ro2, delta + ro2, cu, cd);
+#pragma unroll
+            for (int j = 0; j < kE; ++j) {
+                const float raw = cd[j] + bias;
+                const float gb = gB[j * kAcc];
+                odu[j] = fmaf(dt[j], gb, go[j] * skip);
+                float dr_ = fmaf(cu[j], gb, gA[j * kAcc]);
+                if (softplus && raw <= 20.f) dr_ *= sigmoidf_(raw);
+                odd[j] = l0 + j < L ? dr_ : 0.f;
+                accBias += odd[j];
+            }
+        }
+        if (row_ok) {
+            if constexpr (VEC) {
+                if (l0 + kE <= L) {
+                    store_pack<T, kE>(du + ro + l0, odu);
+                    store_pack<T, kE>(ddelta + ro + l0, odd);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < kE; ++j)
+                    if (l0 + j < L) {
+                        du[ro + l0 + j] = Cvt<T>::from_f(odu[j]);
+                        ddelta[ro + l0 + j] = Cvt<T>::from_f(odd[j]);
+                    }
+            }
+        }
+    }
+    accD = row_sum<LPR>(accD);
+    accBias = row_sum<LPR>(accBias);
+    // the row's channel again, from the opaque int: kept from the prologue, d and the addresses formed from it would be
+    // live (and spilled) across the whole kernel
+    int ri = row_i;
+    asm volatile("" : "+v"(ri));
+    const int de = ri % kd;
+    if (row_ok && sub < N) atomicAdd(dA + (long)de * N + sub, accA);
+    if (row_ok && sub == 0) {
+        if (dD) atomicAdd(dD + de, accD);
+        if (ddbias) atomicAdd(ddbias + de, accBias);
+    }
+}
+
+template <typename T, typename TO>
+static int launch_fwd_nloop(const void *u, const void *delta, const float *A, const void *Bm, const void *Cm,
+                            const float *D, const float *bias, void *out, float *ckpt, int batch, int kd, int K, int N,
+                            int L, int softplus, hipStream_t s)
+{
+    const int lpr = lanes_per_row(L);
+    const int nchunk = (L + lpr * kE - 1) / (lpr * kE);
+    const long rows = (long)batch * kd;
+    const int rpw = kWave / lpr;
+    const long waves = (rows + rpw - 1) / rpw;
+    const long blocks = (waves + kWavesPerBlock - 1) / kWavesPerBlock;
+    const int vec_ok = (L % kE == 0) && aligned16(u) && aligned16(delta) && aligned16(Bm) &&
+                       aligned16(Cm) && aligned16(out);
+    dim3 grid((unsigned)blocks), block(kWavesPerBlock * kWave);
+#define LAUNCH_(LPR_, VEC_)                                                                                     \
+    hipLaunchKernelGGL((selective_scan_fwd_nloop_kernel<T, TO, LPR_, VEC_>), grid, block, 0, s, (const T *)u,   \
+                       (const T *)delta, A, (const T *)Bm, (const T *)Cm, D, bias, (TO *)out, ckpt, (int)rows,  \
+                       kd, K, N, L, nchunk, softplus)
+    if (vec_ok) {
+        if (lpr == 16) LAUNCH_(16, true);
+        else if (lpr == 32) LAUNCH_(32, true);
+        else LAUNCH_(64, true);
+    } else {
+        if (lpr == 16) LAUNCH_(16, false);
+        else if (lpr == 32) LAUNCH_(32, false);
+        else LAUNCH_(64, false);
+    }
+#undef LAUNCH_
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
 }  // namespace tramba
 
 using namespace tramba;
@@ -521,7 +1011,7 @@ extern "C" int tramba_selective_scan_fwd(const void *u, const void *delta, const
     TRAMBA_CHECK(u && delta && A && Bm && Cm && out, "selective_scan_fwd: null tensor");
     TRAMBA_CHECK(batch > 0 && kd > 0 && k > 0 && l > 0, "selective_scan_fwd: empty shape");
     TRAMBA_CHECK(kd % k == 0, "selective_scan_fwd: KD=%d is not a multiple of K=%d", kd, k);
-    TRAMBA_CHECK(n >= 1 && n <= kMaxN, "selective_scan_fwd: d_state=%d unsupported (1..%d)", n, kMaxN);
+    TRAMBA_CHECK(n >= 1 && n <= kMaxDState, "selective_scan_fwd: d_state=%d unsupported (1..%d)", n, kMaxDState);
     TRAMBA_CHECK(out_dtype == TRAMBA_F32 || out_dtype == io_dtype,
                  "selective_scan_fwd: out dtype must be f32 (oflex) or the input dtype");
     hipStream_t s = (hipStream_t)stream;
@@ -536,8 +1026,9 @@ extern "C" int tramba_selective_scan_fwd(const void *u, const void *delta, const
     case 1: GO_(T, TO, 1);                                                     \
     case 2: GO_(T, TO, 2);                                                     \
     case 4: GO_(T, TO, 4);                                                     \
-    default: set_error("selective_scan_fwd: d_state=%d not instantiated (1,2,4)", n); \
-             return TRAMBA_ERR_UNSUPPORTED;                                    \
+    default: /* 3, 5..16: the state-looped kernel */                           \
+        return launch_fwd_nloop<T, TO>(u, delta, A, Bm, Cm, D, delta_bias, out, ckpt, batch, kd, k, n, l, \
+                                       delta_softplus, s);                     \
     }
     TRAMBA_DISPATCH_DTYPE(io_dtype, T, {
         if (out_dtype == TRAMBA_F32) { BY_N_(T, float) } else { BY_N_(T, T) }
@@ -559,10 +1050,7 @@ extern "C" int tramba_selective_scan_bwd(const void *u, const void *delta, const
     TRAMBA_CHECK(batch > 0 && kd > 0 && k > 0 && l > 0, "selective_scan_bwd: empty shape");
     TRAMBA_CHECK(kd % k == 0, "selective_scan_bwd: KD=%d is not a multiple of K=%d", kd, k);
     TRAMBA_CHECK(ncopy >= 1, "selective_scan_bwd: ncopy must be >= 1");
-    if (n != 1 && n != 2 && n != 4) {
-        set_error("selective_scan_bwd: d_state=%d not instantiated (1,2,4)", n);
-        return TRAMBA_ERR_UNSUPPORTED;
-    }
+    TRAMBA_CHECK(n >= 1 && n <= kMaxDState, "selective_scan_bwd: d_state=%d unsupported (1..%d)", n, kMaxDState);
     hipStream_t s = (hipStream_t)stream;
     const int lpr = lanes_per_row(l);
     const int nchunk = (l + lpr * kE - 1) / (lpr * kE);
@@ -578,17 +1066,30 @@ extern "C" int tramba_selective_scan_bwd(const void *u, const void *delta, const
                        A, (const T *)Bm, (const T *)Cm, D, delta_bias, dout, ckpt, (T *)du, (T *)ddelta, dA, dB,    \
                        dC, dD, ddelta_bias, (int)rows, kd, k, l, nchunk, delta_softplus, vec_ok, ncopy,             \
                        (long)batch * k * n * l)
+#define LAUNCH_LOOP_V_(T, LPR_, VEC_)                                                                              \
+    hipLaunchKernelGGL((selective_scan_bwd_nloop_kernel<T, LPR_, VEC_>), grid, block, 0, s, (const T *)u,          \
+                       (const T *)delta, A, (const T *)Bm, (const T *)Cm, D, delta_bias, dout, ckpt, (T *)du,      \
+                       (T *)ddelta, dA, dB, dC, dD, ddelta_bias, (int)rows, kd, k, n, l, nchunk, delta_softplus,   \
+                       ncopy, (long)batch * k * n * l)
+#define LAUNCH_LOOP_(T, LPR_)                          \
+    if (vec_ok) { LAUNCH_LOOP_V_(T, LPR_, true); }     \
+    else { LAUNCH_LOOP_V_(T, LPR_, false); }
 #define LAUNCH_(T, LPR_)                                        \
     if (n == 1) { LAUNCH_N_(T, LPR_, 1); }                      \
     else if (n == 2) { LAUNCH_N_(T, LPR_, 2); }                 \
-    else { LAUNCH_N_(T, LPR_, 4); }
+    else if (n == 4) { LAUNCH_N_(T, LPR_, 4); }                 \
+    else { LAUNCH_LOOP_(T, LPR_); }   /* 3, 5..16: the state-looped kernel */
     TRAMBA_DISPATCH_DTYPE(io_dtype, T, {
         if (lpr == 16) { LAUNCH_(T, 16) }
         else if (lpr == 32) { LAUNCH_(T, 32) }
         else { LAUNCH_(T, 64) }
     });
 #undef LAUNCH_
+#undef LAUNCH_LOOP_
+#undef LAUNCH_LOOP_V_
 #undef LAUNCH_N_
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
+
+extern "C" int tramba_selective_scan_max_dstate(void) { return kMaxDState; }

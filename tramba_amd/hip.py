@@ -41,6 +41,7 @@ SIGNATURES = {
     "tramba_scan_table": (c_int, [c_int, c_int, c_int, c_int, c_vp]),
     "tramba_scan_table_inverse": (c_int, [c_vp, c_int, c_int, c_vp, c_vp]),
     "tramba_selective_scan_nchunk": (c_int, [c_int, c_int]),
+    "tramba_selective_scan_max_dstate": (c_int, []),
     "tramba_selective_scan_fwd": (c_int, [c_vp] * 9 + [c_int] * 8 + [c_vp]),
     "tramba_selective_scan_bwd": (c_int, [c_vp] * 16 + [c_int] * 8 + [c_vp]),
     "tramba_cross_scan": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
@@ -332,10 +333,31 @@ def selective_scan_nchunk(l: int, dtype: torch.dtype) -> int:
     return lib().tramba_selective_scan_nchunk(l, _DT[dtype])
 
 
+def selective_scan_max_dstate() -> int:
+    return lib().tramba_selective_scan_max_dstate()
+
+
+def _check_dstate(n, what):
+    top = selective_scan_max_dstate()
+    if not 1 <= n <= top:
+        raise TrambaHipError(f"{what}: d_state={n} unsupported (1..{top})")
+
+
+def scan_bc_copies(kd: int, k: int, n: int) -> int:
+    """private dB / dC copies of selective_scan_bwd: at most 1/8 of a group's rows add into one address, up to 16 copies;
+    for d_state > 4 also ncopy * N <= 64, so that the (ncopy, B, K, N, L) fp32 workspace never exceeds what N = 4 takes at
+    the same shape"""
+    ncopy = max(1, min(16, (kd // k) // 8))
+    if n > 4:
+        ncopy = max(1, min(ncopy, 64 // n))
+    return ncopy
+
+
 def selective_scan_fwd(u, delta, A, B, C, D, delta_bias, delta_softplus=True, oflex=True, want_ckpt=True):
     _dev(u, delta, A, B, C, D, delta_bias)
     nb, kd, l = u.shape
     k, n = B.shape[1], B.shape[2]
+    _check_dstate(n, "selective_scan_fwd")
     if delta.shape != u.shape or A.shape != (kd, n) or B.shape != (nb, k, n, l) or C.shape != B.shape:
         raise TrambaHipError(f"selective_scan_fwd: inconsistent shapes u{tuple(u.shape)} delta{tuple(delta.shape)} "
                              f"A{tuple(A.shape)} B{tuple(B.shape)} C{tuple(C.shape)}")
@@ -356,11 +378,12 @@ def selective_scan_bwd(u, delta, A, B, C, D, delta_bias, dout, ckpt, delta_softp
     _dev(u, delta, A, B, C, D, delta_bias, dout, ckpt)
     nb, kd, l = u.shape
     k, n = B.shape[1], B.shape[2]
+    _check_dstate(n, "selective_scan_bwd")
     A32, D32, b32 = _f32(A), _f32(D), _f32(delta_bias)
     dout = dout.float().contiguous()
     du, ddelta = torch.empty_like(u), torch.empty_like(delta)
     dA = torch.zeros((kd, n), dtype=torch.float32, device=u.device)
-    ncopy = max(1, min(16, (kd // k) // 8))  # private dB/dC copies: <= 1/8 of a group's rows per address
+    ncopy = scan_bc_copies(kd, k, n)  # private dB/dC copies: <= 1/8 of a group's rows per address
     dB = torch.zeros((ncopy, nb, k, n, l), dtype=torch.float32, device=u.device)
     dC = torch.zeros_like(dB)
     dD = torch.zeros(kd, dtype=torch.float32, device=u.device) if D is not None else None
