@@ -180,6 +180,24 @@ int tramba_selective_scan_bwd(const void *u, const void *delta, const float *A, 
                               float *dA, float *dB, float *dC, float *dD, float *ddelta_bias,
                               int batch, int kd, int k, int n, int l, int io_dtype,
                               int delta_softplus, int ncopy, void *stream);
+/* The deterministic (atomic-free) form of tramba_selective_scan_bwd: same inputs, same seven outputs in the same dtypes
+ * and shapes -- dA (KD,N), dB, dC (B, K, N, L), dD, ddelta_bias (KD) -- every element WRITTEN (the caller zeroes nothing),
+ * each a function of the inputs and the shape alone: no atomics, fixed summation order (bitwise reproducible).  First
+ * launch: one workgroup per (batch, group, slab of S = 512 / LPR consecutive rows of the group's KD/K -- eight waves; LPR = 64
+ * lanes per row for L > 256, 32 for L > 128, else 16, so S = 8, 16 or 32) sums its rows' dB / dC contributions in LDS in ascending row order and stores
+ * one partial row per slab; dA, dD, ddelta_bias leave as per-row partials.  Second launch: dB, dC = the ascending-slab
+ * sum, dA, dD, ddelta_bias = the ascending-batch sum, in f32.  The caller allocates the workspace;
+ * tramba_selective_scan_bwd_det_work returns its size in bytes (negative on bad arguments),
+ *     4 * (2 * ceil((KD/K) / S) * B*K*N*L + B*KD*(N + 2)),
+ * i.e. per tensor at most ceil((KD/K) / 4) copies of (B, K, N, L) f32, and the entry checks work_bytes against it.  The
+ * contents of the workspace on entry do not matter.  No allocation or synchronisation (capturable). */
+int64_t tramba_selective_scan_bwd_det_work(int batch, int kd, int k, int n, int l, int io_dtype);
+int tramba_selective_scan_bwd_det(const void *u, const void *delta, const float *A, const void *Bm,
+                                  const void *Cm, const float *D, const float *delta_bias,
+                                  const float *dout, const float *ckpt, void *du, void *ddelta,
+                                  float *dA, float *dB, float *dC, float *dD, float *ddelta_bias,
+                                  void *work, size_t work_bytes, int batch, int kd, int k, int n, int l,
+                                  int io_dtype, int delta_softplus, void *stream);
 
 /* ------------------------------------------------------------------ L1: scan-order gather / merge, NCHW */
 /* xs[b,k,c,l] = x[b,c,table[k,l]];  x: (B, C, L), xs: (B, K, C, L);  table: DEVICE int32 (K, L). */

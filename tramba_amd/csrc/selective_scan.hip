@@ -27,6 +27,9 @@
 // n; N <= 16 <= LPR) and is read with a cross-lane broadcast, so the register count does not grow with N.
 // No kernel in this file waits on another wave: there are no spin-waits, mailboxes or inter-wave dependencies, and
 // every loop is bounded by nchunk, N or a constant, so none of them can hang by construction.
+// The deterministic backward (template switch DET, tramba_selective_scan_bwd_det) adds two workgroup barriers per
+// (chunk, state) around the in-LDS row sum that replaces the atomics: nchunk and N are uniform over the workgroup and no
+// wave returns early, so every wave reaches every barrier; it still waits on nothing outside its own workgroup.
 #include "common.h"
 
 namespace tramba {
@@ -279,8 +282,69 @@ __device__ __forceinline__ float row_sum(float v)
     return v;
 }
 
-template <typename T, int LPR, int N>
-__global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_kernel(
+// ---- the deterministic (atomic-free) form of both backward kernels: the template switch DET.
+// Launch: one workgroup per (batch b, group k, slab of kDetSlab<LPR, WPB> = WPB * 64 / LPR consecutive rows of the
+// group's dper = KD/K), blockIdx.x = (b * K + k) * nslab + slab: no workgroup straddles a group or a batch.  Rows of the
+// last slab past dper run every loop and barrier on the data of the group's first row with dout read as 0, so that all
+// they stage is 0, and store nothing.  Per (chunk, state) every wave stages its rows' dB / dC contributions in LDS as
+// the atomic form does; after a workgroup barrier the workgroup sums the staged rows in ascending row order and writes
+// ONE partial row per slab with plain coalesced stores into part[slab][b][k][n][l]; a second workgroup barrier keeps the
+// next state's staging from overwriting rows still being summed.  dA per (b, d, n), dD and d delta_bias per (b, d) leave
+// as per-row partials with plain stores.  selective_scan_bwd_det_reduce_kernel then adds the slabs (dB, dC) and the
+// batches (dA, dD, d delta_bias) in ascending order, so every output is a function of the inputs and the shape alone.
+// The two barriers per (chunk, state) sit in loops bounded by nchunk and N, which are kernel arguments (uniform over the
+// workgroup), and no wave leaves the kernel early: every barrier is reached by every wave, and the statement of the file
+// header holds for this form too -- no spin-waits, no mailboxes, no dependency between workgroups, nothing that can hang.
+constexpr int kDetWaves = 8;  // waves per workgroup of the deterministic form: measured against 4, faster
+                               // at every N and half the slabs, i.e. half the workspace
+template <int LPR, int WPB> constexpr int kDetSlab = WPB * (kWave / LPR);
+
+// (b, group, row) of this lane in the deterministic launch; `nslab` slabs per group.  row_ok = false: past the group's end.
+struct DetRow {
+    int b, k, d, slab;
+    bool row_ok;
+};
+template <int LPR, int WPB>
+__device__ __forceinline__ DetRow det_row(int kd, int K, int nslab)
+{
+    DetRow r;
+    const int dper = kd / K;
+    const int grp = blockIdx.x / nslab;
+    r.slab = blockIdx.x % nslab;
+    r.b = grp / K;
+    r.k = grp % K;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int rg = r.slab * kDetSlab<LPR, WPB> + (threadIdx.x >> 6) * (kWave / LPR) + lane / LPR;
+    r.row_ok = rg < dper;
+    r.d = r.k * dper + (r.row_ok ? rg : 0);
+    return r;
+}
+
+// The workgroup's staged dB / dC rows of one (chunk, state), summed in ascending row order, to the slab's partial row.
+// tr[wave][0 = dB, 1 = dC][row of the wave * LPR * kE + position]; consecutive threads take consecutive positions (LDS
+// bank-conflict free, 256-byte global stores per wave).  Call between two __syncthreads().
+template <int LPR, int WPB>
+__device__ __forceinline__ void det_slab_store(const float (*tr)[2][kWave * kE], float *__restrict__ pB,
+                                               float *__restrict__ pC, int chunk, int L)
+{
+    constexpr int P = LPR * kE;  // positions of a chunk
+    constexpr int RPW = kWave / LPR;
+#pragma unroll
+    for (int e = threadIdx.x; e < 2 * P; e += WPB * kWave) {
+        const int t = e / P, p = e % P;
+        float s = tr[0][t][p];
+#pragma unroll
+        for (int r = 1; r < WPB * RPW; ++r) s += tr[r / RPW][t][(r % RPW) * P + p];
+        const int l = chunk * P + p;
+        if (l < L) (t ? pC : pB)[l] = s;
+    }
+}
+
+// DET = false: the atomic form (the default).  DET = true: the deterministic form above; then `ncopy` is the number of
+// slabs per group, `copy_stride` the floats between two slabs' partials, dB / dC point at part[0], dA at the per-row
+// partials (B, KD, N), dD / ddbias at (B, KD), and rows_total is unused.
+template <typename T, int LPR, int N, bool DET = false, int WPB = kWavesPerBlock>
+__global__ __launch_bounds__(WPB * kWave) void selective_scan_bwd_kernel(
     const T *__restrict__ u, const T *__restrict__ delta, const float *__restrict__ A,
     const T *__restrict__ Bm, const T *__restrict__ Cm, const float *__restrict__ Dskip,
     const float *__restrict__ dbias, const float *__restrict__ dout, const float *__restrict__ ckpt,
@@ -292,13 +356,14 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
     // B, C (B, K, N, L), A (KD, N), the forward's checkpoints (rows, nchunk, N).
     constexpr int RPW = kWave / LPR;
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int wave = blockIdx.x * WPB + (threadIdx.x >> 6);
     const int sub = lane % LPR;
     const long row = (long)wave * RPW + lane / LPR;
-    const bool row_ok = row < rows_total;
-    const long rrow = row_ok ? row : 0;
-    const int b = (int)(rrow / kd), d = (int)(rrow % kd);
-    const int k = d / (kd / K);
+    const DetRow dr_ = DET ? det_row<LPR, WPB>(kd, K, ncopy) : DetRow{};
+    const bool row_ok = DET ? dr_.row_ok : row < rows_total;
+    const long rrow = DET ? (long)dr_.b * kd + dr_.d : (row_ok ? row : 0);
+    const int b = DET ? dr_.b : (int)(rrow / kd), d = DET ? dr_.d : (int)(rrow % kd);
+    const int k = DET ? dr_.k : d / (kd / K);
 
     const T *ur = u + rrow * L;
     const T *dr = delta + rrow * L;
@@ -308,7 +373,8 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
     const T *Cr = Cm + bc;
     // dB/dC are shared by the KD/K rows of a group: spread the adds over `ncopy` private copies
     // (summed by the caller) so that KD/K/ncopy, not KD/K, rows contend for one address
-    const long pc = (long)(d % ncopy) * copy_stride;
+    // (DET: the slab's partial)
+    const long pc = (long)(DET ? dr_.slab : d % ncopy) * copy_stride;
     float An[N];
 #pragma unroll
     for (int n = 0; n < N; ++n) An[n] = A[(long)d * N + n];
@@ -318,7 +384,7 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
     // dB/dC contributions leave through LDS so that every atomic wave-instruction adds 64 CONSECUTIVE
     // floats (256 contiguous bytes): in registers lane i holds elements 8i..8i+7, which as atomics would be
     // 64 scattered 4-byte adds per instruction (an order of magnitude slower, MI355X global float atomics)
-    __shared__ float tr[kWavesPerBlock][2][kWave * kE];
+    __shared__ float tr[WPB][2][kWave * kE];
     float *trB = tr[threadIdx.x >> 6][0], *trC = tr[threadIdx.x >> 6][1];
 
     float g_carry[N], a_carry[N], accA[N];   // g / a of the first element of the chunk to the right, per component
@@ -344,6 +410,12 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
                 cu[j] = ok ? Cvt<T>::to_f(ur[l0 + j]) : 0.f;
                 cd[j] = ok ? Cvt<T>::to_f(dr[l0 + j]) : 0.f;
                 go[j] = ok ? gr[l0 + j] : 0.f;
+            }
+        }
+        if constexpr (DET) {  // a row past the group's end: dout = 0, so g = 0 and everything it stages is 0
+            if (!row_ok) {
+#pragma unroll
+                for (int j = 0; j < kE; ++j) go[j] = 0.f;
             }
         }
         float dt[kE], raw[kE], odu[kE], ddt[kE];
@@ -426,22 +498,28 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
                 trB[lane * kE + j] = ok ? g * dt[j] * cu[j] : 0.f;
                 trC[lane * kE + j] = ok ? go[j] * hcur[j] : 0.f;
             }
-            __builtin_amdgcn_wave_barrier();
-            if (row_ok) {
-                // lane i, step j -> element (lane/LPR)*LPR*kE + j*LPR + sub of the wave's staging area, i.e.
-                // position chunk*LPR*kE + j*LPR + sub of the row: consecutive lanes, consecutive addresses
-                const int rbase = (lane / LPR) * (LPR * kE);
+            if constexpr (DET) {
+                __syncthreads();  // every wave's rows are staged
+                det_slab_store<LPR, WPB>(tr, dB + pc + bc + (long)n * L, dC + pc + bc + (long)n * L, chunk, L);
+                __syncthreads();  // ... and summed before the next state stages again
+            } else {
+                __builtin_amdgcn_wave_barrier();
+                if (row_ok) {
+                    // lane i, step j -> element (lane/LPR)*LPR*kE + j*LPR + sub of the wave's staging area, i.e.
+                    // position chunk*LPR*kE + j*LPR + sub of the row: consecutive lanes, consecutive addresses
+                    const int rbase = (lane / LPR) * (LPR * kE);
 #pragma unroll
-                for (int j = 0; j < kE; ++j) {
-                    const int e = j * LPR + sub;
-                    const int l = chunk * (LPR * kE) + e;
-                    if (l < L) {
-                        atomicAdd(dB + pc + bc + (long)n * L + l, trB[rbase + e]);
-                        atomicAdd(dC + pc + bc + (long)n * L + l, trC[rbase + e]);
+                    for (int j = 0; j < kE; ++j) {
+                        const int e = j * LPR + sub;
+                        const int l = chunk * (LPR * kE) + e;
+                        if (l < L) {
+                            atomicAdd(dB + pc + bc + (long)n * L + l, trB[rbase + e]);
+                            atomicAdd(dC + pc + bc + (long)n * L + l, trC[rbase + e]);
+                        }
                     }
                 }
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_wave_barrier();
         }
         float odd[kE];
 #pragma unroll
@@ -470,11 +548,19 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) void selective_scan_bwd_ker
 #pragma unroll
     for (int n = 0; n < N; ++n) {
         const float sA = row_sum<LPR>(accA[n]);
-        if (row_ok && sub == 0) atomicAdd(dA + (long)d * N + n, sA);
+        if (row_ok && sub == 0) {
+            if constexpr (DET) dA[rrow * N + n] = sA;
+            else atomicAdd(dA + (long)d * N + n, sA);
+        }
     }
     if (row_ok && sub == 0) {
-        if (dD) atomicAdd(dD + d, accD);
-        if (ddbias) atomicAdd(ddbias + d, accBias);
+        if constexpr (DET) {
+            if (dD) dD[rrow] = accD;
+            if (ddbias) ddbias[rrow] = accBias;
+        } else {
+            if (dD) atomicAdd(dD + d, accD);
+            if (ddbias) atomicAdd(ddbias + d, accBias);
+        }
     }
 }
 
@@ -717,8 +803,10 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves
 // Registers: both kernels are built for four waves per SIMD (128 VGPRs).  What the state loop does not touch is kept out
 // of registers across it: the row's addresses are re-formed per chunk, u and delta are read a second time after the loop,
 // and the backward's two per-position accumulators live in LDS.
-template <typename T, int LPR, bool VEC>
-__global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves_per_eu(4))) void selective_scan_bwd_nloop_kernel(
+// DET: the deterministic form, with the launch layout, the arguments and the two workgroup barriers per (chunk, state) of
+// selective_scan_bwd_kernel<.., DET = true> (see there).
+template <typename T, int LPR, bool VEC, bool DET = false, int WPB = kWavesPerBlock>
+__global__ __launch_bounds__(WPB * kWave) __attribute__((amdgpu_waves_per_eu(4))) void selective_scan_bwd_nloop_kernel(
     const T *__restrict__ u, const T *__restrict__ delta, const float *__restrict__ A,
     const T *__restrict__ Bm, const T *__restrict__ Cm, const float *__restrict__ Dskip,
     const float *__restrict__ dbias, const float *__restrict__ dout, const float *__restrict__ ckpt,
@@ -728,27 +816,28 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves
 {
     constexpr int RPW = kWave / LPR;
     const int lane = threadIdx.x & (kWave - 1);
-    const int wave = blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const int wave = blockIdx.x * WPB + (threadIdx.x >> 6);
     const int sub = lane % LPR;
     const int row = wave * RPW + lane / LPR;  // rows_total is an int: so is every row index
-    const bool row_ok = row < rows_total;
-    const int rrow = row_ok ? row : 0;
-    const int b = rrow / kd, d = rrow % kd;
-    const int k = d / (kd / K);
+    const DetRow dr_ = DET ? det_row<LPR, WPB>(kd, K, ncopy) : DetRow{};
+    const bool row_ok = DET ? dr_.row_ok : row < rows_total;
+    const int rrow = DET ? dr_.b * kd + dr_.d : (row_ok ? row : 0);
+    const int b = DET ? dr_.b : rrow / kd, d = DET ? dr_.d : rrow % kd;
+    const int k = DET ? dr_.k : d / (kd / K);
 
     // what the row's 64-bit offsets are formed from, per chunk (see there): three ints
     const int row_i = rrow, group_i = b * K + k;
-    const int copy_i = d % ncopy;  // this row's private dB / dC copy
+    const int copy_i = DET ? dr_.slab : d % ncopy;  // this row's private dB / dC copy (DET: the slab's partial)
     const float bias = dbias ? dbias[d] : 0.f;
     const float skip = Dskip ? Dskip[d] : 0.f;
 
-    __shared__ float tr[kWavesPerBlock][2][kWave * kE];
+    __shared__ float tr[WPB][2][kWave * kE];
     // the two per-position sums over the states (gB, gA below): slot [.][j][thread] is read and written by its lane only,
     // consecutive lanes in consecutive banks; parked here because they are touched once per state, at the very end
-    __shared__ float acc[2][kE][kWavesPerBlock * kWave];
+    __shared__ float acc[2][kE][WPB * kWave];
     float *trB = tr[threadIdx.x >> 6][0], *trC = tr[threadIdx.x >> 6][1];
     float *gB = &acc[0][0][threadIdx.x], *gA = &acc[1][0][threadIdx.x];
-    constexpr int kAcc = kWavesPerBlock * kWave;  // stride between a lane's slots
+    constexpr int kAcc = WPB * kWave;  // stride between a lane's slots
 
     // lane n of the row: A[d, n]; g / a of the first element of the chunk to the right, state n
     const float Av = sub < N ? A[(long)d * N + sub] : 0.f;
@@ -803,6 +892,12 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves
             } else {
 #pragma unroll
                 for (int j = 0; j < kE; ++j) go[j] = l0 + j < L ? gr[l0 + j] : 0.f;
+            }
+            if constexpr (DET) {  // a row past the group's end: dout = 0, so g = 0 and everything it stages is 0
+                if (!row_ok) {
+#pragma unroll
+                    for (int j = 0; j < kE; ++j) go[j] = 0.f;
+                }
             }
 #pragma unroll
             for (int j = 0; j < kE; ++j) {
@@ -890,23 +985,29 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves
             }
             sA = row_sum<LPR>(sA);
             if (sub == n) accA += sA;
-            __builtin_amdgcn_wave_barrier();
-            if (row_ok) {
-                // lane i, step j -> element (lane/LPR)*LPR*kE + j*LPR + sub of the wave's staging area, i.e.
-                // position chunk*LPR*kE + j*LPR + sub of the row: consecutive lanes, consecutive addresses
-                const int rbase = (lane / LPR) * (LPR * kE) + sub;
-                const int lfirst = chunk * (LPR * kE) + sub;
-                float *pB = dB + pc + bc + (long)n * L + lfirst;  // one base each, the steps are constant offsets
-                float *pC = dC + pc + bc + (long)n * L + lfirst;
+            if constexpr (DET) {
+                __syncthreads();  // every wave's rows are staged
+                det_slab_store<LPR, WPB>(tr, dB + pc + bc + (long)n * L, dC + pc + bc + (long)n * L, chunk, L);
+                __syncthreads();  // ... and summed before the next state stages again
+            } else {
+                __builtin_amdgcn_wave_barrier();
+                if (row_ok) {
+                    // lane i, step j -> element (lane/LPR)*LPR*kE + j*LPR + sub of the wave's staging area, i.e.
+                    // position chunk*LPR*kE + j*LPR + sub of the row: consecutive lanes, consecutive addresses
+                    const int rbase = (lane / LPR) * (LPR * kE) + sub;
+                    const int lfirst = chunk * (LPR * kE) + sub;
+                    float *pB = dB + pc + bc + (long)n * L + lfirst;  // one base each, the steps are constant offsets
+                    float *pC = dC + pc + bc + (long)n * L + lfirst;
 #pragma unroll
-                for (int j = 0; j < kE; ++j) {
-                    if (lfirst + j * LPR < L) {
-                        atomicAdd(pB + j * LPR, trB[rbase + j * LPR]);
-                        atomicAdd(pC + j * LPR, trC[rbase + j * LPR]);
+                    for (int j = 0; j < kE; ++j) {
+                        if (lfirst + j * LPR < L) {
+                            atomicAdd(pB + j * LPR, trB[rbase + j * LPR]);
+                            atomicAdd(pC + j * LPR, trC[rbase + j * LPR]);
+                        }
                     }
                 }
+                __builtin_amdgcn_wave_barrier();
             }
-            __builtin_amdgcn_wave_barrier();
         }
         float odu[kE], odd[kE];
         {
@@ -950,11 +1051,19 @@ __global__ __launch_bounds__(kWavesPerBlock * kWave) __attribute__((amdgpu_waves
     // live (and spilled) across the whole kernel
     int ri = row_i;
     asm volatile("" : "+v"(ri));
-    const int de = ri % kd;
-    if (row_ok && sub < N) atomicAdd(dA + (long)de * N + sub, accA);
-    if (row_ok && sub == 0) {
-        if (dD) atomicAdd(dD + de, accD);
-        if (ddbias) atomicAdd(ddbias + de, accBias);
+    if constexpr (DET) {  // per-row partials, (B, KD, N) and (B, KD)
+        if (row_ok && sub < N) dA[(long)ri * N + sub] = accA;
+        if (row_ok && sub == 0) {
+            if (dD) dD[ri] = accD;
+            if (ddbias) ddbias[ri] = accBias;
+        }
+    } else {
+        const int de = ri % kd;
+        if (row_ok && sub < N) atomicAdd(dA + (long)de * N + sub, accA);
+        if (row_ok && sub == 0) {
+            if (dD) atomicAdd(dD + de, accD);
+            if (ddbias) atomicAdd(ddbias + de, accBias);
+        }
     }
 }
 
@@ -989,6 +1098,54 @@ static int launch_fwd_nloop(const void *u, const void *delta, const float *A, co
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
+
+// ------------------------------------------------------------------------------------ deterministic backward: the sum pass
+// Second launch of tramba_selective_scan_bwd_det.  Up to five independent sums, one per blockIdx.y: dst[i] = src[0][i] +
+// src[1][i] + ... + src[copies - 1][i] in ascending copy order, fp32 (dB, dC over the slabs; dA, dD, d delta_bias over
+// the batch).  Every element of dst is written.  16-byte accesses where count % 4 == 0 and both ends are aligned.
+constexpr int kDetSums = 5;
+struct DetSum {
+    const float *src;  // (copies, count)
+    float *dst;        // (count); NULL: nothing to do (the scan kernel wrote the output itself, or the output is absent)
+    long count;
+    int copies;
+    int vec;  // count % 4 == 0 and src, dst 16-byte aligned (set by the host)
+};
+struct DetSums {
+    DetSum s[kDetSums];
+};
+
+__global__ __launch_bounds__(256) void selective_scan_bwd_det_reduce_kernel(DetSums args)
+{
+    const DetSum s = args.s[blockIdx.y];
+    if (!s.dst) return;
+    const long stride = (long)gridDim.x * blockDim.x;
+    const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s.vec) {
+        const long count4 = s.count / 4;
+        for (long i = first; i < count4; i += stride) {
+            float4 acc = reinterpret_cast<const float4 *>(s.src)[i];
+            for (int c = 1; c < s.copies; ++c) {
+                const float4 v = reinterpret_cast<const float4 *>(s.src + (long)c * s.count)[i];
+                acc.x += v.x;
+                acc.y += v.y;
+                acc.z += v.z;
+                acc.w += v.w;
+            }
+            reinterpret_cast<float4 *>(s.dst)[i] = acc;
+        }
+    } else {
+        for (long i = first; i < s.count; i += stride) {
+            float acc = s.src[i];
+            for (int c = 1; c < s.copies; ++c) acc += s.src[(long)c * s.count + i];
+            s.dst[i] = acc;
+        }
+    }
+}
+
+// rows of a group one workgroup of the deterministic backward covers, and the slabs per group
+static int det_slab_rows(int l) { return kDetWaves * (kWave / lanes_per_row(l)); }
+static int det_nslab(int kd, int k, int l) { return (kd / k + det_slab_rows(l) - 1) / det_slab_rows(l); }
 
 }  // namespace tramba
 
@@ -1088,6 +1245,106 @@ extern "C" int tramba_selective_scan_bwd(const void *u, const void *delta, const
 #undef LAUNCH_LOOP_
 #undef LAUNCH_LOOP_V_
 #undef LAUNCH_N_
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+// Workspace of the deterministic backward, in floats: part_B, part_C (nslab, B, K, N, L) each, then the per-row partials
+// part_A (B, KD, N), part_D (B, KD), part_bias (B, KD).
+extern "C" int64_t tramba_selective_scan_bwd_det_work(int batch, int kd, int k, int n, int l, int io_dtype)
+{
+    TRAMBA_CHECK(batch > 0 && kd > 0 && k > 0 && l > 0, "selective_scan_bwd_det_work: empty shape");
+    TRAMBA_CHECK(kd % k == 0, "selective_scan_bwd_det_work: KD=%d is not a multiple of K=%d", kd, k);
+    TRAMBA_CHECK(n >= 1 && n <= kMaxDState, "selective_scan_bwd_det_work: d_state=%d unsupported (1..%d)", n, kMaxDState);
+    TRAMBA_CHECK(io_dtype == TRAMBA_F32 || io_dtype == TRAMBA_F16 || io_dtype == TRAMBA_BF16,
+                 "selective_scan_bwd_det_work: bad dtype %d", io_dtype);
+    const int64_t bknl = (int64_t)batch * k * n * l, rows = (int64_t)batch * kd;
+    return 4 * (2 * det_nslab(kd, k, l) * bknl + rows * (n + 2));
+}
+
+extern "C" int tramba_selective_scan_bwd_det(const void *u, const void *delta, const float *A, const void *Bm,
+                                             const void *Cm, const float *D, const float *delta_bias,
+                                             const float *dout, const float *ckpt, void *du, void *ddelta,
+                                             float *dA, float *dB, float *dC, float *dD, float *ddelta_bias,
+                                             void *work, size_t work_bytes, int batch, int kd, int k, int n, int l,
+                                             int io_dtype, int delta_softplus, void *stream)
+{
+    TRAMBA_CHECK(u && delta && A && Bm && Cm && dout && ckpt && du && ddelta && dA && dB && dC && work,
+                 "selective_scan_bwd_det: null tensor");
+    TRAMBA_CHECK(batch > 0 && kd > 0 && k > 0 && l > 0, "selective_scan_bwd_det: empty shape");
+    TRAMBA_CHECK(kd % k == 0, "selective_scan_bwd_det: KD=%d is not a multiple of K=%d", kd, k);
+    TRAMBA_CHECK(n >= 1 && n <= kMaxDState, "selective_scan_bwd_det: d_state=%d unsupported (1..%d)", n, kMaxDState);
+    const int64_t need = tramba_selective_scan_bwd_det_work(batch, kd, k, n, l, io_dtype);
+    if (need < 0) return TRAMBA_ERR_ARG;
+    TRAMBA_CHECK(work_bytes >= (size_t)need, "selective_scan_bwd_det: workspace of %zu bytes, %lld needed", work_bytes,
+                 (long long)need);
+    TRAMBA_CHECK(((uintptr_t)work & 3) == 0, "selective_scan_bwd_det: workspace not 4-byte aligned");
+    const int nslab = det_nslab(kd, k, l);
+    const long rows = (long)batch * kd, groups = (long)batch * k;
+    TRAMBA_CHECK(rows <= 0x7fffffffL && groups * nslab <= 0x7fffffffL,
+                 "selective_scan_bwd_det: B*KD=%ld rows exceed the launch", rows);
+    hipStream_t s = (hipStream_t)stream;
+    const int lpr = lanes_per_row(l);
+    const int nchunk = (l + lpr * kE - 1) / (lpr * kE);
+    const long bknl = groups * n * l;
+    const int vec_ok = (l % kE == 0) && aligned16(u) && aligned16(delta) && aligned16(Bm) && aligned16(Cm) &&
+                       aligned16(dout) && aligned16(du) && aligned16(ddelta);
+    // With one slab per group the scan kernel's partial row IS dB / dC, with batch 1 its per-row partials are dA, dD and
+    // d delta_bias: it writes them in place and the sum pass skips them.
+    float *wf = (float *)work;
+    float *partB = nslab == 1 ? dB : wf, *partC = nslab == 1 ? dC : wf + (long)nslab * bknl;
+    float *wr = wf + 2L * nslab * bknl;
+    float *partA = batch == 1 ? dA : wr;
+    float *partD = !dD ? nullptr : (batch == 1 ? dD : wr + rows * n);
+    float *partBias = !ddelta_bias ? nullptr : (batch == 1 ? ddelta_bias : wr + rows * (n + 1));
+    dim3 grid((unsigned)(groups * nslab)), block(kDetWaves * kWave);
+#define LAUNCH_N_(T, LPR_, N_)                                                                                      \
+    hipLaunchKernelGGL((selective_scan_bwd_kernel<T, LPR_, N_, true, kDetWaves>), grid, block, 0, s,                \
+                       (const T *)u, (const T *)delta, A, (const T *)Bm, (const T *)Cm, D, delta_bias, dout, ckpt,  \
+                       (T *)du,                                                                                     \
+                       (T *)ddelta, partA, partB, partC, partD, partBias, (int)rows, kd, k, l, nchunk,              \
+                       delta_softplus, vec_ok, nslab, bknl)
+#define LAUNCH_LOOP_V_(T, LPR_, VEC_)                                                                               \
+    hipLaunchKernelGGL((selective_scan_bwd_nloop_kernel<T, LPR_, VEC_, true, kDetWaves>), grid, block, 0, s,        \
+                       (const T *)u, (const T *)delta, A, (const T *)Bm, (const T *)Cm, D, delta_bias, dout, ckpt,  \
+                       (T *)du,                                                                                     \
+                       (T *)ddelta, partA, partB, partC, partD, partBias, (int)rows, kd, k, n, l, nchunk,           \
+                       delta_softplus, nslab, bknl)
+#define LAUNCH_LOOP_(T, LPR_)                          \
+    if (vec_ok) { LAUNCH_LOOP_V_(T, LPR_, true); }     \
+    else { LAUNCH_LOOP_V_(T, LPR_, false); }
+#define LAUNCH_(T, LPR_)                                        \
+    if (n == 1) { LAUNCH_N_(T, LPR_, 1); }                      \
+    else if (n == 2) { LAUNCH_N_(T, LPR_, 2); }                 \
+    else if (n == 4) { LAUNCH_N_(T, LPR_, 4); }                 \
+    else { LAUNCH_LOOP_(T, LPR_); }   /* 3, 5..16: the state-looped kernel */
+    TRAMBA_DISPATCH_DTYPE(io_dtype, T, {
+        if (lpr == 16) { LAUNCH_(T, 16) }
+        else if (lpr == 32) { LAUNCH_(T, 32) }
+        else { LAUNCH_(T, 64) }
+    });
+#undef LAUNCH_
+#undef LAUNCH_LOOP_
+#undef LAUNCH_LOOP_V_
+#undef LAUNCH_N_
+    TRAMBA_LAUNCH_CHECK();
+    if (nslab == 1 && batch == 1) return TRAMBA_OK;
+    DetSums sums = {};
+    long most = 0;
+    auto add = [&](int i, const float *src, float *dst, long count, int copies) {
+        if (!dst || src == dst) return;
+        sums.s[i] = DetSum{src, dst, count, copies, count % 4 == 0 && aligned16(src) && aligned16(dst)};
+        if (count > most) most = count;
+    };
+    add(0, partB, dB, bknl, nslab);
+    add(1, partC, dC, bknl, nslab);
+    add(2, partA, dA, (long)kd * n, batch);
+    add(3, partD, dD, kd, batch);
+    add(4, partBias, ddelta_bias, kd, batch);
+    // four floats per thread on the 16-byte path; the grid-stride loop covers what 8192 workgroups do not
+    long rblocks = ((most + 3) / 4 + 255) / 256;
+    if (rblocks > 8192) rblocks = 8192;
+    hipLaunchKernelGGL(selective_scan_bwd_det_reduce_kernel, dim3((unsigned)rblocks, kDetSums), dim3(256), 0, s, sums);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

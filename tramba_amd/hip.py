@@ -44,6 +44,8 @@ SIGNATURES = {
     "tramba_selective_scan_max_dstate": (c_int, []),
     "tramba_selective_scan_fwd": (c_int, [c_vp] * 9 + [c_int] * 8 + [c_vp]),
     "tramba_selective_scan_bwd": (c_int, [c_vp] * 16 + [c_int] * 8 + [c_vp]),
+    "tramba_selective_scan_bwd_det_work": (c_i64, [c_int] * 6),
+    "tramba_selective_scan_bwd_det": (c_int, [c_vp] * 17 + [ctypes.c_size_t] + [c_int] * 7 + [c_vp]),
     "tramba_cross_scan": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "tramba_cross_merge": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "tramba_ss2d_group_stride": (c_int, [c_int]),
@@ -374,7 +376,15 @@ def selective_scan_fwd(u, delta, A, B, C, D, delta_bias, delta_softplus=True, of
     return out, ckpt
 
 
-def selective_scan_bwd(u, delta, A, B, C, D, delta_bias, dout, ckpt, delta_softplus=True):
+def selective_scan_bwd_det_work(nb: int, kd: int, k: int, n: int, l: int, dtype: torch.dtype) -> int:
+    """bytes of workspace selective_scan_bwd(..., deterministic=True) takes for this shape:
+    4 * (2 * ceil((kd/k) / S) * nb*k*n*l + nb*kd*(n + 2)), S = 8, 16 or 32 rows per workgroup (l > 256, > 128, else)"""
+    return _check(lib().tramba_selective_scan_bwd_det_work(nb, kd, k, n, l, _DT[dtype]), "selective_scan_bwd_det_work")
+
+
+def selective_scan_bwd(u, delta, A, B, C, D, delta_bias, dout, ckpt, delta_softplus=True, deterministic=False):
+    """deterministic: the atomic-free form (tramba_selective_scan_bwd_det) -- the same seven tensors in the same dtypes,
+    each a function of the inputs and the shape alone; its partial sums live in the per-stream scan workspace"""
     _dev(u, delta, A, B, C, D, delta_bias, dout, ckpt)
     nb, kd, l = u.shape
     k, n = B.shape[1], B.shape[2]
@@ -382,6 +392,20 @@ def selective_scan_bwd(u, delta, A, B, C, D, delta_bias, dout, ckpt, delta_softp
     A32, D32, b32 = _f32(A), _f32(D), _f32(delta_bias)
     dout = dout.float().contiguous()
     du, ddelta = torch.empty_like(u), torch.empty_like(delta)
+    if deterministic:
+        # the kernels write every element of the five; zeros only because they are the allocator at hand, in two fills
+        dBC = torch.zeros((2, nb, k, n, l), dtype=torch.float32, device=u.device)
+        small = torch.zeros(kd * (n + 2), dtype=torch.float32, device=u.device)
+        dA = small[:kd * n].view(kd, n)
+        dD = small[kd * n:kd * (n + 1)] if D is not None else None
+        dbias = small[kd * (n + 1):] if delta_bias is not None else None
+        nbytes = selective_scan_bwd_det_work(nb, kd, k, n, l, u.dtype)
+        work = _scan_workspace(u.device, nbytes)
+        _check(lib().tramba_selective_scan_bwd_det(
+            _ptr(u), _ptr(delta), _ptr(A32), _ptr(B), _ptr(C), _ptr(D32), _ptr(b32), _ptr(dout), _ptr(ckpt),
+            _ptr(du), _ptr(ddelta), _ptr(dA), _ptr(dBC[0]), _ptr(dBC[1]), _ptr(dD), _ptr(dbias), _ptr(work), nbytes,
+            nb, kd, k, n, l, dt(u), int(delta_softplus), _stream()), "selective_scan_bwd_det")
+        return du, ddelta, dA, dBC[0], dBC[1], dD, dbias
     dA = torch.zeros((kd, n), dtype=torch.float32, device=u.device)
     ncopy = scan_bc_copies(kd, k, n)  # private dB/dC copies: <= 1/8 of a group's rows per address
     dB = torch.zeros((ncopy, nb, k, n, l), dtype=torch.float32, device=u.device)

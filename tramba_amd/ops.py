@@ -11,12 +11,52 @@ Unlike the reference nothing happens at import time: tables are generated on dem
 square size (the reference ships 12/24/48/96 only, csms6s.py:58-61,107-110,157) and cached
 per device.
 """
+import contextlib
+
 import torch
 
 from . import hip
 
 
 # ----------------------------------------------------------------------------- L0
+_DET_MODES = (False, True, "torch")
+_det_mode = False
+
+
+def set_deterministic_scan(mode):
+    """Select the backward of the reference-layout selective scan (SelectiveScanOflex, selective_scan_cuda_oflex.bwd and
+    every module that runs through them): False (default) -- dB / dC, dA, dD and d delta_bias summed with fp32 atomics;
+    True -- the atomic-free form, bitwise reproducible run to run; "torch" -- follow
+    torch.are_deterministic_algorithms_enabled() at backward time.  Returns the previous mode."""
+    global _det_mode
+    if not any(mode is m or (isinstance(mode, str) and mode == m) for m in _DET_MODES):
+        raise ValueError(f"set_deterministic_scan: mode must be False, True or 'torch', got {mode!r}")
+    prev, _det_mode = _det_mode, mode
+    return prev
+
+
+def get_deterministic_scan():
+    """the mode set by set_deterministic_scan"""
+    return _det_mode
+
+
+@contextlib.contextmanager
+def deterministic_scan(mode=True):
+    """with deterministic_scan(True): ... -- set_deterministic_scan for a block; the previous mode comes back on exit,
+    whatever happens inside"""
+    prev = set_deterministic_scan(mode)
+    try:
+        yield
+    finally:
+        set_deterministic_scan(prev)
+
+
+def _scan_is_deterministic():
+    if _det_mode == "torch":
+        return torch.are_deterministic_algorithms_enabled()
+    return _det_mode
+
+
 class _OflexExtension:
     """Object with the two entry points of the absent CUDA extension."""
 
@@ -29,7 +69,8 @@ class _OflexExtension:
     @staticmethod
     def bwd(u, delta, A, B, C, D, delta_bias, dout, x, delta_softplus, nrows):
         du, ddelta, dA, dB, dC, dD, dbias = hip.selective_scan_bwd(
-            _c(u), _c(delta), A, _c(B), _c(C), D, delta_bias, _c(dout), x, bool(delta_softplus))
+            _c(u), _c(delta), A, _c(B), _c(C), D, delta_bias, _c(dout), x, bool(delta_softplus),
+            deterministic=_scan_is_deterministic())
         dA = dA.to(A.dtype)
         dB, dC = dB.to(B.dtype), dC.to(C.dtype)
         dD = None if dD is None else dD.to(D.dtype)
