@@ -127,7 +127,9 @@ int tramba_tune_get(int knob);
                                         0 = the kernels that march down a band of rows (default) */
 #define TRAMBA_TUNE_DW_ROWS 7        /* rows per band of the marching 7x7 kernels (0 = the library's choice) */
 #define TRAMBA_TUNE_MERGE_PW 8       /* pixels per wave of the streaming merge: 4 / 8 / 16 force one (0 = the library's choice, by the wave count) */
-#define TRAMBA_TUNE_COUNT 9
+#define TRAMBA_TUNE_SCAN_N_PASS 9  /* measurement only (scripts/bench_ss2d_dstate.py): tramba_ss2d_scan_n_cl launches 1 = its reduce pass alone,
+                                    * 2 = its replay pass alone (the carries are then whatever an earlier reduce pass left in the workspace) */
+#define TRAMBA_TUNE_COUNT 10
 #define TRAMBA_PROF_SCAN_BOUNDARY 0
 #define TRAMBA_PROF_SCAN_FUSED 1
 #define TRAMBA_PROF_GEMM 2          /* tramba_linear_cl (1x1-conv projections) */
@@ -228,6 +230,23 @@ int tramba_ss2d_scan_cl(const void *x, const float *xdbl, const int32_t *table, 
                         const float *dt_bias, const float *A, const float *Ds, void *ys, void *workspace,
                         size_t workspace_bytes, int batch, int l, int d, int k, int r, int dtype,
                         int ys_dtype, float *states, int a_log, void *stream);
+/* The same scan for d_state N = 2..16 (inference; replaces vmamba.py:230-257 at the reference's default d_state = 16).
+ * xdbl: (B, L, K*RG) f32, per group k [dt_0..dt_{R-1}, 0-pad to R8 | B_0..B_{N-1} | C_0..C_{N-1} | 0-pad to a multiple
+ *       of 4 floats];  RG = tramba_ss2d_group_stride_n(R, N) = R8 + ((2N + 3) & ~3), which is tramba_ss2d_group_stride(R)
+ *       at N = 1.
+ * A (K*D, N) f32 (= -exp(A_logs)); every other tensor as for tramba_ss2d_scan_cl.  r <= 64.
+ * N = 1 is an argument error here (tramba_ss2d_scan_cl serves it), as is N > 16.
+ * Always the wave-segment form: one wave per segment, two launches (one when the plan has a single segment), no
+ * workgroup barrier and no wait between waves.  workspace: >= tramba_ss2d_scan_n_workspace() bytes, 16-byte aligned;
+ * required when the plan has more than one segment; every byte the second launch reads is written by the first.
+ * tramba_ss2d_scan_n_plan: host-only query of that plan (tiles of 32 positions per segment, segments per sequence). */
+int tramba_ss2d_group_stride_n(int r, int n);
+size_t tramba_ss2d_scan_n_workspace(int batch, int l, int d, int k, int n);
+int tramba_ss2d_scan_n_plan(int batch, int l, int d, int k, int n, int *tiles_per_segment, int *nseg);
+int tramba_ss2d_scan_n_cl(const void *x, const float *xdbl, const int32_t *table, const float *dt_w,
+                          const float *dt_bias, const float *A, const float *Ds, void *ys, void *workspace,
+                          size_t workspace_bytes, int batch, int l, int d, int k, int r, int n, int dtype,
+                          int ys_dtype, void *stream);
 /* Training: backward of tramba_ss2d_scan_cl + the merge that follows it.  gym (B, L, D), f32 or dtype (gym_dtype), is the
  * gradient of the MERGED map (CrossMerge output, before out_norm); the kernel gathers it through `table`.  Outputs, in SEQUENCE
  * order like ys: gu (B,K,L,D) dtype = dL/d(gathered x) -- merge it with tramba_ss2d_merge_norm_cl(eps < 0) to get

@@ -51,6 +51,10 @@ SIGNATURES = {
     "tramba_ss2d_group_stride": (c_int, [c_int]),
     "tramba_ss2d_scan_workspace": (ctypes.c_size_t, [c_int] * 4),
     "tramba_ss2d_scan_cl": (c_int, [c_vp] * 9 + [ctypes.c_size_t] + [c_int] * 7 + [c_vp, c_int, c_vp]),
+    "tramba_ss2d_group_stride_n": (c_int, [c_int] * 2),
+    "tramba_ss2d_scan_n_workspace": (ctypes.c_size_t, [c_int] * 5),
+    "tramba_ss2d_scan_n_plan": (c_int, [c_int] * 5 + [c_vp] * 2),
+    "tramba_ss2d_scan_n_cl": (c_int, [c_vp] * 9 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
     "tramba_ss2d_scan_bwd_workspace": (ctypes.c_size_t, [c_int] * 4),
     "tramba_ss2d_scan_bwd_cl": (c_int, [c_vp] * 12 + [c_int, c_vp, c_vp, ctypes.c_size_t] + [c_int] * 9 + [c_vp]),
     "tramba_ss2d_bwd_prep_cl": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp]),
@@ -302,6 +306,7 @@ def scan_order(family: str, h: int, w: int, device, param: int = 0) -> ScanOrder
 # ----------------------------------------------------------------------------- profiling / tuning
 TUNE_MERGE_FORM, TUNE_SCAN_FORM, TUNE_SCAN_W, TUNE_GEMM_TILE, TUNE_MAILBOX_SKIP, TUNE_DW_FORM, TUNE_DW_ROWS = 0, 1, 2, 3, 4, 6, 7   # (5 retired)
 TUNE_MERGE_PW = 8
+TUNE_SCAN_N_PASS = 9      # measurement only: 1 / 2 = the reduce / the replay launch of ss2d_scan_n_cl alone
 
 
 def device_error():
@@ -443,18 +448,25 @@ def cross_merge(ys, order: ScanOrder):
 
 
 # ----------------------------------------------------------------------------- channels-last kernels
-def ss2d_group_stride(r: int) -> int:
-    """Floats per direction group of the x_proj output: [dt_0..dt_{R-1}, 0-pad to R8 = 8*ceil(R/8), B, C, 0, 0]."""
-    return lib().tramba_ss2d_group_stride(r)
+def ss2d_group_stride(r: int, n: int = 1) -> int:
+    """Floats per direction group of the x_proj output: [dt_0..dt_{R-1}, 0-pad to R8 = 8*ceil(R/8), B, C, 0, 0] at d_state
+    n = 1; [R8 ranks | B_0..B_{n-1} | C_0..C_{n-1} | 0-pad to a multiple of 4] = R8 + ((2n + 3) & ~3) in general."""
+    if n == 1:
+        return lib().tramba_ss2d_group_stride(r)
+    return lib().tramba_ss2d_group_stride_n(r, n)
 
 
-def pad_x_proj_weight(x_proj_weight: torch.Tensor) -> torch.Tensor:
-    """(K, R+2, D) -> (K*RG, D) with zero rows as padding, the layout ss2d_scan_cl consumes."""
+def pad_x_proj_weight(x_proj_weight: torch.Tensor, n: int = 1) -> torch.Tensor:
+    """(K, R+2n, D) -> (K*RG, D) with zero rows as padding, the layout ss2d_scan_cl (n = 1) / ss2d_scan_n_cl consume."""
     k, r2, d = x_proj_weight.shape
-    rg = ss2d_group_stride(r2 - 2)
+    r = r2 - 2 * n
+    if n < 1 or r < 1:
+        raise TrambaHipError(f"pad_x_proj_weight: {tuple(x_proj_weight.shape)} is not (K, R + 2*{n}, D)")
+    rg = ss2d_group_stride(r, n)
+    r8 = (r + 7) & ~7
     w = x_proj_weight.new_zeros((k, rg, d))
-    w[:, :r2 - 2] = x_proj_weight[:, :r2 - 2]
-    w[:, rg - 4:rg - 2] = x_proj_weight[:, r2 - 2:]      # B, C after the 8-padded ranks
+    w[:, :r] = x_proj_weight[:, :r]
+    w[:, r8:r8 + 2 * n] = x_proj_weight[:, r:]      # B_0..B_{n-1}, C_0..C_{n-1} after the 8-padded ranks
     return w.reshape(k * rg, d)
 
 
@@ -481,6 +493,12 @@ def ss2d_scan_states(x, order: ScanOrder):
     return torch.empty(lib().tramba_ss2d_scan_bwd_workspace(b, l, d, order.k), dtype=torch.uint8, device=x.device)
 
 
+def _scan_ys(b, k, l, d, ys_dtype, device):
+    """the per-direction outputs (B, K, L, D) of the fused scans (ss2d_scan_cl, ss2d_scan_n_cl): every element is written by the
+    launch that follows"""
+    return torch.empty((b, k, l, d), dtype=ys_dtype, device=device)
+
+
 def ss2d_scan_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch.float32, segmented=True, states=None,
                  a_log=False):
     """x: (B, L, D); xdbl: (B, L, K*RG) f32 -> ys (B, K, L, D).  With `segmented` a workspace is passed and
@@ -495,7 +513,7 @@ def ss2d_scan_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch
         raise TrambaHipError(f"ss2d_scan_cl: xdbl must be f32 (B,L,K*RG), got {xdbl.dtype} {tuple(xdbl.shape)}")
     if l != order.l or dt_w.shape != (k, d, r) or A.numel() != k * d or Ds.numel() != k * d or dt_bias.numel() != k * d:
         raise TrambaHipError("ss2d_scan_cl: parameter shapes do not match (K, D, R)")
-    ys = torch.empty((b, k, l, d), dtype=ys_dtype, device=x.device)
+    ys = _scan_ys(b, k, l, d, ys_dtype, x.device)
     ws, ws_bytes = None, 0
     if segmented:
         ws_bytes = lib().tramba_ss2d_scan_workspace(b, l, d, k)
@@ -503,6 +521,39 @@ def ss2d_scan_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch
     _check(lib().tramba_ss2d_scan_cl(_ptr(x), _ptr(xdbl), _ptr(order.table), _ptr(dt_w), _ptr(dt_bias), _ptr(A),
                                      _ptr(Ds), _ptr(ys), _ptr(ws), ws_bytes, b, l, d, k, r, dt(x), dt(ys), _ptr(states),
                                      int(a_log), _stream()), "ss2d_scan_cl")
+    return ys
+
+
+def ss2d_scan_n_plan(b, l, d, k, n):
+    """(tiles of 32 positions per segment, segments per sequence) of ss2d_scan_n_cl's launch; one segment = one launch."""
+    nt, nseg = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().tramba_ss2d_scan_n_plan(b, l, d, k, n, ctypes.addressof(nt), ctypes.addressof(nseg)), "ss2d_scan_n_plan")
+    return nt.value, nseg.value
+
+
+def ss2d_scan_n_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch.float32):
+    """The fused scan for d_state N = 2..16 (inference).  x: (B, L, D); xdbl: (B, L, K*RG(R, N)) f32; A: (K*D, N) f32,
+    already negated -> ys (B, K, L, D) in sequence order.  Wave-segment form only (state-looped); N = 1 is ss2d_scan_cl."""
+    _dev(x, xdbl, dt_w, dt_bias, A, Ds)
+    b, l, d = x.shape
+    k, r = order.k, dt_w.shape[-1]
+    if A.dim() != 2 or A.shape[0] != k * d:
+        raise TrambaHipError(f"ss2d_scan_n_cl: A must be (K*D, N) = ({k * d}, N), got {tuple(A.shape)}")
+    n = A.shape[1]
+    if not 2 <= n <= 16:
+        raise TrambaHipError(f"ss2d_scan_n_cl: d_state {n} outside 2..16 (d_state 1 is ss2d_scan_cl)")
+    rg = ss2d_group_stride(r, n)
+    if xdbl.dtype != torch.float32 or xdbl.shape != (b, l, k * rg):
+        raise TrambaHipError(f"ss2d_scan_n_cl: xdbl must be f32 (B, L, K*RG(R, N)) = ({b}, {l}, {k}*{rg}), "
+                             f"got {xdbl.dtype} {tuple(xdbl.shape)}")
+    if l != order.l or dt_w.shape != (k, d, r) or Ds.numel() != k * d or dt_bias.numel() != k * d:
+        raise TrambaHipError("ss2d_scan_n_cl: parameter shapes do not match (K, D, R)")
+    ys = _scan_ys(b, k, l, d, ys_dtype, x.device)
+    ws_bytes = lib().tramba_ss2d_scan_n_workspace(b, l, d, k, n)
+    ws = _scan_workspace(x.device, ws_bytes)
+    _check(lib().tramba_ss2d_scan_n_cl(_ptr(x), _ptr(xdbl), _ptr(order.table), _ptr(dt_w), _ptr(dt_bias), _ptr(A),
+                                       _ptr(Ds), _ptr(ys), _ptr(ws), ws_bytes, b, l, d, k, r, n, dt(x), dt(ys),
+                                       _stream()), "ss2d_scan_n_cl")
     return ys
 
 

@@ -1587,23 +1587,27 @@ class SS2D(nn.Module):
 
     # -- the two core paths -----------------------------------------------------------------
     def _fused_ok(self, x):
-        return (self.d_state == 1 and self.dt_rank <= 64
+        # d_state 2..16: the state-looped wave-segment scan (hip.ss2d_scan_n_cl)
+        return (1 <= self.d_state <= 16 and self.dt_rank <= 64
                 and getattr(self.scan, "_tramba_family", None) is not None
                 and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
                 and self.scan._tramba_k == self.k_group
                 and _infer(x, self.x_proj_weight, self.dt_projs_weight, self.A_logs))
 
     def _padded_x_proj(self, dtype):
-        """x_proj weight in the (K*RG, D) layout of the fused scan."""
-        p = self.x_proj_weight
-        return _cache(self).get(("xproj", dtype), (p,), lambda: hip.pad_x_proj_weight(p.detach().to(dtype)).contiguous())
+        """x_proj weight in the (K*RG, D) layout of the fused scan (keyed by d_state: a module never mixes layouts)."""
+        p, n = self.x_proj_weight, self.d_state
+        return _cache(self).get(("xproj", dtype, n), (p,),
+                                lambda: hip.pad_x_proj_weight(p.detach().to(dtype), n).contiguous())
 
     def _scan_params(self):
-        """fp32 kernel-ready (dt_w, dt_bias, -exp(A_logs), Ds)."""
+        """fp32 kernel-ready (dt_w, dt_bias, -exp(A_logs), Ds); -exp(A_logs) is (K*D) at d_state 1, (K*D, N) beyond."""
         ps = (self.dt_projs_weight, self.dt_projs_bias, self.A_logs, self.Ds)
-        return _cache(self).get("scan", ps, lambda: (
+        n = self.d_state
+        a_shape = (-1,) if n == 1 else (-1, n)
+        return _cache(self).get(("scan", n), ps, lambda: (
             _f32(self.dt_projs_weight).clone(), _f32(self.dt_projs_bias).reshape(-1).clone(),
-            (-torch.exp(self.A_logs.detach().float())).reshape(-1).contiguous(), _f32(self.Ds).clone()))
+            (-torch.exp(self.A_logs.detach().float())).reshape(a_shape).contiguous(), _f32(self.Ds).clone()))
 
     def _core_fused_cl(self, x):
         """x (B,H,W,D) after conv+SiLU -> GELU(out_norm(merge(scan(...)))), all HIP."""
@@ -1616,7 +1620,10 @@ class SS2D(nn.Module):
         # the per-direction outputs travel between the scan and the merge kernel in the activation dtype (fp32 sums and
         # LayerNorm statistics inside the merge): half the bytes of the K-fold intermediate at 16-bit activations
         ys_dtype = x.dtype
-        ys = hip.ss2d_scan_cl(xf, xdbl, order, dt_w, dt_b, a_neg, ds, ys_dtype)
+        if self.d_state == 1:
+            ys = hip.ss2d_scan_cl(xf, xdbl, order, dt_w, dt_b, a_neg, ds, ys_dtype)
+        else:
+            ys = hip.ss2d_scan_n_cl(xf, xdbl, order, dt_w, dt_b, a_neg, ds, ys_dtype)
         y = hip.ss2d_merge_norm_cl(ys, order, _f32(self.out_norm.weight), _f32(self.out_norm.bias),
                                    self.out_norm.eps, hip.ACT_GELU, x.dtype)
         return y.view(b, h, w, d)
