@@ -281,6 +281,39 @@ int tramba_ss2d_bwd_prep_cl(const float *xdbl, const int32_t *table, const float
  * the scan kernels' gather of x_dbl rows, cast to the dtype the x_proj gradient GEMMs read. */
 int tramba_ss2d_bwd_assemble_cl(const float *gseq, const int32_t *inv_ptr, const int32_t *inv_idx, void *out, int batch,
                                 int l, int k, int r, int dtype, void *stream);
+/* Training at d_state N = 2..16: backward of tramba_ss2d_scan_n_cl + the merge that follows it (replaces vmamba.py:230-262
+ * under autograd, i.e. csms6s.py selective_scan_cuda_oflex.bwd with the gathers, dt_proj and the merge around it).
+ * x, xdbl (layout of tramba_ss2d_scan_n_cl), table, dt_w, dt_bias, A (K*D, N) f32 = -exp(A_logs), Ds, gym as for
+ * tramba_ss2d_scan_bwd_cl.  Outputs, every element written by exactly one wave (no zero fill, no atomics, bitwise
+ * reproducible):
+ *   gu, graw (B,K,L,D) dtype, in sequence order;
+ *   bpart, cpart (B, K, ceil(D/32), N, L) f32: per-channel-tile partial sums of dL/dB_n, dL/dC_n
+ *         (tramba_ss2d_bwd_prep_n_cl adds them in a fixed order);
+ *   gpar  (B * NSEG, K*D*(N + 2)) f32, NSEG from tramba_ss2d_scan_n_bwd_plan: one slab per (batch, segment) holding
+ *         [dL/dA_logs (K*D, N) = dL/dA * A | dD (K*D) | d(dt_bias) (K*D)]; the sum over the slabs (tramba_slab_sum) has the
+ *         parameters' own strides.
+ * Wave-segment form only: one wave per segment of a (b, k, 32-channel tile); three launches (ss2d_seg_n_kernel's reduce
+ * pass, an adjoint reduce pass, the emit pass), one when the plan has a single segment; no workgroup barrier, no wait
+ * between waves.  The plan is the backward's own: segments of at most 160 / N tiles, whose tile-entry states stay in LDS.
+ * workspace: launch-local scratch, >= tramba_ss2d_scan_n_bwd_workspace() bytes, 16-byte aligned, required when NSEG > 1:
+ *   bytes = 16 if NSEG == 1, else B*K*NSEG*N*D * 12  (the forward (decay, state) float2 pairs, then the adjoint floats);
+ *   0 for arguments outside the supported range.  Every byte read is written earlier in the same call.
+ * tramba_ss2d_scan_n_bwd_plan: host-only query (tiles of 32 positions per segment, segments per sequence). */
+size_t tramba_ss2d_scan_n_bwd_workspace(int batch, int l, int d, int k, int n, int dtype);
+int tramba_ss2d_scan_n_bwd_plan(int batch, int l, int d, int k, int n, int *tiles_per_segment, int *nseg);
+int tramba_ss2d_scan_n_bwd_cl(const void *x, const float *xdbl, const int32_t *table, const float *dt_w,
+                              const float *dt_bias, const float *A, const float *Ds, const void *gym, void *gu,
+                              void *graw, float *bpart, float *cpart, float *gpar, void *workspace,
+                              size_t workspace_bytes, int batch, int l, int d, int k, int r, int n, int dtype,
+                              int gym_dtype, void *stream);
+/* The glue of tramba_ss2d_bwd_prep_cl / tramba_ss2d_bwd_assemble_cl for d_state n = 1..16, RG = tramba_ss2d_group_stride_n(r, n)
+ * (n = 1: exactly the two entries above): bpart / cpart (B, K, CT, n, L); gseq columns R8 .. R8 + n - 1 = dL/dB_0..,
+ * R8 + n .. R8 + 2n - 1 = dL/dC_0.., the pad columns 0; the assemble keeps columns j < r and R8 <= j < R8 + 2n.
+ * RG <= 96 (r <= 64, n <= 16). */
+int tramba_ss2d_bwd_prep_n_cl(const float *xdbl, const int32_t *table, const float *bpart, const float *cpart, void *ranks,
+                              float *gseq, int batch, int l, int k, int r, int n, int ctiles, int dtype, void *stream);
+int tramba_ss2d_bwd_assemble_n_cl(const float *gseq, const int32_t *inv_ptr, const int32_t *inv_idx, void *out, int batch,
+                                  int l, int k, int r, int n, int dtype, void *stream);
 /* y[b,p,:] = act(LayerNorm_D(sum_{e in inv[p]} ys[b, e/L, e%L, :]));  y: (B, L, D) dtype.
  * eps < 0: the plain sum (CrossMerge alone), ln_w / ln_b / act ignored. */
 int tramba_ss2d_merge_norm_cl(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx,

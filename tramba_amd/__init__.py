@@ -14,6 +14,7 @@ from .modules import (DCT2D, SS2D, DropPath, DWConv, DWMSMlp, FinalPatchExpand_X
 from .train import SodLoss, structure_loss, wbce  # noqa: F401
 from .ops import (CrossMerge, CrossMerge_Dilation, CrossMerge_Line, CrossMerge_Window, CrossScan,  # noqa: F401
                   CrossScan_Dilation, CrossScan_Line, CrossScan_Window, SelectiveScanOflex,
-                  deterministic_scan, selective_scan_cuda_oflex, set_deterministic_scan)
+                  deterministic_scan, fused_dstate_training, get_fused_dstate_training, selective_scan_cuda_oflex,
+                  set_deterministic_scan, set_fused_dstate_training)
 
 __version__ = "0.1.0"

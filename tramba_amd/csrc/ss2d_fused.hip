@@ -2511,3 +2511,504 @@ extern "C" int tramba_ss2d_scan_n_cl(const void *x, const float *xdbl, const int
 }
 
 extern "C" int tramba_ss2d_group_stride_n(int r, int n) { return tramba::xdbl_group_stride_n(r, n); }
+
+namespace tramba {
+
+// ---------------------------------------------------------------------------------------------
+// Backward of the state-looped wave-segment scan, d_state N = 2..16 (training; vmamba.py:230-262 under autograd, the
+// reference's selective_scan_cuda_oflex.bwd).  Same work split as ss2d_seg_n_kernel: one wave owns one segment of NT tiles of
+// one (b, k, 32-channel tile) and walks it alone.  Three launches:
+//   (a) ss2d_seg_n_kernel PASS 0, as it is, with THIS plan  -> agg  (B,K,NSEG,N,D) float2: the segment's (decay, state)
+//   (b) MODE 0, right to left over the segment              -> zagg (B,K,NSEG,N,D) float: the adjoint leaving the segment
+//       on its left for zero entering from its right (z_l = a_l (C_l gy_l + z_{l+1})); its decay product is (a)'s .x
+//   (c) MODE 1: per state the state entering the segment = fold of agg from the left, the adjoint entering it = fold of
+//       (agg.x, zagg) from the right (8 wide + remainder, as PASS 1); a sweep left to right that records the state entering
+//       every tile per state in wave-private LDS (NT * N rows of 32 floats, NT * N <= kBwdNRows by the plan); then a sweep
+//       right to left that replays every tile forward from its recorded state, runs the adjoint and emits everything.
+// A single-segment sequence is (c) alone.  Every launch is wave-uniform: no workgroup barrier, no mailbox, no wait on another
+// wave, no LDS-DMA, no atomics.  Loop bounds: the tiles of a segment (<= NT), NSEG (the two folds), N (the state loop), and
+// constants (16 elements, 4 runs, 4 chunks).  Every reduction has a fixed order, so every output is bitwise reproducible:
+//   dB / dC   (B,K,CT,N,L) per-channel-tile partials, each element written by exactly one wave (LDS transpose per state);
+//   gpar      (B*NSEG, K*D*(N+2)): per (batch, segment) slab [dL/dA_logs (K*D, N) | dD (K*D) | dbias (K*D)], each element
+//             written by exactly one wave; the caller adds the slabs in a fixed order (the sum has A_logs' own strides).
+// What is indexed by (channel, state) -- A, the running state, the running adjoint, the dA sums -- sits in wave-private LDS,
+// one float per (state, channel), written by both lanes of a channel with the same bits (see ss2d_seg_n_kernel).
+// Operands are fetched tile by tile without a ring: the kernel keeps ~200 live registers inside the state loop and runs one
+// wave per SIMD, where a second operand stage would spill.
+constexpr int kBwdNRows = 160;   // rows of 32 tile-entry states per wave: NT * N <= 160 (20 KB of LDS per wave)
+
+__host__ inline SegPlan seg_plan_n_bwd(int l, long rowtiles, int n)
+{
+    SegPlan p;
+    p.ntiles = (l + kTP - 1) / kTP;
+    long want = 4096 / (rowtiles > 0 ? rowtiles : 1);
+    if (want < 1) want = 1;
+    int nt = (int)((p.ntiles + want - 1) / want);
+    if (nt < 4) nt = 4;                      // the two folds cost NSEG loads per state: no segments shorter than 4 tiles
+    if (p.ntiles <= 6) nt = p.ntiles;        // short sequences: one segment, single launch
+    const int cap = kBwdNRows / n;           // >= 10
+    if (nt > cap) nt = cap;
+    p.nt = nt;
+    p.nseg = (p.ntiles + nt - 1) / nt;
+    return p;
+}
+
+template <typename T, int NK, bool SPLIT, typename TG, int MODE>
+__global__ __launch_bounds__(256, 1) void ss2d_seg_n_bwd_kernel(
+    const T *__restrict__ x, const float *__restrict__ xdbl, const int32_t *__restrict__ table,
+    const float *__restrict__ dt_w, const float *__restrict__ dt_bias, const float *__restrict__ Aneg /* (K*D, N) */,
+    const float *__restrict__ Ds, const TG *__restrict__ gym, T *__restrict__ gu, T *__restrict__ graw,
+    float *__restrict__ bpart, float *__restrict__ cpart, float *__restrict__ gpar, const float2 *__restrict__ agg,
+    float *__restrict__ zagg, int L, int D, int K, int R, int N, int CT, int NT, int NSEG, long nwaves)
+{
+    constexpr int kTS = 36;   // LDS row stride (floats) of the position-sum transposes
+    __shared__ __attribute__((aligned(16))) float stage[4][3][kTP];
+    __shared__ __attribute__((aligned(16))) float bcs[4][kBcRows * kTP];   // [value][position] of the current tile
+    __shared__ float sAn[4][kMaxN * kTP];                                  // A[channel, n]
+    __shared__ float sZn[4][kMaxN * kTP];                                  // running adjoint per (state, channel)
+    __shared__ float sHn[4][MODE == 1 ? kMaxN * kTP : 1];                  // running state (left-to-right sweep)
+    __shared__ float sGa[4][MODE == 1 ? kMaxN * kTP : 1];                  // dA sums
+    __shared__ float hst[4][MODE == 1 ? kBwdNRows * kTP : 1];              // state entering tile i, state n: row i * N + n
+    __shared__ __attribute__((aligned(16))) float tr[4][MODE == 1 ? kTP * kTS : 4];
+
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const long gid = (long)blockIdx.x * 4 + wv;
+    if (gid >= nwaves) return;  // wave-uniform, the kernel has no barriers
+    const unsigned g32 = (unsigned)gid;
+    const int sgm = (int)(g32 % (unsigned)NSEG);
+    unsigned rt = g32 / (unsigned)NSEG;
+    const int ctile = (int)(rt % (unsigned)CT);
+    rt /= (unsigned)CT;
+    const int k = (int)(rt % (unsigned)K), b = (int)(rt / (unsigned)K);
+
+    const int r32 = lane & 31, hi = lane >> 5;
+    const int c = ctile * kTP + r32;
+    const bool cok = c < D;
+    const int cc_ = cok ? c : D - 1;
+    const int R8 = xdbl_rank_pad(R);
+    const int C4 = xdbl_bc_pad(N) >> 2;
+    const int RG = R8 + 4 * C4;
+    const int PC = K * RG;
+
+    float *bcw = &bcs[wv][0];
+    float *sA = &sAn[wv][0] + r32;
+    float *sZ = &sZn[wv][0] + r32;
+    float *sH = &sHn[wv][0] + (MODE == 1 ? r32 : 0);
+    float *sG = &sGa[wv][0] + (MODE == 1 ? r32 : 0);
+    float *hs = &hst[wv][0] + (MODE == 1 ? r32 : 0);
+    float *trw = &tr[wv][0];
+
+    ScanWave<T, NK, SPLIT> w;
+    w.init(dt_w, dt_bias, Aneg, Ds, (long)k * D + cc_, R, RG, PC, D, lane, cc_, &stage[wv][0][0]);
+    {
+        const float *arow = Aneg + ((long)k * D + cc_) * N;
+        for (int n = 0; n < N; ++n) {
+            sA[n * kTP] = arow[n];
+            sZ[n * kTP] = 0.f;
+            if (MODE == 1) {
+                sH[n * kTP] = 0.f;
+                sG[n * kTP] = 0.f;
+            }
+        }
+    }
+
+    const __amdgpu_buffer_rsrc_t rx = make_rsrc(x + (long)b * L * D, (unsigned)L * w.xrow);
+    const __amdgpu_buffer_rsrc_t rp =
+        make_rsrc(xdbl + (long)b * L * PC + (long)k * RG, ((unsigned)(L - 1) * PC + RG) * 4u);
+    const __amdgpu_buffer_rsrc_t rg = make_rsrc(gym + (long)b * L * D, (unsigned)L * (unsigned)D * (unsigned)sizeof(TG));
+    const unsigned orow = (unsigned)D * (unsigned)sizeof(T);
+    const __amdgpu_buffer_rsrc_t ru = make_rsrc(MODE == 1 ? gu + ((long)b * K + k) * L * D : nullptr, MODE == 1 ? (unsigned)L * orow : 0u);
+    const __amdgpu_buffer_rsrc_t rr = make_rsrc(MODE == 1 ? graw + ((long)b * K + k) * L * D : nullptr, MODE == 1 ? (unsigned)L * orow : 0u);
+    const int32_t *tk = table + (long)k * L;
+
+    const int ntiles = (L + kTP - 1) / kTP;
+    const int t0 = sgm * NT;
+    const int ntl = (t0 + NT < ntiles ? t0 + NT : ntiles) - t0;   // tiles of this segment inside the sequence: 1..NT
+
+    auto load_idx = [&](int t) -> int {
+        const int l = t * kTP + r32;
+        return max(tk[l < L ? l : L - 1], 0);
+    };
+    unsigned bco[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bco[j] = 2 * j + hi < C4 ? (unsigned)(R8 + 4 * (2 * j + hi)) * 4u : kOutOfRange;
+    // the (B | C) block of my position, straight into LDS: rows 0..N-1 = B * ln2, rows N..2N-1 = C, [value][position]
+    auto stage_bc_n = [&](int idxv) {
+        const unsigned pr = (unsigned)idxv * w.prow;
+        v4f bcr[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned vo = bco[j] == kOutOfRange ? kOutOfRange : pr + bco[j];
+            bcr[j] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(rp, vo, 0, 0));
+        }
+        __builtin_amdgcn_wave_barrier();   // (the previous tile's row reads are done)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (bco[j] != kOutOfRange) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int row = 4 * (2 * j + hi) + e;
+                    bcw[row * kTP + r32] = row < N ? bcr[j][e] * 0.693147180559945f : bcr[j][e];
+                }
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    auto read_row = [&](int row, float (&out)[16]) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float4 v = *reinterpret_cast<const float4 *>(bcw + row * kTP + 8 * g + 4 * hi);
+            out[4 * g + 0] = v.x; out[4 * g + 1] = v.y; out[4 * g + 2] = v.z; out[4 * g + 3] = v.w;
+        }
+    };
+    // gradient of the merged map at my 16 positions (the x-row byte offsets staged by fetch_ranks scale to TG rows)
+    auto load_gy = [&](int nvalid, float (&gy)[16]) {
+        float xo[16];
+        w.read_stage4(0, xo);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const unsigned off = __builtin_bit_cast(unsigned, xo[r]) / (unsigned)sizeof(T) * (unsigned)sizeof(TG) +
+                                 (unsigned)cc_ * (unsigned)sizeof(TG);
+            const bool ok = (r & 3) + 8 * (r >> 2) + 4 * hi < nvalid;
+            gy[r] = raw_to_f<TG>(buf_load_raw<TG>(rg, ok ? off : kOutOfRange));
+        }
+    };
+    // adjoint run aggregates and their right-to-left fold over the 8 runs of a tile (ss2d_scan_bwd_cl_kernel's, per state)
+    auto adj_fold = [&](const float (&a)[16], const float (&cg)[16], float (&qA)[4], float (&qZ)[4], float &RA, float &RZ) {
+        float sa[4], sz[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float pa = 1.f, pz = 0.f;
+#pragma unroll
+            for (int q = 3; q >= 0; --q) {
+                pz = a[4 * g + q] * (cg[4 * g + q] + pz);
+                pa *= a[4 * g + q];
+            }
+            sa[g] = pa;
+            sz[g] = pz;
+        }
+        RA = 1.f;
+        RZ = 0.f;
+#pragma unroll
+        for (int g = 3; g >= 0; --g) {
+            float la, lz, ua, uz;
+            half_swap(sa[g], la, ua);
+            half_swap(sz[g], lz, uz);
+            const float mA = ua * RA, mZ = fmaf(ua, RZ, uz);     // after the upper run
+            qA[g] = hi ? RA : mA;
+            qZ[g] = hi ? RZ : mZ;
+            RZ = fmaf(la, mZ, lz);
+            RA = la * mA;
+        }
+    };
+
+    if (MODE == 0) {
+        for (int i = ntl - 1; i >= 0; --i) {   // right to left
+            const int t = t0 + i, l0 = t * kTP, nvalid = L - l0;
+            const int idxv = load_idx(t);
+            TileOps<T, NK> cur;
+            fetch_ranks(w, rx, rp, idxv, cur);
+            float gy[16];
+            load_gy(nvalid, gy);
+            stage_bc_n(idxv);
+            float tt[16], uf[16];
+            terms_t(w, cur, nvalid, tt, uf);
+#pragma nounroll
+            for (int n = 0; n < N; ++n) {
+                const float An = sA[n * kTP];
+                float a[16], cg[16], qA[4], qZ[4], RA, RZ;
+                read_row(N + n, cg);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    a[r] = __builtin_amdgcn_exp2f(tt[r] * An);
+                    cg[r] *= gy[r];
+                }
+                adj_fold(a, cg, qA, qZ, RA, RZ);
+                sZ[n * kTP] = fmaf(RA, sZ[n * kTP], RZ);
+            }
+        }
+        if (hi == 0 && cok) {
+            float *zg = zagg + ((((long)b * K + k) * NSEG + sgm) * N) * D + c;
+            for (int n = 0; n < N; ++n) zg[(long)n * D] = sZ[n * kTP];
+        }
+        return;
+    }
+
+    // ---- MODE 1
+    if (NSEG > 1) {
+        const long sstr = (long)N * D;
+        for (int n = 0; n < N; ++n) {
+            const float2 *ag = agg + (((long)b * K + k) * NSEG * N + n) * D + cc_;
+            const float *zg = zagg + (((long)b * K + k) * NSEG * N + n) * D + cc_;
+            float hin = 0.f;
+            int s2 = 0;
+            for (; s2 + 8 <= sgm; s2 += 8) {
+                float2 v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = ag[(s2 + j) * sstr];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) hin = fmaf(v[j].x, hin, v[j].y);
+            }
+            for (; s2 < sgm; ++s2) {
+                const float2 v = ag[s2 * sstr];
+                hin = fmaf(v.x, hin, v.y);
+            }
+            sH[n * kTP] = hin;
+            float zin = 0.f;
+            s2 = NSEG - 1;
+            for (; s2 - 8 >= sgm; s2 -= 8) {
+                float va[8], vz[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    va[j] = ag[(s2 - j) * sstr].x;
+                    vz[j] = zg[(s2 - j) * sstr];
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) zin = fmaf(va[j], zin, vz[j]);
+            }
+            for (; s2 > sgm; --s2) zin = fmaf(ag[s2 * sstr].x, zin, zg[s2 * sstr]);
+            sZ[n * kTP] = zin;
+        }
+    }
+
+    // sweep 1, left to right: the state entering every tile of the segment, per state
+    for (int i = 0; i < ntl; ++i) {
+        for (int n = 0; n < N; ++n) hs[(i * N + n) * kTP] = sH[n * kTP];
+        if (i == ntl - 1) break;   // (the last tile's own aggregate is not needed)
+        const int t = t0 + i, l0 = t * kTP;
+        const int idxv = load_idx(t);
+        TileOps<T, NK> cur;
+        fetch_ranks(w, rx, rp, idxv, cur);
+        stage_bc_n(idxv);
+        float tt[16], uf[16];
+        terms_t(w, cur, L - l0, tt, uf);
+#pragma nounroll
+        for (int n = 0; n < N; ++n) {
+            const float An = sA[n * kTP];
+            float a[16], bb[16], preA[4], preH[4], tA, tH;
+            read_row(n, bb);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                a[r] = __builtin_amdgcn_exp2f(tt[r] * An);
+                bb[r] = tt[r] * (bb[r] * uf[r]);
+            }
+            w.prefix(a, bb, preA, preH, tA, tH);
+            sH[n * kTP] = fmaf(tA, sH[n * kTP], tH);
+        }
+    }
+
+    // sweep 2, right to left
+    float accD = 0.f, accb = 0.f;
+    const bool cfull = ctile * kTP + kTP <= D;
+    for (int i = ntl - 1; i >= 0; --i) {
+        const int t = t0 + i, l0 = t * kTP, nvalid = L - l0;
+        const int idxv = load_idx(t);
+        TileOps<T, NK> cur;
+        fetch_ranks(w, rx, rp, idxv, cur);
+        float gy[16];
+        load_gy(nvalid, gy);
+        stage_bc_n(idxv);
+        float tt[16], uf[16], gdt[16], gua[16];
+        terms_t(w, cur, nvalid, tt, uf);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) gdt[r] = gua[r] = 0.f;
+#pragma nounroll
+        for (int n = 0; n < N; ++n) {
+            const float An = sA[n * kTP];
+            float a[16], bb[16], Bp[16], cg[16], preA[4], preH[4], tA, tH;
+            read_row(n, Bp);
+            read_row(N + n, cg);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                a[r] = __builtin_amdgcn_exp2f(tt[r] * An);
+                bb[r] = tt[r] * (Bp[r] * uf[r]);
+            }
+            w.prefix(a, bb, preA, preH, tA, tH);
+            const float hin = hs[(i * N + n) * kTP];
+            float hh[16], hp[16];   // h after / before every element
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                float hcur = fmaf(preA[g], hin, preH[g]);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    hp[4 * g + q] = hcur;
+                    hcur = fmaf(a[4 * g + q], hcur, bb[4 * g + q]);
+                    hh[4 * g + q] = hcur;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) cg[r] *= gy[r];
+            float qA[4], qZ[4], RA, RZ;
+            adj_fold(a, cg, qA, qZ, RA, RZ);
+            const float zin = sZ[n * kTP];
+            sZ[n * kTP] = fmaf(RA, zin, RZ);
+            float eb[16], ec[16], accA = 0.f;
+#pragma unroll
+            for (int g = 3; g >= 0; --g) {
+                float zr = fmaf(qA[g], zin, qZ[g]);
+#pragma unroll
+                for (int q = 3; q >= 0; --q) {
+                    const int r = 4 * g + q;
+                    const float gh = cg[r] + zr;
+                    zr = a[r] * gh;
+                    const float dtv = tt[r] * 0.693147180559945f;                 // dt
+                    gdt[r] = fmaf(gh, fmaf(a[r] * An, hp[r], Bp[r] * uf[r] * 1.44269504088896f), gdt[r]);
+                    gua[r] = fmaf(gh, tt[r] * Bp[r], gua[r]);                     // dt * B = t * (B ln2)
+                    eb[r] = gh * dtv * uf[r];
+                    ec[r] = gy[r] * hh[r];
+                    accA = fmaf(gh * hp[r], a[r] * dtv, accA);
+                }
+            }
+            accA += __shfl_xor(accA, 32, 64);
+            sG[n * kTP] += accA;
+            // position sums over this tile's 32 channels: transpose through LDS, once for dB_n and once for dC_n
+            float sbc[2];
+#pragma unroll
+            for (int which = 0; which < 2; ++which) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int pos = (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    trw[pos * kTS + r32] = cok ? (which == 0 ? eb[r] : ec[r]) : 0.f;
+                }
+                __builtin_amdgcn_wave_barrier();
+                float sv = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float4 v = *reinterpret_cast<const float4 *>(trw + r32 * kTS + 16 * hi + 4 * j);
+                    sv += (v.x + v.y) + (v.z + v.w);
+                }
+                __builtin_amdgcn_wave_barrier();
+                sbc[which] = sv + __shfl_xor(sv, 32, 64);
+            }
+            if (hi == 0 && l0 + r32 < L) {
+                const long o = ((((long)b * K + k) * CT + ctile) * N + n) * L + l0 + r32;
+                bpart[o] = sbc[0];
+                cpart[o] = sbc[1];
+            }
+        }
+        const unsigned ov = (unsigned)((l0 + 4 * hi) * D + cc_) * (unsigned)sizeof(T);
+        const bool full = cfull && l0 + kTP <= L;   // wave-uniform
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float gr = gdt[r] * (1.f - __builtin_amdgcn_exp2f(-tt[r]));   // softplus' = 1 - exp(-dt)
+            const float guv = fmaf(w.Dk, gy[r], gua[r]);
+            accD = fmaf(gy[r], uf[r], accD);
+            accb += gr;
+            const int p0 = (r & 3) + 8 * (r >> 2);
+            const unsigned vo = (full || (cok && p0 + 4 * hi < nvalid)) ? ov : kOutOfRange;
+            buf_store_elem<T>(ru, vo, (unsigned)p0 * orow, guv);
+            buf_store_elem<T>(rr, vo, (unsigned)p0 * orow, gr);
+        }
+    }
+    accD += __shfl_xor(accD, 32, 64);
+    accb += __shfl_xor(accb, 32, 64);
+    if (hi == 0 && cok) {
+        const long KD = (long)K * D, kd = (long)k * D + c;
+        float *gp = gpar + ((long)b * NSEG + sgm) * KD * (N + 2);
+        for (int n = 0; n < N; ++n) gp[kd * N + n] = sG[n * kTP] * sA[n * kTP];   // dL/dA_logs = dL/dA * A
+        gp[KD * N + kd] = accD;
+        gp[KD * (N + 1) + kd] = accb;
+    }
+}
+
+}  // namespace tramba
+
+// ---- backward of the state-looped wave-segment scan, d_state N = 2..16 (ss2d_seg_n_bwd_kernel)
+extern "C" int tramba_ss2d_scan_n_bwd_plan(int batch, int l, int d, int k, int n, int *tiles_per_segment, int *nseg)
+{
+    TRAMBA_CHECK(n != 1, "ss2d_scan_n_bwd: d_state 1 is served by tramba_ss2d_scan_bwd_cl");
+    TRAMBA_CHECK(n >= 2 && n <= kMaxN, "ss2d_scan_n_bwd: d_state %d outside 2..%d", n, kMaxN);
+    TRAMBA_CHECK(batch > 0 && l > 0 && d > 0 && k > 0, "ss2d_scan_n_bwd: empty shape");
+    const SegPlan p = seg_plan_n_bwd(l, (long)batch * k * ((d + kTP - 1) / kTP), n);
+    if (tiles_per_segment) *tiles_per_segment = p.nt;
+    if (nseg) *nseg = p.nseg;
+    return TRAMBA_OK;
+}
+
+// bytes: 16 for a single segment, else B*K*NSEG*N*D * (8 + 4): the forward (decay, state) pairs, then the adjoint states
+extern "C" size_t tramba_ss2d_scan_n_bwd_workspace(int batch, int l, int d, int k, int n, int dtype)
+{
+    if (batch <= 0 || l <= 0 || d <= 0 || k <= 0 || n < 2 || n > kMaxN) return 0;
+    if (dtype != TRAMBA_F32 && dtype != TRAMBA_BF16 && dtype != TRAMBA_F16) return 0;
+    const SegPlan p = seg_plan_n_bwd(l, (long)batch * k * ((d + kTP - 1) / kTP), n);
+    if (p.nseg <= 1) return 16;
+    return (size_t)batch * k * p.nseg * n * d * (sizeof(float2) + sizeof(float));
+}
+
+extern "C" int tramba_ss2d_scan_n_bwd_cl(const void *x, const float *xdbl, const int32_t *table, const float *dt_w,
+                                         const float *dt_bias, const float *A, const float *Ds, const void *gym, void *gu,
+                                         void *graw, float *bpart, float *cpart, float *gpar, void *workspace,
+                                         size_t workspace_bytes, int batch, int l, int d, int k, int r, int n, int dtype,
+                                         int gym_dtype, void *stream)
+{
+    TRAMBA_CHECK(n != 1, "ss2d_scan_n_bwd_cl: d_state 1 is served by tramba_ss2d_scan_bwd_cl");
+    TRAMBA_CHECK(n >= 2 && n <= kMaxN, "ss2d_scan_n_bwd_cl: d_state %d outside 2..%d", n, kMaxN);
+    TRAMBA_CHECK(x && xdbl && table && dt_w && dt_bias && A && Ds && gym && gu && graw && bpart && cpart && gpar,
+                 "ss2d_scan_n_bwd_cl: null tensor");
+    TRAMBA_CHECK(batch > 0 && l > 0 && d > 0 && k > 0 && r > 0, "ss2d_scan_n_bwd_cl: empty shape");
+    TRAMBA_CHECK(batch <= 65535 && k <= 65535, "ss2d_scan_n_bwd_cl: B or K exceeds this build's limits");
+    TRAMBA_CHECK(r <= 64, "ss2d_scan_n_bwd_cl: dt_rank %d > 64 unsupported", r);
+    TRAMBA_CHECK(dtype == TRAMBA_F32 || dtype == TRAMBA_BF16 || dtype == TRAMBA_F16, "ss2d_scan_n_bwd_cl: bad dtype %d", dtype);
+    TRAMBA_CHECK(gym_dtype == TRAMBA_F32 || gym_dtype == dtype, "ss2d_scan_n_bwd_cl: gym must be f32 or the input dtype");
+    TRAMBA_CHECK(aligned16(xdbl), "ss2d_scan_n_bwd_cl: xdbl must be 16-byte aligned");
+    TRAMBA_CHECK((double)batch * k * l * (double)d < 2.0e9, "ss2d_scan_n_bwd_cl: tensor too large for this build");
+    const int rg = xdbl_group_stride_n(r, n);
+    TRAMBA_CHECK(((double)l + 1024.0) * d * 4.0 < 2147483648.0 && (double)l * k * rg * 4.0 < 2147483648.0,
+                 "ss2d_scan_n_bwd_cl: L*D too large for 32-bit offsets");
+    const int ct = (d + kTP - 1) / kTP;
+    const SegPlan p = seg_plan_n_bwd(l, (long)batch * k * ct, n);
+    const long nwaves = (long)batch * k * ct * p.nseg;
+    TRAMBA_CHECK(nwaves < 2147483647L, "ss2d_scan_n_bwd_cl: too many segments");
+    TRAMBA_CHECK(p.nt * n <= kBwdNRows, "ss2d_scan_n_bwd_cl: plan exceeds the tile-state rows");
+    const size_t need = tramba_ss2d_scan_n_bwd_workspace(batch, l, d, k, n, dtype);
+    if (p.nseg > 1) {
+        TRAMBA_CHECK(workspace && workspace_bytes >= need, "ss2d_scan_n_bwd_cl: workspace of %zu bytes needed", need);
+        TRAMBA_CHECK(aligned16(workspace), "ss2d_scan_n_bwd_cl: workspace must be 16-byte aligned");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nk = (r + 15) / 16;
+    // algorithmic bytes: x, the x_proj rows and gy read once, gu and graw written
+    ProfScope prof(TRAMBA_PROF_SCAN_BWD, s,
+                   (double)batch * l * d * (dtype_size(dtype) + dtype_size(gym_dtype)) + (double)batch * l * k * rg * 4.0 +
+                       2.0 * (double)batch * k * l * (double)d * dtype_size(dtype));
+    float2 *agg = reinterpret_cast<float2 *>(workspace);
+    float *zagg = p.nseg > 1 ? reinterpret_cast<float *>(agg + (size_t)batch * k * p.nseg * n * d) : nullptr;
+    dim3 grid((unsigned)((nwaves + 3) / 4)), block(256);
+#define BWDN_G_(T, NK_, SP_, TG)                                                                                         \
+    do {                                                                                                                \
+        if (p.nseg > 1) {                                                                                               \
+            hipLaunchKernelGGL((ss2d_seg_n_kernel<T, float, NK_, SP_, 0>), grid, block, 0, s, (const T *)x, xdbl, table, dt_w, \
+                               dt_bias, A, Ds, (float *)nullptr, agg, l, d, k, r, n, ct, p.nt, p.nseg, nwaves);         \
+            hipLaunchKernelGGL((ss2d_seg_n_bwd_kernel<T, NK_, SP_, TG, 0>), grid, block, 0, s, (const T *)x, xdbl, table, \
+                               dt_w, dt_bias, A, Ds, (const TG *)gym, (T *)gu, (T *)graw, bpart, cpart, gpar,           \
+                               (const float2 *)agg, zagg, l, d, k, r, n, ct, p.nt, p.nseg, nwaves);                     \
+        }                                                                                                               \
+        hipLaunchKernelGGL((ss2d_seg_n_bwd_kernel<T, NK_, SP_, TG, 1>), grid, block, 0, s, (const T *)x, xdbl, table,    \
+                           dt_w, dt_bias, A, Ds, (const TG *)gym, (T *)gu, (T *)graw, bpart, cpart, gpar,               \
+                           (const float2 *)agg, zagg, l, d, k, r, n, ct, p.nt, p.nseg, nwaves);                         \
+    } while (0)
+#define BWDN_(T, NK_, SP_)                                                             \
+    do {                                                                               \
+        if (gym_dtype == TRAMBA_F32) BWDN_G_(T, NK_, SP_, float); else BWDN_G_(T, NK_, SP_, T); \
+    } while (0)
+#define BWDN_NK_(T, SP_)                 \
+    switch (nk) {                        \
+    case 1: BWDN_(T, 1, SP_); break;     \
+    case 2: BWDN_(T, 2, SP_); break;     \
+    case 3: BWDN_(T, 3, SP_); break;     \
+    default: BWDN_(T, 4, SP_); break;    \
+    }
+    if (dtype == TRAMBA_F32) {
+        BWDN_NK_(float, true)
+    } else if (dtype == TRAMBA_BF16) {
+        BWDN_NK_(__hip_bfloat16, false)
+    } else {
+        BWDN_NK_(__half, false)
+    }
+#undef BWDN_NK_
+#undef BWDN_
+#undef BWDN_G_
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}

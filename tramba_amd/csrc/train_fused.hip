@@ -183,21 +183,22 @@ static int launch_add_ln(const void *x, const void *y, const float *mask, long r
 }
 
 // ------------------------------------------------------------------------------------------------ SS2D backward glue
-// thread = one (b, k, i) sequence position; R8 = padded rank count, RG = R8 + 4.
+// thread = one (b, k, i) sequence position; R8 = padded rank count, N = d_state, BC = (2N + 3) & ~3, RG = R8 + BC (N = 1:
+// RG = R8 + 4).
 //   ranks  (B, K, L, R8) T     = xdbl[b, table[k][i], k*RG + 0 .. R8)          (the dt-rank rows in sequence order)
-//   g_seq  (B, K, L, RG) f32   columns R8 / R8 + 1 = sum over the CT channel tiles of the scan backward's dB / dC partials
-//                              (bpart / cpart: (B, K, CT, L) f32), columns R8 + 2, R8 + 3 = 0; the rank columns are written
-//                              by tramba_rows_gemm_cl afterwards
+//   g_seq  (B, K, L, RG) f32   columns R8 + n / R8 + N + n = sum over the CT channel tiles of the scan backward's dB_n / dC_n
+//                              partials (bpart / cpart: (B, K, CT, N, L) f32), the remaining pad columns = 0; the rank columns
+//                              are written by tramba_rows_gemm_cl afterwards
 template <typename T>
 __global__ __launch_bounds__(256) void ss2d_bwd_prep_kernel(const float *__restrict__ xdbl, const int32_t *__restrict__ table,
                                                            const float *__restrict__ bpart, const float *__restrict__ cpart,
                                                            T *__restrict__ ranks, float *__restrict__ gseq, int L, int K,
-                                                           int R8, int CT)
+                                                           int R8, int CT, int N, int BC)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L) return;
     const int k = blockIdx.y, b = blockIdx.z;
-    const int RG = R8 + 4, PC = K * RG;
+    const int RG = R8 + BC, PC = K * RG;
     const int p = table[(long)k * L + i];
     const float *src = xdbl + ((long)b * L + p) * PC + (long)k * RG;
     T *dst = ranks + (((long)b * K + k) * L + i) * R8;
@@ -206,14 +207,23 @@ __global__ __launch_bounds__(256) void ss2d_bwd_prep_kernel(const float *__restr
         const float o[4] = {v.x, v.y, v.z, v.w};
         store_pack<T, 4>(dst + j, o);
     }
-    const float *bp = bpart + (((long)b * K + k) * CT) * L + i;
-    const float *cp = cpart + (((long)b * K + k) * CT) * L + i;
-    float sb = 0.f, sc = 0.f;
-    for (int t = 0; t < CT; ++t) {   // fixed order: reproducible
-        sb += bp[(long)t * L];
-        sc += cp[(long)t * L];
+    const float *bp = bpart + (((long)b * K + k) * CT) * N * L + i;
+    const float *cp = cpart + (((long)b * K + k) * CT) * N * L + i;
+    float *grow = gseq + (((long)b * K + k) * L + i) * RG + R8;
+    for (int j0 = 0; j0 < BC; j0 += 4) {
+        float o[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = j0 + e;
+            float sv = 0.f;
+            if (j < 2 * N) {
+                const float *q = (j < N ? bp + (long)j * L : cp + (long)(j - N) * L);
+                for (int t = 0; t < CT; ++t) sv += q[(long)t * N * L];   // fixed order: reproducible
+            }
+            o[e] = sv;
+        }
+        *reinterpret_cast<float4 *>(grow + j0) = make_float4(o[0], o[1], o[2], o[3]);
     }
-    *reinterpret_cast<float4 *>(gseq + (((long)b * K + k) * L + i) * RG + R8) = make_float4(sb, sc, 0.f, 0.f);
 }
 
 // block = 4 waves, wave = one pixel; lane j < RG walks the pixel's CSR entries (ascending entry = ascending direction)
@@ -222,23 +232,23 @@ template <typename T>
 __global__ __launch_bounds__(256) void ss2d_bwd_assemble_kernel(const float *__restrict__ gseq,
                                                                const int32_t *__restrict__ inv_ptr,
                                                                const int32_t *__restrict__ inv_idx, T *__restrict__ out,
-                                                               long npix, int L, int K, int R, int R8)
+                                                               long npix, int L, int K, int R, int R8, int N, int BC)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const long wid = (long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (wid >= npix) return;
     const int b = (int)((unsigned long)wid / (unsigned)L), p = (int)((unsigned long)wid % (unsigned)L);
-    const int RG = R8 + 4;
+    const int RG = R8 + BC;
     const int e0 = __builtin_amdgcn_readfirstlane(inv_ptr[p]), e1 = __builtin_amdgcn_readfirstlane(inv_ptr[p + 1]);
     const float *gb = gseq + (long)b * K * L * RG;
     T *orow = out + ((long)b * L + p) * (long)(K * RG);
     // a lane owns column `lane` (and lane + 64 when RG > 64) of every direction group; columns R .. R8 - 1 (rank padding)
-    // and R8 + 2, R8 + 3 leave as zeros.  The entry list is fetched 64 per load, the rows 8 per batch (all in flight
+    // and R8 + 2N .. RG - 1 leave as zeros.  The entry list is fetched 64 per load, the rows 8 per batch (all in flight
     // before any is added); entries ascend, i.e. they are grouped by direction: a group's sums leave when the next begins.
     const int l1 = lane + kWave;
     const bool col0 = lane < RG, col1 = l1 < RG;
-    const bool live0 = lane < R || lane == R8 || lane == R8 + 1;
-    const bool live1 = l1 < R || l1 == R8 || l1 == R8 + 1;
+    const bool live0 = lane < R || (lane >= R8 && lane < R8 + 2 * N);
+    const bool live1 = l1 < R || (l1 >= R8 && l1 < R8 + 2 * N);
     float a0 = 0.f, a1 = 0.f;
     int k = 0;
     auto flush = [&]() {
@@ -413,19 +423,45 @@ extern "C" int tramba_add_layernorm_cl(const void *x, const void *y, const float
     return TRAMBA_OK;
 }
 
-extern "C" int tramba_ss2d_bwd_prep_cl(const float *xdbl, const int32_t *table, const float *bpart, const float *cpart,
-                                       void *ranks, float *gseq, int batch, int l, int k, int r, int ctiles, int dtype,
-                                       void *stream)
+extern "C" int tramba_ss2d_bwd_prep_n_cl(const float *xdbl, const int32_t *table, const float *bpart, const float *cpart,
+                                         void *ranks, float *gseq, int batch, int l, int k, int r, int n, int ctiles, int dtype,
+                                         void *stream)
 {
     TRAMBA_CHECK(xdbl && table && bpart && cpart && ranks && gseq, "ss2d_bwd_prep_cl: null tensor");
     TRAMBA_CHECK(batch > 0 && l > 0 && k > 0 && r > 0 && ctiles > 0 && batch <= 65535 && k <= 65535,
                  "ss2d_bwd_prep_cl: bad shape");
+    TRAMBA_CHECK(n >= 1 && n <= 16, "ss2d_bwd_prep_cl: d_state %d outside 1..16", n);
     TRAMBA_CHECK(aligned16(xdbl) && aligned16(ranks) && aligned16(gseq), "ss2d_bwd_prep_cl: 16-byte alignment");
-    const int r8 = (r + 7) & ~7;
+    const int r8 = (r + 7) & ~7, bc = (2 * n + 3) & ~3;
     dim3 grid((unsigned)((l + 255) / 256), (unsigned)k, (unsigned)batch), block(256);
     TRAMBA_DISPATCH_DTYPE(dtype, T,
         hipLaunchKernelGGL((ss2d_bwd_prep_kernel<T>), grid, block, 0, (hipStream_t)stream, xdbl, table, bpart, cpart,
-                           (T *)ranks, gseq, l, k, r8, ctiles));
+                           (T *)ranks, gseq, l, k, r8, ctiles, n, bc));
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_ss2d_bwd_prep_cl(const float *xdbl, const int32_t *table, const float *bpart, const float *cpart,
+                                       void *ranks, float *gseq, int batch, int l, int k, int r, int ctiles, int dtype,
+                                       void *stream)
+{
+    return tramba_ss2d_bwd_prep_n_cl(xdbl, table, bpart, cpart, ranks, gseq, batch, l, k, r, 1, ctiles, dtype, stream);
+}
+
+extern "C" int tramba_ss2d_bwd_assemble_n_cl(const float *gseq, const int32_t *inv_ptr, const int32_t *inv_idx, void *out,
+                                             int batch, int l, int k, int r, int n, int dtype, void *stream)
+{
+    TRAMBA_CHECK(gseq && inv_ptr && inv_idx && out, "ss2d_bwd_assemble_cl: null tensor");
+    TRAMBA_CHECK(batch > 0 && l > 0 && k > 0 && r > 0, "ss2d_bwd_assemble_cl: bad shape");
+    TRAMBA_CHECK(n >= 1 && n <= 16, "ss2d_bwd_assemble_cl: d_state %d outside 1..16", n);
+    const int r8 = (r + 7) & ~7, bc = (2 * n + 3) & ~3;
+    TRAMBA_CHECK(r8 + bc <= 2 * kWave, "ss2d_bwd_assemble_cl: dt_rank %d too large", r);
+    const long npix = (long)batch * l;
+    TRAMBA_CHECK(npix < 2147483647L, "ss2d_bwd_assemble_cl: too many pixels");
+    dim3 grid((unsigned)((npix + 3) / 4)), block(256);
+    TRAMBA_DISPATCH_DTYPE(dtype, T,
+        hipLaunchKernelGGL((ss2d_bwd_assemble_kernel<T>), grid, block, 0, (hipStream_t)stream, gseq, inv_ptr, inv_idx,
+                           (T *)out, npix, l, k, r, r8, n, bc));
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -433,18 +469,7 @@ extern "C" int tramba_ss2d_bwd_prep_cl(const float *xdbl, const int32_t *table, 
 extern "C" int tramba_ss2d_bwd_assemble_cl(const float *gseq, const int32_t *inv_ptr, const int32_t *inv_idx, void *out,
                                            int batch, int l, int k, int r, int dtype, void *stream)
 {
-    TRAMBA_CHECK(gseq && inv_ptr && inv_idx && out, "ss2d_bwd_assemble_cl: null tensor");
-    TRAMBA_CHECK(batch > 0 && l > 0 && k > 0 && r > 0, "ss2d_bwd_assemble_cl: bad shape");
-    const int r8 = (r + 7) & ~7;
-    TRAMBA_CHECK(r8 + 4 <= 2 * kWave, "ss2d_bwd_assemble_cl: dt_rank %d too large", r);
-    const long npix = (long)batch * l;
-    TRAMBA_CHECK(npix < 2147483647L, "ss2d_bwd_assemble_cl: too many pixels");
-    dim3 grid((unsigned)((npix + 3) / 4)), block(256);
-    TRAMBA_DISPATCH_DTYPE(dtype, T,
-        hipLaunchKernelGGL((ss2d_bwd_assemble_kernel<T>), grid, block, 0, (hipStream_t)stream, gseq, inv_ptr, inv_idx,
-                           (T *)out, npix, l, k, r, r8));
-    TRAMBA_LAUNCH_CHECK();
-    return TRAMBA_OK;
+    return tramba_ss2d_bwd_assemble_n_cl(gseq, inv_ptr, inv_idx, out, batch, l, k, r, 1, dtype, stream);
 }
 
 extern "C" int tramba_dw_unpack_grad(const float *gwt, float *g7, float *g5, float *g3, float *gb, int nb, int c, int ks,

@@ -59,6 +59,11 @@ SIGNATURES = {
     "tramba_ss2d_scan_bwd_cl": (c_int, [c_vp] * 12 + [c_int, c_vp, c_vp, ctypes.c_size_t] + [c_int] * 9 + [c_vp]),
     "tramba_ss2d_bwd_prep_cl": (c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp]),
     "tramba_ss2d_bwd_assemble_cl": (c_int, [c_vp] * 4 + [c_int] * 5 + [c_vp]),
+    "tramba_ss2d_scan_n_bwd_workspace": (ctypes.c_size_t, [c_int] * 6),
+    "tramba_ss2d_scan_n_bwd_plan": (c_int, [c_int] * 5 + [c_vp] * 2),
+    "tramba_ss2d_scan_n_bwd_cl": (c_int, [c_vp] * 14 + [ctypes.c_size_t] + [c_int] * 8 + [c_vp]),
+    "tramba_ss2d_bwd_prep_n_cl": (c_int, [c_vp] * 6 + [c_int] * 7 + [c_vp]),
+    "tramba_ss2d_bwd_assemble_n_cl": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
     "tramba_ss2d_merge_grad_cl": (c_int, [c_vp] * 8 + [c_int] * 4 + [c_f, c_int, c_int, c_int, c_vp]),
     "tramba_ss2d_merge_norm_cl": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_f, c_int, c_int, c_int, c_vp]),
     "tramba_layernorm_cl": (c_int, [c_vp] * 4 + [c_i64, c_int, c_f, c_int, c_int, c_vp]),
@@ -567,6 +572,15 @@ def ss2d_merge_sum_cl(ys, order: ScanOrder, out_dtype):
     return y
 
 
+def ss2d_scan_n_bwd_plan(b, l, d, k, n):
+    """(tiles of 32 positions per segment, segments per sequence) of the N = 2..16 scan backward (ss2d_scan_bwd_cl with a
+    (K*D, N) `A`): its own plan, segments short enough for their tile-entry states to stay in LDS; one segment = one launch."""
+    nt, nseg = ctypes.c_int(0), ctypes.c_int(0)
+    _check(lib().tramba_ss2d_scan_n_bwd_plan(b, l, d, k, n, ctypes.addressof(nt), ctypes.addressof(nseg)),
+           "ss2d_scan_n_bwd_plan")
+    return nt.value, nseg.value
+
+
 def ss2d_scan_bwd_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, gym, g_seq=None, states=None, a_log=False,
                      bc_partials=False):
     """Backward of ss2d_scan_cl + merge.  gym (B, L, D) f32 = gradient of the merged map.
@@ -576,16 +590,35 @@ def ss2d_scan_bwd_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, gym, g_seq
     states: the buffer the forward launch filled (ss2d_scan_cl(states=...)): the sweep that recomputes them is skipped.
     a_log: `A` is the parameter A_logs; gpar's first plane is then dL/dA_logs.
     bc_partials: gB / gC come back as (B, K, ceil(D/32), L) per-channel-tile partial sums written without atomics (no zero
-    fill; ss2d_bwd_prep adds them in a fixed order)."""
+    fill; ss2d_bwd_prep adds them in a fixed order).
+    d_state N = 2..16 (backward of ss2d_scan_n_cl + merge): `A` is (K*D, N) f32, already negated (= -exp(A_logs)), xdbl has
+    the (B, L, K*RG(R, N)) layout, and bc_partials is required (g_seq, states and a_log do not apply).  gB / gC are then
+    (B, K, ceil(D/32), N, L) partials and gpar is (B*NSEG, K*D*(N+2)): one slab per (batch, segment of ss2d_scan_n_bwd_plan)
+    holding [dL/dA_logs (K*D, N) | dD (K*D) | dbias (K*D)] -- slab_sum(gpar) gives the three parameter gradients.  gu / graw
+    are handed out by the launch (every element written); nothing is accumulated and nothing needs a zero fill."""
     _dev(x, xdbl, dt_w, dt_bias, A, Ds, gym, g_seq)
     b, l, d = x.shape
     k, r = order.k, dt_w.shape[-1]
+    n = A.shape[1] if A.dim() == 2 else 1
     if gym.dtype not in (torch.float32, x.dtype) or gym.shape != x.shape:
         raise TrambaHipError("ss2d_scan_bwd_cl: gym must be (B, L, D) in f32 or the activation dtype")
+    ct = (d + 31) // 32
+    if n != 1:
+        if A.shape[0] != k * d or not 2 <= n <= 16:
+            raise TrambaHipError(f"ss2d_scan_bwd_cl: A must be (K*D,) or (K*D, N) = ({k * d}, 2..16), got {tuple(A.shape)}")
+        rg = ss2d_group_stride(r, n)
+        if xdbl.dtype != torch.float32 or xdbl.shape != (b, l, k * rg):
+            raise TrambaHipError(f"ss2d_scan_bwd_cl: xdbl must be f32 (B, L, K*RG(R, N)) = ({b}, {l}, {k}*{rg}), "
+                                 f"got {xdbl.dtype} {tuple(xdbl.shape)}")
+        if l != order.l or dt_w.shape != (k, d, r) or Ds.numel() != k * d or dt_bias.numel() != k * d:
+            raise TrambaHipError("ss2d_scan_bwd_cl: parameter shapes do not match (K, D, R)")
+        if not bc_partials or g_seq is not None or states is not None or a_log:
+            raise TrambaHipError("ss2d_scan_bwd_cl: d_state > 1 needs bc_partials=True and takes no g_seq / states / a_log")
+        ct *= n
     gu = torch.empty((b, k, l, d), dtype=x.dtype, device=x.device)
     graw = torch.empty_like(gu)
     if bc_partials:
-        gB = torch.empty((b, k, (d + 31) // 32, l), dtype=torch.float32, device=x.device)
+        gB = torch.empty((b, k, ct, l), dtype=torch.float32, device=x.device)
         gC = torch.empty_like(gB)
         bcs = 1
     elif g_seq is None:
@@ -597,7 +630,16 @@ def ss2d_scan_bwd_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, gym, g_seq
         if g_seq.shape != (b, k, l, rg) or g_seq.dtype != torch.float32 or not g_seq.is_contiguous():
             raise TrambaHipError(f"ss2d_scan_bwd_cl: g_seq must be a contiguous float32 (B, K, L, {rg}) tensor")
         gB, gC, bcs = g_seq[..., rg - 4], g_seq[..., rg - 3], rg
-    gpar = torch.empty((b, 3, k, d), dtype=torch.float32, device=x.device)
+    nslab = b if n == 1 else b * ss2d_scan_n_bwd_plan(b, l, d, k, n)[1]
+    gpar = torch.empty((nslab, 3, k, d) if n == 1 else (nslab, k * d * (n + 2)), dtype=torch.float32, device=x.device)
+    if n != 1:
+        ws_bytes = lib().tramba_ss2d_scan_n_bwd_workspace(b, l, d, k, n, dt(x))
+        ws = _scan_workspace(x.device, ws_bytes)      # launch-local: written and read inside this one call
+        _check(lib().tramba_ss2d_scan_n_bwd_cl(_ptr(x), _ptr(xdbl), _ptr(order.table), _ptr(dt_w), _ptr(dt_bias), _ptr(A),
+                                               _ptr(Ds), _ptr(gym), _ptr(gu), _ptr(graw), _ptr(gB), _ptr(gC), _ptr(gpar),
+                                               _ptr(ws), ws_bytes, b, l, d, k, r, n, dt(x), dt(gym), _stream()),
+               "ss2d_scan_n_bwd_cl")
+        return gu, graw, gB.view(b, k, ct // n, n, l), gC.view(b, k, ct // n, n, l), gpar
     ws_bytes = lib().tramba_ss2d_scan_bwd_workspace(b, l, d, k)
     if states is not None:
         _dev(states)
@@ -613,31 +655,38 @@ def ss2d_scan_bwd_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, gym, g_seq
     return gu, graw, gB, gC, gpar
 
 
-def ss2d_bwd_prep(xdbl, order: ScanOrder, bpart, cpart, r, dtype):
+def ss2d_bwd_prep(xdbl, order: ScanOrder, bpart, cpart, r, dtype, n=1):
     """after ss2d_scan_bwd_cl(bc_partials=True): (ranks (B,K,L,R8) `dtype` = the dt-rank rows of xdbl in sequence order,
-    g_seq (B,K,L,RG) f32 with the summed dB / dC in columns R8, R8 + 1; the rank columns are for rows_gemm_cl to fill)"""
+    g_seq (B,K,L,RG) f32 with the summed dB / dC in columns R8, R8 + 1; the rank columns are for rows_gemm_cl to fill).
+    d_state n > 1: bpart / cpart are (B, K, CT, n, L), RG = RG(r, n), dB_0.. in columns R8 .., dC_0.. in columns R8 + n .."""
     _dev(xdbl, bpart, cpart)
     b, l, pc = xdbl.shape
     k = order.k
-    rg = ss2d_group_stride(r)
-    if pc != k * rg or bpart.shape != cpart.shape or bpart.shape[:2] != (b, k) or bpart.shape[3] != l:
-        raise TrambaHipError("ss2d_bwd_prep: operand shapes do not match")
-    ranks = torch.empty((b, k, l, rg - 4), dtype=dtype, device=xdbl.device)
+    rg = ss2d_group_stride(r, n)
+    r8 = (r + 7) & ~7
+    want = (b, k, bpart.shape[2], l) if n == 1 else (b, k, bpart.shape[2], n, l)
+    if pc != k * rg or bpart.shape != cpart.shape or tuple(bpart.shape) != want:
+        raise TrambaHipError(f"ss2d_bwd_prep: xdbl must be (B, L, {k}*{rg}) and bpart / cpart (B, K, CT"
+                             f"{'' if n == 1 else ', ' + str(n)}, L), got {tuple(xdbl.shape)}, {tuple(bpart.shape)}, "
+                             f"{tuple(cpart.shape)}")
+    ranks = torch.empty((b, k, l, r8), dtype=dtype, device=xdbl.device)
     gseq = torch.empty((b, k, l, rg), dtype=torch.float32, device=xdbl.device)
-    _check(lib().tramba_ss2d_bwd_prep_cl(_ptr(xdbl), _ptr(order.table), _ptr(bpart), _ptr(cpart), _ptr(ranks), _ptr(gseq),
-                                         b, l, k, r, bpart.shape[2], _DT[dtype], _stream()), "ss2d_bwd_prep_cl")
+    _check(lib().tramba_ss2d_bwd_prep_n_cl(_ptr(xdbl), _ptr(order.table), _ptr(bpart), _ptr(cpart), _ptr(ranks), _ptr(gseq),
+                                           b, l, k, r, n, bpart.shape[2], _DT[dtype], _stream()), "ss2d_bwd_prep_cl")
     return ranks, gseq
 
 
-def ss2d_bwd_assemble(gseq, order: ScanOrder, r, dtype):
-    """gseq (B,K,L,RG) f32 in sequence order -> (B, L, K*RG) `dtype` in spatial order (gather-sum through the inverse table)"""
+def ss2d_bwd_assemble(gseq, order: ScanOrder, r, dtype, n=1):
+    """gseq (B,K,L,RG) f32 in sequence order -> (B, L, K*RG) `dtype` in spatial order (gather-sum through the inverse table);
+    RG = RG(r, n) at d_state n"""
     _dev(gseq)
     b, k, l, rg = gseq.shape
-    if k != order.k or l != order.l or rg != ss2d_group_stride(r):
-        raise TrambaHipError("ss2d_bwd_assemble: gseq does not match the scan order / dt_rank")
+    if k != order.k or l != order.l or rg != ss2d_group_stride(r, n):
+        raise TrambaHipError(f"ss2d_bwd_assemble: gseq must be (B, {order.k}, {order.l}, RG(r, n) = "
+                             f"{ss2d_group_stride(r, n)}), got {tuple(gseq.shape)}")
     out = torch.empty((b, l, k * rg), dtype=dtype, device=gseq.device)
-    _check(lib().tramba_ss2d_bwd_assemble_cl(_ptr(gseq), _ptr(order.inv_ptr), _ptr(order.inv_idx), _ptr(out), b, l, k, r,
-                                             _DT[dtype], _stream()), "ss2d_bwd_assemble_cl")
+    _check(lib().tramba_ss2d_bwd_assemble_n_cl(_ptr(gseq), _ptr(order.inv_ptr), _ptr(order.inv_idx), _ptr(out), b, l, k, r,
+                                               n, _DT[dtype], _stream()), "ss2d_bwd_assemble_cl")
     return out
 
 

@@ -1436,21 +1436,24 @@ class _DwmsActCL(torch.autograd.Function):
         return gh, g3.to(t), gbs[0], g5.to(t), gbs[1], g7.to(t), gbs[2]
 
 
-def _xproj_padded(w, dtype):
-    """the x_proj weight (K, R + 2, D) in the scan kernels' padded (K*RG, D) layout and its transpose (or None), `dtype`:
-    the shadows written after the optimizer step when they are current, else built here"""
+def _xproj_padded(w, dtype, n=1):
+    """the x_proj weight (K, R + 2n, D) in the scan kernels' padded (K*RG, D) layout and its transpose (or None), `dtype`:
+    the shadows written after the optimizer step when they are current (d_state n = 1 only), else built here"""
     k, r2, d = w.shape
-    r = r2 - 2
-    rg = hip.ss2d_group_stride(r)
-    ent = _lowp_shadow.get(id(w))
+    r = r2 - 2 * n
+    rg = hip.ss2d_group_stride(r, n)
+    r8 = (r + 7) & ~7
+    ent = _lowp_shadow.get(id(w)) if n == 1 else None
     if (ent is not None and ent[1] == w._version and ent[0].dtype == dtype and ent[2]() is w
             and ent[0].shape == (k * rg, d)):
         return ent[0], ent[3]
     wl = w.detach().to(dtype)
     parts = [wl[:, :r]]
-    if rg - 4 - r:
-        parts.append(_zeros_const((k, rg - 4 - r, d), dtype, w.device))
-    parts += [wl[:, r:], _zeros_const((k, 2, d), dtype, w.device)]
+    if r8 - r:
+        parts.append(_zeros_const((k, r8 - r, d), dtype, w.device))
+    parts.append(wl[:, r:])
+    if rg - r8 - 2 * n:
+        parts.append(_zeros_const((k, rg - r8 - 2 * n, d), dtype, w.device))
     return torch.cat(parts, dim=1).view(k * rg, d), None
 
 
@@ -1541,6 +1544,87 @@ class _SS2DInnerCL(torch.autograd.Function):
                 gxw = torch.cat((gp_[:, :r], gp_[:, r8:r8 + 2]), dim=1).to(xwdtype)
         gp = hip.slab_sum(gpar, defer=ctx.par_f32)                                             # (3,K,D): contiguous planes, leaf gradients
         return (gz, None, gxw, g_dtw.to(dtwdtype), gp[2].reshape(dtbshape), gp[0].reshape(alshape), gp[1].reshape(-1), None)
+
+
+class _SS2DInnerNCL(torch.autograd.Function):
+    """_SS2DInnerCL at d_state N = 2..16 (opt-in, ops.set_fused_dstate_training): same inputs with x_proj_weight (K,R+2N,D)
+    and A_logs (K*D,N), same launch sequence.  Forward: x_proj once in spatial order (GEMM, fp32 rows in the
+    [R8 ranks | B_0.. | C_0.. | pad] layout) -> A = -exp(A_logs) -> tramba_ss2d_scan_n_cl -> merge.  Backward:
+    tramba_ss2d_scan_n_bwd_cl (recomputes the states from the saved x, x_dbl rows and A; dB_n / dC_n as per-channel-tile
+    partials, dA_logs / dD / dbias as per-(batch, segment) slabs, no atomics) -> tramba_ss2d_bwd_prep_n_cl -> the two
+    per-direction projections -> tramba_ss2d_bwd_assemble_n_cl -> x_proj input gradient -> tramba_ss2d_merge_grad_cl.
+    Nothing that must survive from forward to backward lives in the per-stream scan workspace: only saved tensors."""
+
+    @staticmethod
+    def forward(ctx, z, xs, xw, dt_w, dt_b, a_logs, ds, order):
+        z, xs = z.contiguous(), xs.contiguous()
+        n = a_logs.shape[-1]
+        wa, _ = _xproj_padded(xw, xs.dtype, n)
+        xdbl = hip.linear_cl(xs, wa, out_dtype=torch.float32)
+        dtw, dtb = dt_w.detach().float().contiguous(), dt_b.detach().float().reshape(-1).contiguous()
+        dsf = ds.detach().float().contiguous()
+        a_neg = torch.exp(a_logs.detach().float().reshape(-1, n)).neg_()            # (K*D, N), vmamba.py:246
+        ys = hip.ss2d_scan_n_cl(xs, xdbl, order, dtw, dtb, a_neg, dsf, xs.dtype)
+        ctx.save_for_backward(z, xs, xdbl, dtw, dtb, a_neg, dsf, wa)
+        ctx.order = order
+        ent = _lowp_shadow.get(id(dt_w))
+        ctx.dtw_t = ent[3] if (ent is not None and ent[1] == dt_w._version and ent[2]() is dt_w
+                               and ent[3] is not None and ent[3].dtype == xs.dtype) else None
+        ctx.meta = (xw.dtype, xw.shape, dt_w.dtype, dt_b.shape, a_logs.shape)
+        ctx.par_f32 = dt_b.dtype == a_logs.dtype == ds.dtype == torch.float32
+        return hip.ss2d_merge_sum_cl(ys, order, xs.dtype)
+
+    @staticmethod
+    def backward(ctx, gym):
+        z, xs, xdbl, dtw, dtb, a_neg, dsf, wa = ctx.saved_tensors
+        order = ctx.order
+        xwdtype, xwshape, dtwdtype, dtbshape, alshape = ctx.meta
+        b, l, d = xs.shape
+        k, r, n = order.k, dtw.shape[-1], a_neg.shape[1]
+        rg = hip.ss2d_group_stride(r, n)
+        r8 = (r + 7) & ~7
+        gym = gym.contiguous()
+        if gym.dtype not in (torch.float32, xs.dtype):
+            gym = gym.float()
+        gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs, xdbl, order, dtw, dtb, a_neg, dsf, gym, bc_partials=True)
+        cd = torch.bfloat16 if xs.dtype == torch.float32 else xs.dtype
+        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if xs.dtype == torch.float32 else cd, n)
+        if xs.dtype != torch.float32:
+            g_dtw = hip.wgrad_grouped_cl(graw, ranks, defer=ranks.shape[-1] == r and dtwdtype == torch.float32)
+            dtw_t = ctx.dtw_t            # (K, R, D): the shadow written after the optimizer step, when current
+            if dtw_t is None:
+                dtw_t = dtw.transpose(1, 2).to(cd).contiguous()
+            hip.rows_gemm_cl(graw.view(b * k, l, d), dtw_t, gseq.view(b * k, l, rg), r)
+        else:   # fp32 validation mode: three passes on bf16 splits
+            gh, gl = _split16(graw)
+            rh, rl = _split16(ranks)
+            wh, wl = _split16(dtw.transpose(1, 2).contiguous())                                    # (K, R, D)
+            g_dtw = hip.wgrad_grouped_cl(gh, rh) + hip.wgrad_grouped_cl(gh, rl) + hip.wgrad_grouped_cl(gl, rh)
+            tmp = torch.zeros_like(gseq)             # (validation mode only; the 16-bit path above allocates nothing here)
+            hip.rows_gemm_cl(gh.view(b * k, l, d), wh, gseq.view(b * k, l, rg), r)
+            for ga_, wa_ in ((gh, wl), (gl, wh)):
+                hip.rows_gemm_cl(ga_.view(b * k, l, d), wa_, tmp.view(b * k, l, rg), r)
+                gseq[..., :r] += tmp[..., :r]
+        if g_dtw.shape[-1] != r:
+            g_dtw = g_dtw[..., :r].contiguous()
+        g_xd = hip.ss2d_bwd_assemble(gseq, order, r, xs.dtype, n).view(b * l, k * rg)     # spatial order, activation dtype
+        gz = None
+        if ctx.needs_input_grad[0]:
+            t = _dgrad(g_xd, wa, None).view(b, l, d)                                       # the x_proj branch's share
+            gz = hip.ss2d_merge_grad_cl(gu, order, t, z)                                   # (merge(gu) + t) * silu'(z)
+        gxw = None
+        if ctx.needs_input_grad[2]:
+            if xs.dtype != torch.float32:
+                segs = [s_ for g in range(k) for s_ in ((g * rg, r), (g * rg + r8, 2 * n))]
+                gxw = hip.wgrad_rows_cl(g_xd, xs.view(b * l, d), segs, defer=xwdtype == torch.float32).view(k, r + 2 * n, d)
+                gxw = gxw.to(xwdtype)
+            else:
+                gp_ = _wgrad(g_xd, xs.view(b * l, d))[0].view(k, rg, d)
+                gxw = torch.cat((gp_[:, :r], gp_[:, r8:r8 + 2 * n]), dim=1).to(xwdtype)
+        kd = k * d
+        gp = hip.slab_sum(gpar, defer=ctx.par_f32)              # [dA_logs (K*D, N) | dD | dbias]: contiguous leaf gradients
+        return (gz, None, gxw, g_dtw.to(dtwdtype), gp[kd * (n + 1):].reshape(dtbshape), gp[:kd * n].reshape(alshape),
+                gp[kd * n:kd * (n + 1)], None)
 
 
 
@@ -1668,9 +1752,20 @@ class SS2D(nn.Module):
         y = self.out_norm._forward_cl(y, act=hip.ACT_GELU)
         return y.to(x.dtype)
 
+    def _train_fused_n_ok(self, x):
+        """d_state 2..16 on the fused training path: only with ops.set_fused_dstate_training(True)"""
+        if not (x.is_cuda and 2 <= self.d_state <= 16):
+            return False
+        from . import ops
+        return (ops.get_fused_dstate_training() and self.dt_rank <= 64
+                and getattr(self.scan, "_tramba_family", None) is not None
+                and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
+                and self.scan._tramba_k == self.k_group)
+
     def _train_path_ok(self, x):
-        """the fused training path: built-in scan family, N = 1, depth-wise conv present, autograd on"""
-        return (self.with_dconv and self._train_fused_ok(x) and isinstance(self.dropout, nn.Identity)
+        """the fused training path: built-in scan family, N = 1 (N = 2..16 when opted in), depth-wise conv present, autograd on"""
+        return (self.with_dconv and (self._train_fused_ok(x) or self._train_fused_n_ok(x))
+                and isinstance(self.dropout, nn.Identity)
                 and not _infer(x, self.in_proj.weight, self.x_proj_weight, self.dt_projs_weight, self.A_logs))
 
     def _forward_train_cl(self, xn):
@@ -1682,8 +1777,9 @@ class SS2D(nn.Module):
         xi = _LinearTrainCL.apply(xn, self.in_proj.weight, self.in_proj.bias)
         z, xs = _DwConvActCL.apply(xi, self.conv2d.weight, self.conv2d.bias, hip.ACT_SILU)
         order = hip.scan_order(self.scan._tramba_family, h, w, xn.device)
-        ym = _SS2DInnerCL.apply(z.view(b, h * w, d), xs.view(b, h * w, d), self.x_proj_weight, self.dt_projs_weight,
-                                self.dt_projs_bias, self.A_logs, self.Ds, order)
+        inner = _SS2DInnerCL if self.d_state == 1 else _SS2DInnerNCL
+        ym = inner.apply(z.view(b, h * w, d), xs.view(b, h * w, d), self.x_proj_weight, self.dt_projs_weight,
+                         self.dt_projs_bias, self.A_logs, self.Ds, order)
         # out_norm and the GELU of vmamba.py:270 in one pass; out_proj's input-gradient GEMM carries the GELU's gradient
         _, yn, ya = _AddLayerNormCL.apply(ym.view(b, h, w, d), None, None, self.out_norm.weight, self.out_norm.bias,
                                           self.out_norm.eps, hip.ACT_GELU, False)

@@ -51,6 +51,36 @@ def deterministic_scan(mode=True):
         set_deterministic_scan(prev)
 
 
+_fused_dstate_training = False
+
+
+def set_fused_dstate_training(on):
+    """Opt in (True) or out (False, the default) of the fused channels-last TRAINING path of SS2D at d_state 2..16
+    (modules._SS2DInnerCL on hip.ss2d_scan_n_cl and the state-looped scan backward).  Off, a module with
+    d_state > 1 under autograd takes the reference graph with the scan plugins, as before.  Returns the previous value."""
+    global _fused_dstate_training
+    if on is not True and on is not False:
+        raise ValueError(f"set_fused_dstate_training: the value must be True or False, got {on!r}")
+    prev, _fused_dstate_training = _fused_dstate_training, on
+    return prev
+
+
+def get_fused_dstate_training():
+    """the value set by set_fused_dstate_training"""
+    return _fused_dstate_training
+
+
+@contextlib.contextmanager
+def fused_dstate_training(on=True):
+    """with fused_dstate_training(True): ... -- set_fused_dstate_training for a block; the previous value comes back on
+    exit, whatever happens inside"""
+    prev = set_fused_dstate_training(on)
+    try:
+        yield
+    finally:
+        set_fused_dstate_training(prev)
+
+
 def _scan_is_deterministic():
     if _det_mode == "torch":
         return torch.are_deterministic_algorithms_enabled()
