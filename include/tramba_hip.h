@@ -459,6 +459,25 @@ int tramba_linear_ln_cl(const void *x, const void *w_folded, const float *colsum
  * FreqSS2Dv6, freq_mamba.py:52).  16-bit dtypes, k1 % 64 == 0 and (k - k1) % 64 == 0. */
 int tramba_linear2_cl(const void *x1, const void *x2, int k1, const void *w, const float *bias, const void *residual,
                       void *y, int64_t m, int n, int k, int act, int dtype, int out_dtype, void *stream);
+/* Row statistics handed from the GEMM that writes a map to the LayerNorm-folded GEMM that reads it next (16-bit inference:
+ * fc2 + residual -> norm -> in_proj, out_proj + residual -> norm2 -> fc1).
+ * Producer (tramba_linear_rowstat_cl / tramba_linear2_rowstat_cl = the plain / two-source GEMM with one more output):
+ * rowstat_out, a float2 slab (M, ceil(N / 64)), receives per row and 64-column tile (sum, sum of squares) of the valid
+ * columns of y as rounded to the output dtype -- fp32, fixed order, no atomics, rows below M only.  *emitted = 1 when the
+ * slab was written; 0 when the form planned for the call cannot write it (weight-stationary form, fp32 output, K that is no
+ * multiple of 64): the slab is then untouched and the caller goes on without statistics.  rowstat_out = NULL: the plain call.
+ * Consumer (tramba_linear_ln_rowstat_cl): rowstat_in, such a slab over ITS input rows with p = K / 64 partials per row; the
+ * block folds them in ascending order into mean = S1 / K, rstd = rsqrt(max(S2 / K - mean^2, 0) + eps) instead of deriving
+ * them from its staged tiles in every column tile, and may then run the form the plain GEMM of the shape runs.  The weight-
+ * stationary form keeps deriving its own.  rowstat_in = NULL: tramba_linear_ln_cl, bit for bit. */
+int tramba_linear_rowstat_cl(const void *x, const void *w, const float *bias, const void *residual, void *y, int64_t m,
+                             int n, int k, int act, int dtype, int out_dtype, float *rowstat_out, int *emitted, void *stream);
+int tramba_linear2_rowstat_cl(const void *x1, const void *x2, int k1, const void *w, const float *bias, const void *residual,
+                              void *y, int64_t m, int n, int k, int act, int dtype, int out_dtype, float *rowstat_out,
+                              int *emitted, void *stream);
+int tramba_linear_ln_rowstat_cl(const void *x, const void *w_folded, const float *colsum, const float *bias,
+                                const void *residual, void *y, int64_t m, int n, int k, float eps, int act, int dtype,
+                                int out_dtype, const float *rowstat_in, int p, void *stream);
 
 /* y_pre = x @ w^T + bias and y_act = act(y_pre) from ONE launch (act = GELU or SiLU): the forward of `act(Linear(x))` on the
  * training path, whose backward needs the pre-activation (Models/modules.py:134-153 under autograd).  16-bit dtypes,

@@ -173,6 +173,18 @@ __device__ __forceinline__ void acc_to_lds(ACC &acc, float *ep)   // ACC = acc16
             }
 }
 
+// v + the values of the other 7 lanes of an aligned group of 8, in a fixed order: quad_perm [1,0,3,2], quad_perm [2,3,0,1], then
+// row_half_mirror (lane i <-> 7 - i: the other quad, whose four lanes all hold its sum by then).  DPP moves at VALU rate --
+// three ds_bpermute round trips per value (__shfl_xor) were most of what the row partials cost the epilogue.  Every lane of
+// the wave must be active.
+__device__ __forceinline__ float sum8_dpp(float v)
+{
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
+    return v;
+}
+
 // Epilogue through LDS, block-wide (shared by the tile kernels): see the comment inside.
 template <typename T, typename TO, int BM, int BN, int NT = 256, typename ACC>
 __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
@@ -180,8 +192,15 @@ __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
                                               TO *__restrict__ y, long M, int N, int act, long m0, int n0,
                                               const float *__restrict__ colsum = nullptr,
                                               const float2 *__restrict__ rowstat = nullptr,
-                                              TO *__restrict__ y_pre = nullptr)
+                                              TO *__restrict__ y_pre = nullptr,
+                                              float2 *__restrict__ stat_out = nullptr)
 {
+    // stat_out (64-column tiles, 16-bit outputs): the tile also leaves, per row below M, (sum, sum of squares) of its valid
+    // columns of y AS ROUNDED to the output dtype -- slab (M, ceil(N / 64)) of float2, entry [row][n0 / 64].  The LayerNorm-
+    // folded GEMM that reads y next takes its row statistics from these partials instead of re-deriving them in every one
+    // of its column tiles (LnIn::stat).  Fixed order: a lane's 8 columns left to right, then the 8 lanes of the row (sum8_dpp);
+    // no atomics.
+    constexpr bool STAT_OK = BN == 64 && sizeof(TO) == 2;
     // y_pre (training, linear_dma_kernel<.., DUAL>): the value BEFORE the activation (acc + bias) also leaves, to a second
     // tensor -- the pre-activation the backward of a GELU needs, without a separate activation launch re-reading it.
     // colsum / rowstat: LayerNorm of the INPUT rows folded into the GEMM (linear_dma_kernel / linear_pc_kernel<.., LNIN>): the accumulator
@@ -204,51 +223,75 @@ __device__ __forceinline__ void tile_epilogue(ACC &acc, unsigned char *lds,
     for (int it = 0; it < (BM + RPI - 1) / RPI; ++it) {
         const int row = it * RPI + rl;
         const long grow = m0 + row;
-        if (grow >= M || gcol >= N) continue;
-        float o[CPL];
-        {
-            const float4 v0 = *reinterpret_cast<const float4 *>(ep + row * LDE + cl);
-            const float4 v1 = *reinterpret_cast<const float4 *>(ep + row * LDE + cl + 4);
-            o[0] = v0.x; o[1] = v0.y; o[2] = v0.z; o[3] = v0.w; o[4] = v1.x; o[5] = v1.y; o[6] = v1.z; o[7] = v1.w;
-        }
-        if (gcol + CPL <= N && (N & 7) == 0) {
-            if (colsum) {
-                const float2 st = rowstat[row];
-                float cs[CPL];
-                load_pack<float, CPL>(colsum + gcol, cs);
-#pragma unroll
-                for (int q = 0; q < CPL; ++q) o[q] = st.y * fmaf(-st.x, cs[q], o[q]);
+        float s1 = 0.f, s2 = 0.f;
+        if (grow < M && gcol < N) {
+            float o[CPL];
+            {
+                const float4 v0 = *reinterpret_cast<const float4 *>(ep + row * LDE + cl);
+                const float4 v1 = *reinterpret_cast<const float4 *>(ep + row * LDE + cl + 4);
+                o[0] = v0.x; o[1] = v0.y; o[2] = v0.z; o[3] = v0.w; o[4] = v1.x; o[5] = v1.y; o[6] = v1.z; o[7] = v1.w;
             }
-            if (bias) {
-                float bv[CPL];
-                load_pack<float, CPL>(bias + gcol, bv);
+            if (gcol + CPL <= N && (N & 7) == 0) {
+                if (colsum) {
+                    const float2 st = rowstat[row];
+                    float cs[CPL];
+                    load_pack<float, CPL>(colsum + gcol, cs);
 #pragma unroll
-                for (int q = 0; q < CPL; ++q) o[q] += bv[q];
-            }
-            if (y_pre) store_pack<TO, CPL>(y_pre + grow * N + gcol, o);
-#pragma unroll
-            for (int q = 0; q < CPL; ++q) o[q] = apply_act(o[q], act);
-            if (res) {
-                float rv[CPL];
-                load_pack<T, CPL>(res + grow * N + gcol, rv);
-#pragma unroll
-                for (int q = 0; q < CPL; ++q) o[q] = combine_residual(o[q], rv[q], act);
-            }
-            store_pack<TO, CPL>(y + grow * N + gcol, o);
-        } else {
-#pragma unroll
-            for (int q = 0; q < CPL; ++q) {
-                if (gcol + q < N) {
-                    if (colsum) o[q] = rowstat[row].y * fmaf(-rowstat[row].x, colsum[gcol + q], o[q]);
-                    const float pre = o[q] + (bias ? bias[gcol + q] : 0.f);
-                    if (y_pre) y_pre[grow * N + gcol + q] = Cvt<TO>::from_f(pre);
-                    float t = apply_act(pre, act);
-                    if (res) {
-                        const float rv = Cvt<T>::to_f(res[grow * N + gcol + q]);
-                        t = combine_residual(t, rv, act);
-                    }
-                    y[grow * N + gcol + q] = Cvt<TO>::from_f(t);
+                    for (int q = 0; q < CPL; ++q) o[q] = st.y * fmaf(-st.x, cs[q], o[q]);
                 }
+                if (bias) {
+                    float bv[CPL];
+                    load_pack<float, CPL>(bias + gcol, bv);
+#pragma unroll
+                    for (int q = 0; q < CPL; ++q) o[q] += bv[q];
+                }
+                if (y_pre) store_pack<TO, CPL>(y_pre + grow * N + gcol, o);
+#pragma unroll
+                for (int q = 0; q < CPL; ++q) o[q] = apply_act(o[q], act);
+                if (res) {
+                    float rv[CPL];
+                    load_pack<T, CPL>(res + grow * N + gcol, rv);
+#pragma unroll
+                    for (int q = 0; q < CPL; ++q) o[q] = combine_residual(o[q], rv[q], act);
+                }
+                store_pack<TO, CPL>(y + grow * N + gcol, o);
+                if constexpr (STAT_OK) {
+                    if (stat_out) {
+#pragma unroll
+                        for (int q = 0; q < CPL; ++q) {
+                            const float r = Cvt<TO>::to_f(Cvt<TO>::from_f(o[q]));
+                            s1 += r;
+                            s2 = fmaf(r, r, s2);
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int q = 0; q < CPL; ++q) {
+                    if (gcol + q < N) {
+                        if (colsum) o[q] = rowstat[row].y * fmaf(-rowstat[row].x, colsum[gcol + q], o[q]);
+                        const float pre = o[q] + (bias ? bias[gcol + q] : 0.f);
+                        if (y_pre) y_pre[grow * N + gcol + q] = Cvt<TO>::from_f(pre);
+                        float t = apply_act(pre, act);
+                        if (res) {
+                            const float rv = Cvt<T>::to_f(res[grow * N + gcol + q]);
+                            t = combine_residual(t, rv, act);
+                        }
+                        y[grow * N + gcol + q] = Cvt<TO>::from_f(t);
+                        if constexpr (STAT_OK) {
+                            const float r = Cvt<TO>::to_f(Cvt<TO>::from_f(t));
+                            s1 += r;
+                            s2 = fmaf(r, r, s2);
+                        }
+                    }
+                }
+            }
+        }
+        if constexpr (STAT_OK) {
+            if (stat_out) {   // (kernel-uniform: every lane of the wave takes part; LPRW = 8 lanes hold a row)
+                s1 = sum8_dpp(s1);
+                s2 = sum8_dpp(s2);
+                if (cl == 0 && grow < M) stat_out[grow * ((N + BN - 1) / BN) + n0 / BN] = make_float2(s1, s2);
             }
         }
     }
@@ -434,10 +477,52 @@ __global__ __launch_bounds__(256) void linear_tiled_kernel(const T *__restrict__
 // vmamba.py:384-396): y = act(LN(x) W^T + b) = act(rstd * (x W'^T - mean * colsum) + t), W' = W * gamma (folded once per
 // weight version), colsum_n = sum_k W'_nk, t = W beta + b.  The block derives mean / rstd of its own 64 rows from the A tiles it stages anyway (read back
 // from the staged tile, or summed from the MFMA fragments); the normalised map is never written or re-read, and the LayerNorm launch disappears.
+//
+// Row statistics from the producer (STATIN kernels): the rows of x were written one launch earlier by a GEMM whose epilogue
+// left, per row and 64-column tile, (sum, sum of squares) of the rounded values (tile_epilogue, stat_out) -- exactly the 64-term
+// partial sums of this GEMM's K steps.  With that slab in `stat` the block folds its rows' K / 64 partials once, in its
+// prologue, and the K loop is the plain GEMM's: no statistics reads, no dot products, and not once per column tile.
+// In a kernel WITHOUT the LayerNorm (LNIN = false) the same field is the slab its own epilogue writes (or null).
 struct LnIn {
     const float *colsum;
     float eps;
+    float2 *stat = nullptr;
 };
+
+// STATIN prologue: thread t (of the 256 that call it) loads partials 8 (t & 3) .. + 7 of row t >> 2 -- issued BEFORE the
+// block's first LDS-DMA pieces, so that every counted vmcnt wait of the K loop still covers only DMA pieces behind them.
+struct StatIn {
+    float2 v[8];
+};
+__device__ __forceinline__ StatIn statin_load(const float2 *__restrict__ stat, long m0, long M, int nk, int t)
+{
+    StatIn s;
+    const long row = m0 + (t >> 2);
+    const int p0 = (t & 3) * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        s.v[j] = make_float2(0.f, 0.f);
+        if (row < M && p0 + j < nk) s.v[j] = stat[row * nk + p0 + j];
+    }
+    return s;
+}
+// ... and folds them in ascending order (8 per lane, then the 4 lanes of the row pairwise) into (mean, rstd) of the row
+__device__ __forceinline__ void statin_fold(const StatIn &s, float2 *rowstat, int K, float eps, int t)
+{
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        s1 += s.v[j].x;
+        s2 += s.v[j].y;
+    }
+    s1 += __shfl_xor(s1, 1, 64);
+    s2 += __shfl_xor(s2, 1, 64);
+    s1 += __shfl_xor(s1, 2, 64);
+    s2 += __shfl_xor(s2, 2, 64);
+    const float mean = s1 / (float)K;
+    const float var = fmaxf(s2 / (float)K - mean * mean, 0.f);
+    if ((t & 3) == 0) rowstat[t >> 2] = make_float2(mean, rsqrtf(var + eps));
+}
 
 struct LnHead {
     const float *ln_w, *ln_b, *head_w;
@@ -555,7 +640,7 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
                                                          const float *__restrict__ bias,
                                                          const T *__restrict__ res, TO *__restrict__ y, long M,
                                                          int N, int K, int act, const T *__restrict__ x2, int K1,
-                                                         LnHead hd = LnHead{})
+                                                         LnHead hd = LnHead{}, float2 *__restrict__ stat_out = nullptr)
 {
     // x2 != nullptr: A = [x (M, K1) | x2 (M, K - K1)], both halves whole K steps (no concatenation in memory)
     using WL = WaveLayout<BM, BN>;
@@ -694,7 +779,7 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
         static_assert(BN == 128, "one tile = whole 128-channel groups");
         tile_epilogue_ln_head<T, BM>(acc, lds, hd, M, m0, n0);
     } else {
-        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0);
+        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, nullptr, stat_out);
     }
 }
 
@@ -719,7 +804,7 @@ __global__ __launch_bounds__(256) void linear_lean_kernel(const T *__restrict__ 
 // Same epilogue (tile_epilogue) as the other forms.
 #define TRAMBA_DSR128_(OUT, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(OUT) : "v"(ADDR) : "memory")
 
-template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false>
+template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false, bool STATIN = false>
 __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x, const T *__restrict__ w,
                                                         const float *__restrict__ bias, const T *__restrict__ res,
                                                         TO *__restrict__ y, long M, int N, int K, int act,
@@ -731,6 +816,7 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
     constexpr int EPI_BYTES = BM * (BN + 4) * 4;
     constexpr int LDS_BYTES = NSTG * TILE_BYTES > EPI_BYTES ? NSTG * TILE_BYTES : EPI_BYTES;
     static_assert(NSTG == 2 || NSTG == 3 || NSTG == 4, "stage index = kt % NSTG with the loop unrolled by NSTG (up to 8 stages are coded)");
+    static_assert(LNIN || !STATIN, "supplied row statistics belong to the LayerNorm-folded GEMM");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES + (LNIN ? BM * 8 : 0)];
     typedef __attribute__((address_space(3))) void lds_void;
 
@@ -794,9 +880,13 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
     const unsigned sad = lbase + (unsigned)((tid >> 3) * 128 + (tid & 7) * 16);
 
     constexpr int DEPTH = NSTG - 1;                  // tiles in flight ahead of the one being multiplied
+    StatIn spart;
+    if constexpr (STATIN) spart = statin_load(li.stat, m0, M, nk, tid);
 #pragma unroll
     for (int t = 0; t < DEPTH; ++t)
         if (t < nk) issue(t, t);
+    // (the table lies behind the staging ring; the K loop's barriers and the epilogue's own order it before its readers)
+    if constexpr (STATIN) statin_fold(spart, reinterpret_cast<float2 *>(lds + LDS_BYTES), K, li.eps, tid);
     // stages 4..7 lie past the 16-bit offset field of ds_read: a second set of addresses, 64 KB up
     unsigned aad_hi[4], bad_hi[4];
 #pragma unroll
@@ -832,7 +922,7 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
         const unsigned *aa = STG < 4 ? aad : aad_hi, *ba = STG < 4 ? bad : bad_hi;
         const unsigned sa = STG < 4 ? sad : sad_hi;
 #define TRAMBA_RD_STG_(S, S2)                                                                       \
-    if constexpr (LNIN) { TRAMBA_DSR128_(sv[0], sa, S); TRAMBA_DSR128_(sv[1], sa, S2); }             \
+    if constexpr (LNIN && !STATIN) { TRAMBA_DSR128_(sv[0], sa, S); TRAMBA_DSR128_(sv[1], sa, S2); }  \
     TRAMBA_DSR128_(a[0], aa[0], S); TRAMBA_DSR128_(b[0], ba[0], S); TRAMBA_DSR128_(a[1], aa[1], S);  \
     TRAMBA_DSR128_(b[1], ba[1], S); TRAMBA_DSR128_(a[2], aa[2], S); TRAMBA_DSR128_(b[2], ba[2], S);  \
     TRAMBA_DSR128_(a[3], aa[3], S); TRAMBA_DSR128_(b[3], ba[3], S)
@@ -841,7 +931,7 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
         else if constexpr ((STG & 3) == 2) { TRAMBA_RD_STG_(32768, 36864); }
         else { TRAMBA_RD_STG_(49152, 53248); }
 #undef TRAMBA_RD_STG_
-        if constexpr (LNIN) {   // (the two statistics reads were issued first: they are done once eight reads remain)
+        if constexpr (LNIN && !STATIN) {   // (the two statistics reads were issued first: they are done once eight reads remain)
             asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(sv[0]), "+v"(sv[1]) : : "memory");
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -890,22 +980,25 @@ __global__ __launch_bounds__(256) void linear_dma_kernel(const T *__restrict__ x
     __syncthreads();                                       // every wave has read the last tile: the epilogue reuses the LDS
     if constexpr (LNIN) {
         float2 *rowstat = reinterpret_cast<float2 *>(lds + LDS_BYTES);   // read by the epilogue behind its own barrier
+        if constexpr (!STATIN) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            float s1 = rs1[i], s2 = rs2[i];
+            for (int i = 0; i < 2; ++i) {
+                float s1 = rs1[i], s2 = rs2[i];
 #pragma unroll
-            for (int m = 1; m < 8; m <<= 1) {      // the 8 lanes that cover one row
-                s1 += __shfl_xor(s1, m, 64);
-                s2 += __shfl_xor(s2, m, 64);
+                for (int m = 1; m < 8; m <<= 1) {      // the 8 lanes that cover one row
+                    s1 += __shfl_xor(s1, m, 64);
+                    s2 += __shfl_xor(s2, m, 64);
+                }
+                const float mean = s1 / (float)K;
+                const float var = fmaxf(s2 / (float)K - mean * mean, 0.f);
+                if ((tid & 7) == 0) rowstat[(tid >> 3) + 32 * i] = make_float2(mean, rsqrtf(var + li.eps));
             }
-            const float mean = s1 / (float)K;
-            const float var = fmaxf(s2 / (float)K - mean * mean, 0.f);
-            if ((tid & 7) == 0) rowstat[(tid >> 3) + 32 * i] = make_float2(mean, rsqrtf(var + li.eps));
         }
         tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
                                      reinterpret_cast<const float2 *>(lds + LDS_BYTES));
     } else {
-        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
+        tile_epilogue<T, TO, BM, BN>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr,
+                                     DUAL ? nullptr : li.stat);
     }
 #endif
 }
@@ -945,7 +1038,7 @@ struct ASrc {
 #define TRAMBA_DSR128_(OUT, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:" #OFF : "=v"(OUT) : "v"(ADDR) : "memory")
 // (A_CONV on 3 stages asks for six waves per SIMD = three workgroups per CU by name: its loader code is a little longer, and left alone the
 //  register allocator ends two registers above the 80 that the other forms need, with unused holes below)
-template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false, int ASRC = A_PLAIN>
+template <typename T, typename TO, int NSTG, bool LNIN = false, bool DUAL = false, int ASRC = A_PLAIN, bool STATIN = false>
 __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void linear_pc_kernel(const T *__restrict__ x, const T *__restrict__ w,
                                                        const float *__restrict__ bias, const T *__restrict__ res,
                                                        TO *__restrict__ y, long M, int N, int K, int act,
@@ -958,6 +1051,7 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
     constexpr int EPI_BYTES = BM * (BN + 4) * 4;
     constexpr int LDS_BYTES = NSTG * TILE_BYTES > EPI_BYTES ? NSTG * TILE_BYTES : EPI_BYTES;
     static_assert(NSTG == 3 || NSTG == 4, "stage index = kt % NSTG with the loop unrolled by NSTG");
+    static_assert(LNIN || !STATIN, "supplied row statistics belong to the LayerNorm-folded GEMM");
     __shared__ __attribute__((aligned(1024))) unsigned char lds[LDS_BYTES + (LNIN ? BM * 8 : 0)];
     typedef __attribute__((address_space(3))) void lds_void;
 
@@ -1107,6 +1201,11 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
 #pragma unroll
         for (int t = 0; t < DEPTH; ++t)
             if (t < nk) issue(t, t);
+    } else if constexpr (STATIN) {
+        // supplied statistics: the multiplier waves fold them while the loaders' first pieces are in flight (they issue no
+        // LDS-DMA, so nothing here meets a counted wait)
+        const StatIn spart = statin_load(li.stat, m0, M, nk, lt);
+        statin_fold(spart, reinterpret_cast<float2 *>(lds + LDS_BYTES), K, li.eps, lt);
     }
     auto kstep = [&](int kt, auto stg_c) {
         constexpr int STG = decltype(stg_c)::value;
@@ -1130,7 +1229,7 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
         } else {
             frag8_t a[4], b[4];
             v4u_t sv[2];
-            if constexpr (LNIN) {
+            if constexpr (LNIN && !STATIN) {
                 if constexpr (STG == 0) { TRAMBA_DSR128_(sv[0], sad, 0); TRAMBA_DSR128_(sv[1], sad, 4096); }
                 else if constexpr (STG == 1) { TRAMBA_DSR128_(sv[0], sad, 16384); TRAMBA_DSR128_(sv[1], sad, 20480); }
                 else if constexpr (STG == 2) { TRAMBA_DSR128_(sv[0], sad, 32768); TRAMBA_DSR128_(sv[1], sad, 36864); }
@@ -1146,7 +1245,7 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
             else { TRAMBA_RD_STG_(49152); }
 #undef TRAMBA_RD_STG_
             // counted waits: slice kk needs the first 2 (kk + 1) reads; every destination is named so that no MFMA moves above
-            if constexpr (LNIN) {   // (the two statistics reads were issued first: they are done once eight reads remain)
+            if constexpr (LNIN && !STATIN) {   // (the two statistics reads were issued first: they are done once eight reads remain)
                 asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(sv[0]), "+v"(sv[1]) : : "memory");
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
@@ -1186,7 +1285,7 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
     __syncthreads();                                       // every wave has read the last tile: the epilogue reuses the LDS
     if constexpr (LNIN) {
         float2 *rowstat = reinterpret_cast<float2 *>(lds + LDS_BYTES);   // read by the epilogue behind its own barrier
-        if (!loader) {
+        if (!STATIN && !loader) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 float s1 = rs1[i], s2 = rs2[i];
@@ -1203,7 +1302,8 @@ __global__ __launch_bounds__(512, ASRC == A_CONV && NSTG == 3 ? 6 : 1) void line
         tile_epilogue<T, TO, BM, BN, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, li.colsum,
                                           reinterpret_cast<const float2 *>(lds + LDS_BYTES));
     } else {
-        tile_epilogue<T, TO, BM, BN, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr);
+        tile_epilogue<T, TO, BM, BN, 512>(acc, lds, bias, res, y, M, N, act, m0, n0, nullptr, nullptr, DUAL ? y_pre : nullptr,
+                                          DUAL ? nullptr : li.stat);
     }
 #endif
 }
@@ -1553,6 +1653,11 @@ static int pc_rule(long tiles64, int k, int kind)
     return 3;
 }
 
+// LayerNorm folded in WITH the row statistics supplied by the producer of the rows (LnIn::stat): the statistics reads that kept
+// the many-tile launches off the producer / consumer kernel are gone, so the launch follows the plain rule (scripts/
+// bench_ln_stats.py on MI355X, profiles/lnstats_forms.txt).
+static int ln_stat_rule(long tiles64, int k) { return pc_rule(tiles64, k, 0); }
+
 // Weight-stationary form (linear_ws_kernel, r04): column blocks per wave, or 0 = it cannot run.  16-bit in and out, K = 128 /
 // 256, N a whole number of 128 NCW-column panels.
 static int ws_ncw(long m, int n, int k)
@@ -1628,7 +1733,9 @@ struct GemmPlan {
 // rule), 13 / 14 = DMA2 / DMA3, 16 / 17 = PC3 / PC4, 18 = the rule without the PC and WS forms (the r03 kernels; the only value
 // the two-source and convolution entries look at: their register-staged kernels), 19 = WS wherever it can run, else the rule.
 // 0 = the rule.
-static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool same_dtype, bool a_dma = true)
+// ln_stat: a LayerNorm-folded launch whose row statistics are supplied (LnIn::stat) -- its K loop is the plain GEMM's, see
+// ln_stat_rule.
+static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool same_dtype, bool a_dma = true, bool ln_stat = false)
 {
     int tune = tramba_tune_get(TRAMBA_TUNE_GEMM_TILE);
     // Two-source A operand and implicit-GEMM convolution (a_dma: the operand fits the LDS-DMA loaders -- both K parts whole
@@ -1663,7 +1770,7 @@ static GemmPlan gemm_plan(GemmKind kind, long m, int n, int k, int act, bool sam
     case 17: return {GemmForm::PC4, 0};
     }
     const long tiles64 = ((m + 63) / 64) * ((n + 63) / 64);
-    const int pc = tune == 18 ? 0 : pc_rule(tiles64, k, kind);
+    const int pc = tune == 18 ? 0 : (kind == GEMM_LN && ln_stat) ? ln_stat_rule(tiles64, k) : pc_rule(tiles64, k, kind);
     if (pc) return {pc == 4 ? GemmForm::PC4 : GemmForm::PC3, 0};
     // short K (<= 4 steps) on a grid of many tiles: the launch is prologue + epilogue, and what it needs is workgroups in flight
     if (k <= DMA_SHORT_K && tiles64 >= 1024) return {GemmForm::DMA2, 0};
@@ -1718,14 +1825,33 @@ static void launch_gemm(const GemmPlan &p, const GemmArgs &a, hipStream_t s)
                 break;
             }
         }
+        if constexpr (LNIN) {
+            if (a.li.stat) {   // row statistics supplied
+                if (four) hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, true, false, A_PLAIN, true>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+                else hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, true, false, A_PLAIN, true>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+                break;
+            }
+        }
         if (four) hipLaunchKernelGGL((linear_pc_kernel<T, TO, 4, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         else hipLaunchKernelGGL((linear_pc_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(512), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         break;
     }
     case GemmForm::DMA2:
+        if constexpr (LNIN) {
+            if (a.li.stat) {
+                hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2, true, false, true>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+                break;
+            }
+        }
         hipLaunchKernelGGL((linear_dma_kernel<T, TO, 2, LNIN, DUAL>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         break;
     case GemmForm::DMA3:
+        if constexpr (LNIN) {
+            if (a.li.stat) {
+                hipLaunchKernelGGL((linear_dma_kernel<T, TO, 3, true, false, true>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
+                break;
+            }
+        }
         hipLaunchKernelGGL((linear_dma_kernel<T, TO, 3, LNIN, DUAL>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.li, y_pre);
         break;
     case GemmForm::DMA4:   // (gemm_plan: plain entry only)
@@ -1734,7 +1860,7 @@ static void launch_gemm(const GemmPlan &p, const GemmArgs &a, hipStream_t s)
         break;
     case GemmForm::LEAN:
         hipLaunchKernelGGL((linear_lean_kernel<T, TO, 64, 64, 1>), g64, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act,
-                           (const T *)a.x2, a.k1);
+                           (const T *)a.x2, a.k1, LnHead{}, a.li.stat);
         break;
     case GemmForm::TILED128:
         hipLaunchKernelGGL((linear_tiled_kernel<T, TO, 128, 128, 2, CONV>), g128, dim3(256), 0, s, x, w, a.bias, res, y, m, n, k, act, a.cg);
@@ -1809,10 +1935,34 @@ __global__ __launch_bounds__(256) void linear32_kernel(const float *__restrict__
 
 using namespace tramba;
 
+// the forms whose epilogue (tile_epilogue on a 64-column tile) can leave the row partials of a 16-bit output
+// ... and not where the LayerNorm-folded GEMM over these rows (K = n, N >= 2 n) would take the weight-stationary form, which
+// derives its own statistics (the 96 x 96 stage from batch 2 on): the slab would cost its producer 0.6 us for nothing.
+static bool plan_emits_rowstat(const GemmPlan &p, int dtype, int out_dtype, long m, int n)
+{
+    if (out_dtype != dtype || dtype == TRAMBA_F32) return false;
+    if (tramba_tune_get(TRAMBA_TUNE_GEMM_TILE) == 0 && ws_ncw(m, 2 * n, n) && ws_rule(m, 2 * n, n, GEMM_LN)) return false;
+    switch (p.form) {
+    case GemmForm::PC3: case GemmForm::PC4: case GemmForm::DMA2: case GemmForm::DMA3: case GemmForm::DMA4: case GemmForm::LEAN:
+        return true;
+    default:
+        return false;
+    }
+}
+
 extern "C" int tramba_linear_cl(const void *x, const void *w, const float *bias, const void *residual,
                                 void *y, int64_t m, int n, int k, int act, int dtype, int out_dtype,
                                 void *stream)
 {
+    return tramba_linear_rowstat_cl(x, w, bias, residual, y, m, n, k, act, dtype, out_dtype, nullptr, nullptr, stream);
+}
+
+extern "C" int tramba_linear_rowstat_cl(const void *x, const void *w, const float *bias, const void *residual,
+                                        void *y, int64_t m, int n, int k, int act, int dtype, int out_dtype,
+                                        float *rowstat_out, int *emitted, void *stream)
+{
+    if (emitted) *emitted = 0;
+    TRAMBA_CHECK(!rowstat_out || (emitted && ((size_t)rowstat_out & 7) == 0), "linear_cl: rowstat_out needs `emitted` and 8-byte alignment");
     TRAMBA_CHECK(x && w && y, "linear_cl: null tensor");
     TRAMBA_CHECK(m > 0 && n > 0 && k > 0, "linear_cl: empty shape");
     TRAMBA_CHECK(out_dtype == dtype || out_dtype == TRAMBA_F32, "linear_cl: out dtype must be dtype or f32");
@@ -1828,8 +1978,13 @@ extern "C" int tramba_linear_cl(const void *x, const void *w, const float *bias,
     const bool tiled = vec && dtype != TRAMBA_F32 && aligned16(y) && (residual == nullptr || aligned16(residual)) &&
                        (m + 63) / 64 <= 65535;
     if (tiled) {
-        launch_gemm16(gemm_plan(GEMM_PLAIN, m, n, k, act, out_dtype == dtype), GemmArgs{x, w, bias, residual, y, m, n, k, act},
-                      dtype, out_dtype, s);
+        const GemmPlan p = gemm_plan(GEMM_PLAIN, m, n, k, act, out_dtype == dtype);
+        GemmArgs a{x, w, bias, residual, y, m, n, k, act};
+        if (rowstat_out && plan_emits_rowstat(p, dtype, out_dtype, m, n)) {
+            a.li.stat = reinterpret_cast<float2 *>(rowstat_out);
+            *emitted = 1;
+        }
+        launch_gemm16(p, a, dtype, out_dtype, s);
         TRAMBA_LAUNCH_CHECK();
         return TRAMBA_OK;
     }
@@ -1864,6 +2019,16 @@ extern "C" int tramba_linear_ln_cl(const void *x, const void *w_folded, const fl
                                    const void *residual, void *y, int64_t m, int n, int k, float eps, int act, int dtype,
                                    int out_dtype, void *stream)
 {
+    return tramba_linear_ln_rowstat_cl(x, w_folded, colsum, bias, residual, y, m, n, k, eps, act, dtype, out_dtype, nullptr, 0,
+                                       stream);
+}
+
+extern "C" int tramba_linear_ln_rowstat_cl(const void *x, const void *w_folded, const float *colsum, const float *bias,
+                                           const void *residual, void *y, int64_t m, int n, int k, float eps, int act,
+                                           int dtype, int out_dtype, const float *rowstat_in, int p, void *stream)
+{
+    TRAMBA_CHECK(!rowstat_in || (p > 0 && p == k / 64 && ((size_t)rowstat_in & 7) == 0),
+                 "linear_ln_cl: rowstat_in holds %d partials per row, K = %d needs K / 64 (8-byte aligned)", p, k);
     TRAMBA_CHECK(x && w_folded && colsum && y, "linear_ln_cl: null tensor");
     TRAMBA_CHECK(m > 0 && n > 0 && k > 0, "linear_ln_cl: empty shape");
     TRAMBA_CHECK(dtype == TRAMBA_BF16 || dtype == TRAMBA_F16, "linear_ln_cl: 16-bit activations only");
@@ -1875,8 +2040,8 @@ extern "C" int tramba_linear_ln_cl(const void *x, const void *w_folded, const fl
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(TRAMBA_PROF_GEMM, s, 2.0 * (double)m * n * k);
     GemmArgs a{x, w_folded, bias, residual, y, m, n, k, act};
-    a.li = LnIn{colsum, eps};
-    launch_gemm16<true>(gemm_plan(GEMM_LN, m, n, k, act, out_dtype == dtype), a, dtype, out_dtype, s);
+    a.li = LnIn{colsum, eps, const_cast<float2 *>(reinterpret_cast<const float2 *>(rowstat_in))};
+    launch_gemm16<true>(gemm_plan(GEMM_LN, m, n, k, act, out_dtype == dtype, true, rowstat_in != nullptr), a, dtype, out_dtype, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -1885,6 +2050,15 @@ extern "C" int tramba_linear2_cl(const void *x1, const void *x2, int k1, const v
                                  const void *residual, void *y, int64_t m, int n, int k, int act, int dtype,
                                  int out_dtype, void *stream)
 {
+    return tramba_linear2_rowstat_cl(x1, x2, k1, w, bias, residual, y, m, n, k, act, dtype, out_dtype, nullptr, nullptr, stream);
+}
+
+extern "C" int tramba_linear2_rowstat_cl(const void *x1, const void *x2, int k1, const void *w, const float *bias,
+                                         const void *residual, void *y, int64_t m, int n, int k, int act, int dtype,
+                                         int out_dtype, float *rowstat_out, int *emitted, void *stream)
+{
+    if (emitted) *emitted = 0;
+    TRAMBA_CHECK(!rowstat_out || (emitted && ((size_t)rowstat_out & 7) == 0), "linear2_cl: rowstat_out needs `emitted` and 8-byte alignment");
     TRAMBA_CHECK(x1 && x2 && w && y, "linear2_cl: null tensor");
     TRAMBA_CHECK(m > 0 && n > 0 && k > 0 && k1 > 0 && k1 < k, "linear2_cl: empty shape");
     TRAMBA_CHECK(dtype == TRAMBA_BF16 || dtype == TRAMBA_F16, "linear2_cl: 16-bit dtypes only");
@@ -1898,7 +2072,12 @@ extern "C" int tramba_linear2_cl(const void *x1, const void *x2, int k1, const v
     GemmArgs a{x1, w, bias, residual, y, m, n, k, act};
     a.x2 = x2;
     a.k1 = k1;
-    launch_gemm16(gemm_plan(GEMM_TWO_SRC, m, n, k, act, out_dtype == dtype), a, dtype, out_dtype, s);
+    const GemmPlan p = gemm_plan(GEMM_TWO_SRC, m, n, k, act, out_dtype == dtype);
+    if (rowstat_out && plan_emits_rowstat(p, dtype, out_dtype, m, n)) {
+        a.li.stat = reinterpret_cast<float2 *>(rowstat_out);
+        *emitted = 1;
+    }
+    launch_gemm16(p, a, dtype, out_dtype, s);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -115,6 +115,11 @@ SIGNATURES = {
     "tramba_linear_dual_cl": (c_int, [c_vp] * 5 + [c_i64, c_int, c_int, c_int, c_int, c_vp]),
     "tramba_linear_ln_cl": (c_int, [c_vp] * 6 + [c_i64, c_int, c_int, c_f, c_int, c_int, c_int, c_vp]),
     "tramba_linear2_cl": (c_int, [c_vp, c_vp, c_int] + [c_vp] * 4 + [c_i64, c_int, c_int, c_int, c_int, c_int, c_vp]),
+    "tramba_linear_rowstat_cl": (c_int, [c_vp] * 5 + [c_i64, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                      ctypes.POINTER(c_int), c_vp]),
+    "tramba_linear2_rowstat_cl": (c_int, [c_vp, c_vp, c_int] + [c_vp] * 4 + [c_i64, c_int, c_int, c_int, c_int, c_int, c_vp,
+                                                                             ctypes.POINTER(c_int), c_vp]),
+    "tramba_linear_ln_rowstat_cl": (c_int, [c_vp] * 6 + [c_i64, c_int, c_int, c_f, c_int, c_int, c_int, c_vp, c_int, c_vp]),
     "tramba_wgrad_workspace": (ctypes.c_size_t, [c_i64, c_int, c_int, c_int, c_int]),
     "tramba_wgrad_cl": (c_int, [c_vp] * 4 + [ctypes.c_size_t, c_i64, c_int, c_int, c_int, c_int, c_i64, c_i64, c_int, c_i64,
                                              c_i64, c_int, c_int, c_int, c_vp]),
@@ -1508,17 +1513,53 @@ def _check_epilogue(what, bias, residual, dtype, m, n):
                              f"{residual.numel()}")
 
 
-def linear_cl(x, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None):
-    """x: (..., K); w: (N, K) same dtype; -> (..., N)."""
+def _rowstat_extra(rowstat, dtype, out_dtype, m, n):
+    """elements of the 16-bit output dtype that linear_cl / linear2_cl allocate behind y for the row-partial slab (0: no slab):
+    y and its slab come from ONE allocation -- y's m * n elements, padding to 16 bytes, then (M, ceil(N / 64), 2) f32"""
+    if not rowstat or out_dtype != dtype or dtype == torch.float32:
+        return 0
+    return (-(m * n)) % 8 + m * ((n + 63) // 64) * 4
+
+
+def _rowstat_split(buf, shape, m, n):
+    """(y, slab) views of such an allocation"""
+    off = (m * n + 7) // 8 * 8
+    return buf[:m * n].view(shape), buf[off:].view(torch.float32).view(m, (n + 63) // 64, 2)
+
+
+def rowstat_for(x, k):
+    """the slab a producer GEMM left on x (attribute set by linear_cl / linear2_cl(rowstat=True)), if it still describes x
+    as the input of a GEMM over K = k: same tensor version, one 64-term partial per K step.  Else None."""
+    tag = getattr(x, "_tramba_rowstat", None)
+    if tag is None:
+        return None
+    slab, version = tag
+    if version != x._version or k % 64 or slab.shape != (x.numel() // k, k // 64, 2) or slab.device != x.device:
+        return None
+    return slab
+
+
+def linear_cl(x, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None, rowstat=False):
+    """x: (..., K); w: (N, K) same dtype; -> (..., N).  rowstat: the launch also leaves the row partials of y for the
+    LayerNorm-folded GEMM that reads y next (tramba_linear_rowstat_cl) -- attached to y where the planned form can write
+    them (see rowstat_for), silently absent where it cannot."""
     _dev(x, w, bias, residual)
     k = x.shape[-1]
     n = w.shape[0]
     m = x.numel() // k
     out_dtype = x.dtype if out_dtype is None else out_dtype
-    y = torch.empty(x.shape[:-1] + (n,), dtype=out_dtype, device=x.device)
+    extra = _rowstat_extra(rowstat, x.dtype, out_dtype, m, n)
+    y = torch.empty((m * n + extra,) if extra else x.shape[:-1] + (n,), dtype=out_dtype, device=x.device)
     if w.dtype != x.dtype or w.shape[1] != k:
         raise TrambaHipError("linear_cl: weight dtype/shape mismatch")
     _check_epilogue("linear_cl", bias, residual, x.dtype, m, n)
+    if extra:
+        (y, slab), emitted = _rowstat_split(y, x.shape[:-1] + (n,), m, n), c_int(0)
+        _check(lib().tramba_linear_rowstat_cl(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), m, n, k, act, dt(x),
+                                              dt(y), _ptr(slab), ctypes.byref(emitted), _stream()), "linear_cl")
+        if emitted.value:
+            y._tramba_rowstat = (slab, y._version)
+        return y
     _check(lib().tramba_linear_cl(_ptr(x), _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), m, n, k, act, dt(x),
                                   dt(y), _stream()), "linear_cl")
     return y
@@ -1653,9 +1694,10 @@ def linear_dual_cl(x, w, bias, act):
     return y_pre, y_act
 
 
-def linear_ln_cl(x, w_folded, colsum, bias, eps, residual=None, act=ACT_NONE, out_dtype=None):
+def linear_ln_cl(x, w_folded, colsum, bias, eps, residual=None, act=ACT_NONE, out_dtype=None, rowstat=None):
     """act(LayerNorm(x) @ W^T + b) in one launch: w_folded = W * gamma (N, K) in x's dtype, colsum (N) f32 its row sums,
-    bias (N) f32 = W @ beta + b (see include/tramba_hip.h)."""
+    bias (N) f32 = W @ beta + b (see include/tramba_hip.h).  rowstat: the (M, K / 64, 2) f32 slab of x's row partials its
+    producer left (rowstat_for), or None = the GEMM derives the statistics itself."""
     _dev(x, w_folded, colsum, bias, residual)
     k = x.shape[-1]
     n = w_folded.shape[0]
@@ -1665,13 +1707,23 @@ def linear_ln_cl(x, w_folded, colsum, bias, eps, residual=None, act=ACT_NONE, ou
     _check_epilogue("linear_ln_cl", bias, residual, x.dtype, m, n)
     out_dtype = x.dtype if out_dtype is None else out_dtype
     y = torch.empty(x.shape[:-1] + (n,), dtype=out_dtype, device=x.device)
+    if rowstat is not None:
+        if (rowstat.dtype != torch.float32 or rowstat.shape != (m, k // 64, 2) or k % 64 or not rowstat.is_contiguous()
+                or rowstat.device != x.device):
+            raise TrambaHipError(f"linear_ln_cl: rowstat must be a contiguous f32 ({m}, {k // 64}, 2) slab, got "
+                                 f"{rowstat.dtype} {tuple(rowstat.shape)}")
+        _check(lib().tramba_linear_ln_rowstat_cl(_ptr(x), _ptr(w_folded), _ptr(colsum), _ptr(bias), _ptr(residual), _ptr(y),
+                                                 m, n, k, float(eps), act, dt(x), dt(y), _ptr(rowstat), k // 64, _stream()),
+               "linear_ln_cl")
+        return y
     _check(lib().tramba_linear_ln_cl(_ptr(x), _ptr(w_folded), _ptr(colsum), _ptr(bias), _ptr(residual), _ptr(y), m, n, k,
                                      float(eps), act, dt(x), dt(y), _stream()), "linear_ln_cl")
     return y
 
 
-def linear2_cl(x1, x2, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None):
-    """Linear2d on torch.cat((x1, x2), dim=-1) without the concatenation: x1 (..., K1), x2 (..., K2), w (N, K1+K2)."""
+def linear2_cl(x1, x2, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None, rowstat=False):
+    """Linear2d on torch.cat((x1, x2), dim=-1) without the concatenation: x1 (..., K1), x2 (..., K2), w (N, K1+K2).
+    rowstat: as in linear_cl."""
     _dev(x1, x2, w, bias, residual)
     k1, k2 = x1.shape[-1], x2.shape[-1]
     n = w.shape[0]
@@ -1680,7 +1732,16 @@ def linear2_cl(x1, x2, w, bias=None, residual=None, act=ACT_NONE, out_dtype=None
         raise TrambaHipError("linear2_cl: operand shapes / dtypes do not match")
     _check_epilogue("linear2_cl", bias, residual, x1.dtype, m, n)
     out_dtype = x1.dtype if out_dtype is None else out_dtype
-    y = torch.empty(x1.shape[:-1] + (n,), dtype=out_dtype, device=x1.device)
+    extra = _rowstat_extra(rowstat, x1.dtype, out_dtype, m, n)
+    y = torch.empty((m * n + extra,) if extra else x1.shape[:-1] + (n,), dtype=out_dtype, device=x1.device)
+    if extra:
+        (y, slab), emitted = _rowstat_split(y, x1.shape[:-1] + (n,), m, n), c_int(0)
+        _check(lib().tramba_linear2_rowstat_cl(_ptr(x1), _ptr(x2), k1, _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), m, n,
+                                               k1 + k2, act, dt(x1), dt(y), _ptr(slab), ctypes.byref(emitted), _stream()),
+               "linear2_cl")
+        if emitted.value:
+            y._tramba_rowstat = (slab, y._version)
+        return y
     _check(lib().tramba_linear2_cl(_ptr(x1), _ptr(x2), k1, _ptr(w), _ptr(bias), _ptr(residual), _ptr(y), m, n, k1 + k2,
                                    act, dt(x1), dt(y), _stream()), "linear2_cl")
     return y

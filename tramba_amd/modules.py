@@ -38,7 +38,7 @@ from .ops import (CrossMerge, CrossMerge_Dilation, CrossMerge_Line, CrossMerge_W
 
 # LayerNorm2d -> Linear2d pairs as one launch in 16-bit inference (a scheduling choice of the same arithmetic: A/B timing
 # scripts flip it, scripts/ab_forward.py tramba_amd.modules.FOLD_LAYERNORM)
-FOLD_LAYERNORM = True
+FOLD_LAYERNORM, ROW_STATS = True, True   # (ROW_STATS: producer GEMMs hand row statistics to the folded LayerNorm, see _want_rs)
 
 
 def to_cl(x: torch.Tensor) -> torch.Tensor:
@@ -641,7 +641,7 @@ class Linear2d(nn.Linear):
         activation to its consumer, see _GeluLinearTrainCL); gelu_ready: that GELU, when the producer wrote it as well"""
         if _infer(x, self.weight):
             w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
-            return hip.linear_cl(F.gelu(x) if gelu_in else x, w.detach(), _f32(self.bias), residual, act, out_dtype)
+            return hip.linear_cl(F.gelu(x) if gelu_in else x, w.detach(), _f32(self.bias), residual, act, out_dtype, _want_rs(residual, act))
         if gelu_in:
             y = _act_torch(_GeluLinearTrainCL.apply(x, self.weight, self.bias, gelu_ready), act)
         else:
@@ -666,7 +666,7 @@ class Linear2d(nn.Linear):
                 and self.weight.shape[0] % 8 == 0):
             wf, cs, tb = _cache(self).get(("lnfold", x.dtype, id(norm)), (self.weight, self.bias, norm.weight, norm.bias),
                                           lambda: _fold_layernorm(self, norm, x.dtype))
-            return hip.linear_ln_cl(x, wf, cs, tb, norm.eps, residual, act, out_dtype)
+            return hip.linear_ln_cl(x, wf, cs, tb, norm.eps, residual, act, out_dtype, hip.rowstat_for(x, k) if ROW_STATS else None)
         return self._forward_cl(norm._forward_cl(x), act=act, residual=residual, out_dtype=out_dtype)
 
     def _forward_cat_cl(self, x1, x2, act=hip.ACT_NONE, residual=None, out_dtype=None):
@@ -1270,6 +1270,16 @@ def _add_ln(v, norm, act=hip.ACT_NONE):
     if isinstance(v, _Deferred):
         return _AddLayerNormCL.apply(v.x, v.y, v.mask, norm.weight, norm.bias, norm.eps, act, True)
     return _AddLayerNormCL.apply(v, None, None, norm.weight, norm.bias, norm.eps, act, True)
+
+
+def _want_rs(residual, act):
+    """ROW_STATS (16-bit inference, Linear2d._forward_cl): a GEMM output with a residual is a block's output (fc2 / out_proj +
+    residual), and the GEMM that reads it next is LayerNorm-folded (norm -> in_proj, norm2 -> fc1).  The producer's epilogue
+    leaves per-row partial sums of what it writes (tramba_linear_rowstat_cl), hip.linear_cl hangs them on the tensor object,
+    and Linear2d._forward_norm_cl hands them to tramba_linear_ln_rowstat_cl when they still describe its input
+    (hip.rowstat_for: same tensor version, one partial per 64-deep K step) -- that launch then derives no statistics in its
+    K loop.  A consumer that finds none derives its own, as before.  Same-process A/B: flip modules.ROW_STATS."""
+    return ROW_STATS and FOLD_LAYERNORM and residual is not None and act == hip.ACT_NONE
 
 
 # Packed depth-wise stencils of the TRAINING path.  The weights change once per step, at the optimizer: instead of one small
