@@ -756,6 +756,34 @@ int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count,
 int tramba_adam_step_ctl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                          float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
                          double eps, double weight_decay, const float *gscale, const int *skip, void *stream);
+/* ---- dynamic loss scaling (fp16 training): the scale lives on the device and moves after every optimizer step ----
+ * A second record, owned by the caller like tramba_step_ctl.  `scale` is what the gradient of the loss is multiplied by
+ * (the caller hands &scale to the loss gradient kernels as their `gscale`); it is always a power of two, so `inv_scale`
+ * is exact and un-scaling changes no bit of a gradient that neither over- nor underflowed.  The caller fills scale and
+ * inv_scale before the first step (zeros are not a valid state). */
+typedef struct tramba_loss_scale {
+    float scale;             /* 2^k: the loss gradient is multiplied by it */
+    float inv_scale;         /* 1 / scale, exact */
+    int32_t good_steps;      /* optimizer steps since the scale last changed that were not skipped */
+    int32_t reserved;
+    int64_t backoffs;        /* times the scale was cut since the record was filled */
+} tramba_loss_scale;
+/* tramba_grad_norm on gradients that carry ls->scale: the same two kernels, the same fp64 partial sums and per-element
+ * Inf / NaN flags; the finishing block reads ls->inv_scale on the device and writes
+ *   norm  = sqrt(sum of squares) * mean_scale * inv_scale                     (the norm of the UNSCALED mean gradient)
+ *   scale = mean_scale * inv_scale * min(1, max_norm / (norm + 1e-6))         (what tramba_adam_step_ctl multiplies in)
+ * ls == NULL is tramba_grad_norm bit for bit. */
+int tramba_grad_norm_scaled(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
+                            int skip_nonfinite, tramba_step_ctl *ctl, const tramba_loss_scale *ls, void *workspace,
+                            size_t workspace_bytes, void *stream);
+/* The scale's move after a step (a one-lane launch behind the optimizer's; reads ctl->skip on the device):
+ *   skipped:  scale = max(min_scale, scale * backoff), good_steps = 0, backoffs += 1;
+ *   else:     good_steps += 1; at growth_interval: scale = min(max_scale, scale * growth), good_steps = 0;
+ *   inv_scale = 1 / scale.
+ * growth > 1, backoff < 1, min_scale <= max_scale: powers of two that fp32 holds as normal numbers together with their
+ * inverses (2^-126 .. 2^126); growth_interval >= 1.  Anything else is refused (< 0, tramba_last_error()). */
+int tramba_loss_scale_update(tramba_loss_scale *ls, const tramba_step_ctl *ctl, double growth, double backoff,
+                             int growth_interval, double min_scale, double max_scale, void *stream);
 
 /* ------------------------------------------------------------------ fused attention (Tramba-S / -P encoders, inference) */
 /* Both entries: K and V of one (problem, head) are staged whole in LDS (at most 256 keys), scores on MFMA with f32

@@ -14,7 +14,9 @@
 //     reference steps once per batch): gradient accumulation, the global L2 norm with its clip factor and the "a
 //     gradient is not finite: skip this step" decision.  The decisions live in a small record ON THE DEVICE
 //     (tramba_step_ctl) that the kernels read and write, so a replayed hipGraph needs no host value that changes from
-//     step to step.
+//     step to step.  Dynamic loss scaling for fp16 activations hangs on the same record: a second one (tramba_loss_scale)
+//     holds a power-of-two scale that the loss gradient kernels read through `gscale`, tramba_grad_norm_scaled folds its
+//     inverse into the optimizer's scalar, and a one-lane kernel moves it after the optimizer by the record's skip flag;
 //
 //   * the reference's other two losses (utils/loss.py:14-42: structure_loss, wbce): the same passes with a per-pixel weight
 //     map formed once per call from the label (separable box sums in LDS), 12 B per label pixel and output;
@@ -24,6 +26,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace tramba {
@@ -642,7 +645,8 @@ constexpr int kNormFinishThreads = 1024;
 __global__ __launch_bounds__(kNormFinishThreads) void grad_norm_finish_kernel(const double *__restrict__ part,
                                                                              const unsigned *__restrict__ bad, int nchunk,
                                                                              double mean_scale, double max_norm,
-                                                                             int skip_nonfinite, tramba_step_ctl *ctl)
+                                                                             int skip_nonfinite, tramba_step_ctl *ctl,
+                                                                             const tramba_loss_scale *ls)
 {
     __shared__ double red[kNormFinishThreads / kWave];
     __shared__ unsigned redbad[kNormFinishThreads / kWave];
@@ -668,6 +672,8 @@ __global__ __launch_bounds__(kNormFinishThreads) void grad_norm_finish_kernel(co
             tot += red[q];
             any |= redbad[q];
         }
+        // gradients that carry a loss scale 2^k: the mean and the un-scaling are one exact factor (ls null: mean_scale as given)
+        if (ls) mean_scale *= (double)ls->inv_scale;
         const float norm = (float)(sqrt(tot) * mean_scale);
         double scale = mean_scale;
         if (max_norm > 0.0) {                       // torch.nn.utils.clip_grad_norm_: min(1, max_norm / (norm + 1e-6))
@@ -682,6 +688,27 @@ __global__ __launch_bounds__(kNormFinishThreads) void grad_norm_finish_kernel(co
         ctl->micro = 0;
         ctl->skipped_steps += skip;
     }
+}
+
+// The loss scale's move after a step: one lane.  Every quantity is a power of two inside fp32's normal range (the entry
+// checks the hyper-parameters, the clamps keep the scale there), so products and the division are exact.
+__global__ void loss_scale_update_kernel(tramba_loss_scale *ls, const tramba_step_ctl *ctl, float growth, float backoff,
+                                         int growth_interval, float min_scale, float max_scale)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    float scale = ls->scale;
+    int good = ls->good_steps;
+    if (ctl->skip != 0) {
+        scale = fmaxf(min_scale, scale * backoff);
+        good = 0;
+        ls->backoffs += 1;
+    } else if (++good >= growth_interval) {
+        scale = fminf(max_scale, scale * growth);
+        good = 0;
+    }
+    ls->scale = scale;
+    ls->inv_scale = __fdiv_rn(1.0f, scale);
+    ls->good_steps = good;
 }
 
 // the tensors dealt to ceil(count / per_launch) launches of equal weight: largest first, in snake order
@@ -977,8 +1004,9 @@ extern "C" size_t tramba_grad_norm_workspace(const int64_t *numel, int count)
     return n < 0 ? 0 : (size_t)n * (sizeof(double) + sizeof(unsigned));
 }
 
-extern "C" int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
-                                int skip_nonfinite, tramba_step_ctl *ctl, void *workspace, size_t workspace_bytes, void *stream)
+static int grad_norm_impl(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
+                          int skip_nonfinite, tramba_step_ctl *ctl, const tramba_loss_scale *ls, void *workspace,
+                          size_t workspace_bytes, void *stream)
 {
     TRAMBA_CHECK(grads && numel && ctl && workspace, "grad_norm: null argument");
     TRAMBA_CHECK(count > 0, "grad_norm: count must be positive (got %d)", count);
@@ -1015,7 +1043,44 @@ extern "C" int tramba_grad_norm(const float *const *grads, const int64_t *numel,
         base += blocks;
     }
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kNormFinishThreads), 0, s, part, bad, (int)nchunk, mean_scale,
-                       max_norm, skip_nonfinite, ctl);
+                       max_norm, skip_nonfinite, ctl, ls);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_grad_norm(const float *const *grads, const int64_t *numel, int count, double mean_scale, double max_norm,
+                                int skip_nonfinite, tramba_step_ctl *ctl, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grad_norm_impl(grads, numel, count, mean_scale, max_norm, skip_nonfinite, ctl, nullptr, workspace, workspace_bytes,
+                          stream);
+}
+
+extern "C" int tramba_grad_norm_scaled(const float *const *grads, const int64_t *numel, int count, double mean_scale,
+                                       double max_norm, int skip_nonfinite, tramba_step_ctl *ctl, const tramba_loss_scale *ls,
+                                       void *workspace, size_t workspace_bytes, void *stream)
+{
+    return grad_norm_impl(grads, numel, count, mean_scale, max_norm, skip_nonfinite, ctl, ls, workspace, workspace_bytes, stream);
+}
+
+// 2^k with 2^k and 2^-k both normal in fp32
+static bool pow2_f32(double x)
+{
+    int e = 0;
+    return x > 0.0 && std::frexp(x, &e) == 0.5 && e - 1 >= -126 && e - 1 <= 126;
+}
+
+extern "C" int tramba_loss_scale_update(tramba_loss_scale *ls, const tramba_step_ctl *ctl, double growth, double backoff,
+                                        int growth_interval, double min_scale, double max_scale, void *stream)
+{
+    TRAMBA_CHECK(ls && ctl, "loss_scale_update: null argument");
+    TRAMBA_CHECK(pow2_f32(growth) && growth > 1.0, "loss_scale_update: growth must be a power of two above 1 (got %g)", growth);
+    TRAMBA_CHECK(pow2_f32(backoff) && backoff < 1.0, "loss_scale_update: backoff must be a power of two below 1 (got %g)", backoff);
+    TRAMBA_CHECK(growth_interval >= 1, "loss_scale_update: growth_interval must be at least 1 (got %d)", growth_interval);
+    TRAMBA_CHECK(pow2_f32(min_scale), "loss_scale_update: min_scale must be a power of two in 2^-126 .. 2^126 (got %g)", min_scale);
+    TRAMBA_CHECK(pow2_f32(max_scale), "loss_scale_update: max_scale must be a power of two in 2^-126 .. 2^126 (got %g)", max_scale);
+    TRAMBA_CHECK(min_scale <= max_scale, "loss_scale_update: min_scale %g above max_scale %g", min_scale, max_scale);
+    hipLaunchKernelGGL(loss_scale_update_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, ls, ctl, (float)growth,
+                       (float)backoff, growth_interval, (float)min_scale, (float)max_scale);
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -84,6 +84,10 @@ class GraphedTrainStep:
     graph like the learning rates, so they are part of its key (a short last group of an epoch gets an update graph of
     its own, the full one stays).  The warm-up steps are one-micro-batch controlled steps; the control record, the
     accumulators and `skipped_steps` are put back with the parameters afterwards.  Returns the mean micro-batch loss.
+    A control with a loss scale (StepControl(loss_scale=...)) replays the same way: both graphs start their backward from
+    the scale in the device record, the update graph ends with the scale's move, and the scaler's hyper-parameters are
+    host scalars of that launch and so part of the update graph's key; the scaler record is put back after the warm-up
+    with the rest.
 
     `loss` (tramba_amd.train.SodLoss; None: `tramba_loss`) is what `train_step(..., loss=loss)` takes; it is recorded into
     the graphs, so it is fixed here, at construction."""
@@ -232,7 +236,7 @@ class GraphedTrainStep:
         if entry is None:
             entry = self._graphs[shape_key] = {"static": None, "mid": None, "update": {}, "pool": torch.cuda.graph_pool_handle()}
         need_mid = count > 1 and entry["mid"] is None
-        update_key = (count, control.clip_norm, control.skip_nonfinite)
+        update_key = (count, control.clip_norm, control.skip_nonfinite, None if control.scaler is None else control.scaler.key())
         need_update = update_key not in entry["update"]
         if need_mid or need_update:
             if entry["static"] is None:

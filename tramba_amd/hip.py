@@ -5,6 +5,7 @@ path is launched through this module onto torch's CURRENT stream.  There is no f
 the library is missing or the tensors are not on a HIP device the call raises.
 """
 import ctypes
+import math
 import os
 import threading
 import weakref
@@ -147,6 +148,9 @@ SIGNATURES = {
     "tramba_grad_norm_workspace": (ctypes.c_size_t, [c_vp, c_int]),
     "tramba_grad_norm": (c_int, [c_vp] * 2 + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "tramba_adam_step_ctl": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp] * 3),
+    "tramba_grad_norm_scaled": (c_int, [c_vp] * 2 + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, c_vp,
+                                        ctypes.c_size_t, c_vp]),
+    "tramba_loss_scale_update": (c_int, [c_vp] * 2 + [ctypes.c_double] * 2 + [c_int] + [ctypes.c_double] * 2 + [c_vp]),
     "tramba_window_attn_cl": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "tramba_kv_attn_cl": (c_int, [c_vp] * 3 + [c_int, c_i64] + [c_int] * 4 + [c_vp]),
     "tramba_window_attn_bwd_work": (ctypes.c_size_t, [c_int] * 6),
@@ -1442,6 +1446,36 @@ def grad_norm_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, wo
     _check(lib().tramba_grad_norm(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
                                   ctl.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
            "grad_norm")
+
+
+LOSS_SCALE_BYTES = 24    # struct tramba_loss_scale: float scale, float inv_scale, int32 good_steps, int32 reserved, int64 backoffs
+
+
+def loss_scale_record(device, init=1.0):
+    """a tramba_loss_scale on `device` at scale `init` (a power of two) and typed 0-dim views of its fields:
+    (record, {"scale", "inv_scale": fp32, "good_steps": int32, "backoffs": int64})"""
+    m, _ = math.frexp(float(init))
+    if m != 0.5 or not 2.0 ** -126 <= init <= 2.0 ** 126:
+        raise TrambaHipError(f"loss_scale_record: the scale must be a power of two in 2^-126 .. 2^126 (got {init!r})")
+    rec = torch.zeros(LOSS_SCALE_BYTES // 8, dtype=torch.int64, device=device)
+    f, i = rec.view(torch.float32), rec.view(torch.int32)
+    f[0], f[1] = float(init), 1.0 / float(init)
+    return rec, {"scale": f[0], "inv_scale": f[1], "good_steps": i[2], "backoffs": rec[2]}
+
+
+def grad_norm_scaled_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, ls, workspace):
+    """`grad_norm_raw` on gradients that carry the loss scale of the record `ls` (tramba_grad_norm_scaled): norm and scale
+    come out for the unscaled mean gradient, the un-scaling rides in the record's scale.  ls None: `grad_norm_raw`."""
+    _check(lib().tramba_grad_norm_scaled(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
+                                         ctl.data_ptr(), None if ls is None else ls.data_ptr(), workspace.data_ptr(),
+                                         workspace.numel() * workspace.element_size(), _stream()), "grad_norm_scaled")
+
+
+def loss_scale_update_raw(ls, ctl, growth, backoff, growth_interval, min_scale, max_scale):
+    """the loss scale's move after an optimizer step, decided by the step-control record's skip flag on the device
+    (tramba_loss_scale_update; a one-lane launch)"""
+    _check(lib().tramba_loss_scale_update(ls.data_ptr(), ctl.data_ptr(), float(growth), float(backoff), int(growth_interval),
+                                          float(min_scale), float(max_scale), _stream()), "loss_scale_update")
 
 
 def im2col3x3_cl(x, stride, pad, ckp):

@@ -1509,14 +1509,25 @@ class _SS2DInnerCL(torch.autograd.Function):
         gym = gym.contiguous()
         if gym.dtype not in (torch.float32, xs.dtype):
             gym = gym.float()
-        gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs, xdbl, order, dtw, dtb, al, dsf, gym, states=states,
-                                                           a_log=True, bc_partials=True)
+        # fp16 activations: the gradient of the raw time step is the smallest quantity of the whole pass (measured: most of it
+        # below fp16's normal range even under a loss scale of 2^16, 13 % relative error in d(dt_projs_weight)),
+        # and the kernel stores it in the activation dtype.  The scan backward therefore runs its fp32 form on the same values
+        # (graw comes out in fp32) and the two projections take the split passes of the fp32 mode; gu goes back to fp16.
+        wide = xs.dtype == torch.float16
+        if wide:
+            gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs.float(), xdbl, order, dtw, dtb, al, dsf, gym.float(),
+                                                               states=states, a_log=True, bc_partials=True)
+            gu = gu.to(xs.dtype)
+        else:
+            gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs, xdbl, order, dtw, dtb, al, dsf, gym, states=states,
+                                                               a_log=True, bc_partials=True)
+        wide = wide or xs.dtype == torch.float32
         cd = torch.bfloat16 if xs.dtype == torch.float32 else xs.dtype
-        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if xs.dtype == torch.float32 else cd)
+        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if wide else cd)
         # the two per-direction projections on the (B,K,L,.) tensors as they are:
         #   d(dt_projs_weight)[k] = sum_{b,l} graw^T ranks   (TN, tramba_wgrad_cl with groups = K, batches = B)
         #   d(ranks)              = graw @ dt_w[k]           (tramba_rows_gemm_cl into the first R floats of every gseq row)
-        if xs.dtype != torch.float32:
+        if not wide:
             # (K, D, R8); a leaf's gradient, handed on as it is when no columns are cut and no cast follows: its slab sums
             # join the step's batched ones
             g_dtw = hip.wgrad_grouped_cl(graw, ranks, defer=ranks.shape[-1] == r and dtwdtype == torch.float32)

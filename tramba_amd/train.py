@@ -341,6 +341,53 @@ def _has_standing_grads(opt):
     return False
 
 
+def _is_pow2(x):
+    import math
+    return isinstance(x, (int, float)) and math.isfinite(x) and x > 0 and math.frexp(x)[0] == 0.5
+
+
+class LossScale:
+    """Hyper-parameters of dynamic loss scaling (what fp16 activations need: the gradient of a mean over B*H*W pixels lies
+    below fp16's range).  The gradient of the loss is multiplied by `scale`; the optimizer sees the
+    gradient divided by it again.  After a step that was skipped for an Inf / NaN gradient the scale is multiplied by
+    `backoff` (not below `min_scale`); after `growth_interval` steps in a row that were not, by `growth` (not above
+    `max_scale`).  torch.cuda.amp.GradScaler's defaults, plus the two clamps.  Every factor is a power of two, so scaling
+    and un-scaling are exact and a run with a scaler equals the run without one wherever nothing over- or underflows."""
+
+    def __init__(self, init=65536.0, growth=2.0, backoff=0.5, growth_interval=2000, min_scale=1.0, max_scale=2.0 ** 24):
+        for name, v in (("init", init), ("growth", growth), ("backoff", backoff), ("min_scale", min_scale), ("max_scale", max_scale)):
+            if not _is_pow2(v) or not 2.0 ** -126 <= v <= 2.0 ** 126:
+                raise ValueError(f"LossScale: {name} must be a power of two in 2^-126 .. 2^126 (got {v!r})")
+        if not growth > 1:
+            raise ValueError(f"LossScale: growth must be above 1 (got {growth!r})")
+        if not backoff < 1:
+            raise ValueError(f"LossScale: backoff must be below 1 (got {backoff!r})")
+        if int(growth_interval) != growth_interval or growth_interval < 1:
+            raise ValueError(f"LossScale: growth_interval must be a positive integer (got {growth_interval!r})")
+        if not min_scale <= max_scale:
+            raise ValueError(f"LossScale: min_scale {min_scale!r} above max_scale {max_scale!r}")
+        # (`init` may lie outside the clamps: they bound where the scale MOVES to)
+        self.init, self.growth, self.backoff = float(init), float(growth), float(backoff)
+        self.growth_interval, self.min_scale, self.max_scale = int(growth_interval), float(min_scale), float(max_scale)
+
+    def key(self):
+        """the host scalars a captured update bakes in"""
+        return (self.growth, self.backoff, self.growth_interval, self.min_scale, self.max_scale)
+
+    def moved(self, scale, good_steps, skipped):
+        """the rule: (scale, good_steps) after a step that was / was not skipped"""
+        if skipped:
+            return max(self.min_scale, scale * self.backoff), 0
+        good_steps += 1
+        if good_steps >= self.growth_interval:
+            return min(self.max_scale, scale * self.growth), 0
+        return scale, good_steps
+
+    def __repr__(self):
+        return (f"LossScale(init={self.init!r}, growth={self.growth!r}, backoff={self.backoff!r}, growth_interval="
+                f"{self.growth_interval!r}, min_scale={self.min_scale!r}, max_scale={self.max_scale!r})")
+
+
 class StepControl:
     """What an optimisation step built from several micro-batches needs to keep between them, and between replays of a
     captured step:
@@ -349,7 +396,12 @@ class StepControl:
                       optimizer steps once on the mean (N micro-batches accumulated == N data-parallel ranks averaged);
       clip_norm       the mean gradient is scaled by min(1, clip_norm / (norm + 1e-6)), torch's clip_grad_norm_ rule;
       skip_nonfinite  a step whose accumulated gradient holds an Inf / NaN element changes nothing (parameters, moments,
-                      Adam's step counters) and is counted in `skipped_steps`.
+                      Adam's step counters) and is counted in `skipped_steps`;
+      loss_scale      None, "dynamic" (= LossScale()) or a LossScale: the gradient of every micro-batch's loss is multiplied
+                      by a scale that lives next to the record (constant over the micro-batches of a step), the optimizer
+                      gets the gradient divided by it again, and the scale moves after every optimizer step by the rule
+                      of `LossScale`.  Implies skip_nonfinite (a skipped step is what cuts the scale; an explicit False is
+                      refused).  The returned loss and `grad_norm` stay unscaled.
 
     On the device (fp32 parameters, the library's `Adam`) all three are the library's kernels around a 24-byte record in
     device memory (tramba_step_ctl): tramba_grad_accumulate after each backward, tramba_grad_norm once, and the optimizer
@@ -361,21 +413,44 @@ class StepControl:
 
     `grad_norm` (the norm of the mean gradient before clipping) and `skipped_steps` are 0-dim tensors on the parameters'
     device, valid after the first step: log them once per epoch, reading them costs a sync.  Memory: one fp32 accumulator
-    per trainable parameter (with a data-parallel reducer its flat buckets are the accumulators)."""
+    per trainable parameter (with a data-parallel reducer its flat buckets are the accumulators).
 
-    def __init__(self, accumulate=1, clip_norm=None, skip_nonfinite=False):
+    With a loss scale the device path keeps a second 24-byte record (tramba_loss_scale): the backward starts from a 0-dim
+    view of its `scale` (the loss gradient kernels read it through their `gscale` pointer), tramba_grad_norm_scaled folds
+    1 / scale into the one scalar the optimizer kernel multiplies in, and tramba_loss_scale_update moves the scale behind
+    the optimizer's launches -- again no host decision, so a captured step replays all of it.  After such a step `p.grad`
+    holds the SCALED sum over the micro-batches (p.grad / loss_scale-at-that-step / micro-batches is the mean gradient);
+    on the host path it is the unscaled clipped mean as before.  `loss_scale` and `scale_backoffs` are 0-dim tensors like
+    the two above (the scale the NEXT step will use; how often it was cut); `state_dict()` / `load_state_dict()` carry
+    scale, good_steps, backoffs and skipped_steps across a restart."""
+
+    def __init__(self, accumulate=1, clip_norm=None, skip_nonfinite=None, loss_scale=None):
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"StepControl: accumulate must be a positive integer (got {accumulate!r})")
         if clip_norm is not None and not clip_norm > 0:
             raise ValueError(f"StepControl: clip_norm must be positive or None (got {clip_norm!r})")
+        if isinstance(loss_scale, str):
+            if loss_scale != "dynamic":
+                raise ValueError(f"StepControl: loss_scale={loss_scale!r}: None, 'dynamic' or a LossScale")
+            loss_scale = LossScale()
+        if loss_scale is not None and not isinstance(loss_scale, LossScale):
+            raise TypeError(f"StepControl: loss_scale={loss_scale!r}: None, 'dynamic' or a LossScale")
+        if loss_scale is not None and skip_nonfinite is not None and not skip_nonfinite:
+            raise ValueError("StepControl: a loss scale needs skip_nonfinite (a skipped step is what cuts the scale)")
         self.accumulate = int(accumulate)
         self.clip_norm = None if clip_norm is None else float(clip_norm)
-        self.skip_nonfinite = bool(skip_nonfinite)
+        self.skip_nonfinite = bool(skip_nonfinite) or loss_scale is not None
+        self.scaler = loss_scale
         self._key = None            # what the buffers below were laid out for
         self._device_path = None
         self._record = self._fields = self._flat = self._workspace = None
         self._acc = {}              # parameter -> its accumulator (a 16-byte aligned view)
         self._norm = self._skipped = None
+        self._ls_record = self._ls = None   # device: the tramba_loss_scale and its views; host: {"scale", "good_steps", "backoffs"}
+        # what the records start from when they are laid out (load_state_dict before the first step lands here)
+        self._start = {"skipped_steps": 0}
+        if loss_scale is not None:
+            self._start.update(scale=loss_scale.init, good_steps=0, backoffs=0)
         self._plans = {}
         self._used = set()          # parameters that had a gradient in a micro-batch of the step under way
         self._dirty = set()         # parameters whose accumulator holds an earlier step's sums
@@ -392,6 +467,53 @@ class StepControl:
         if self._key is None:
             raise RuntimeError("StepControl.skipped_steps: no step has run yet")
         return self._fields["skipped_steps"] if self._device_path else self._skipped
+
+    def _scaler_field(self, name, what):
+        if self.scaler is None:
+            raise RuntimeError(f"StepControl.{what}: this control has no loss scale")
+        if self._key is None:
+            raise RuntimeError(f"StepControl.{what}: no step has run yet")
+        return self._ls[name]
+
+    @property
+    def loss_scale(self):
+        """the scale the next step multiplies its loss gradient by"""
+        return self._scaler_field("scale", "loss_scale")
+
+    @property
+    def scale_backoffs(self):
+        """how often a skipped step has cut the scale"""
+        return self._scaler_field("backoffs", "scale_backoffs")
+
+    def state_dict(self):
+        """host numbers (reading them is a sync): skipped_steps, and with a loss scale its scale, good_steps, backoffs"""
+        if self._key is None:
+            return dict(self._start)
+        sd = {"skipped_steps": int(self.skipped_steps)}
+        if self.scaler is not None:
+            sd.update(scale=float(self._ls["scale"]), good_steps=int(self._ls["good_steps"]), backoffs=int(self._ls["backoffs"]))
+        return sd
+
+    def load_state_dict(self, sd):
+        want = {"skipped_steps"} | ({"scale", "good_steps", "backoffs"} if self.scaler is not None else set())
+        if set(sd) != want:
+            raise ValueError(f"StepControl.load_state_dict: keys {sorted(sd)} for a control that keeps {sorted(want)}")
+        if self.scaler is not None and not (_is_pow2(float(sd["scale"])) and 2.0 ** -126 <= sd["scale"] <= 2.0 ** 126):
+            raise ValueError(f"StepControl.load_state_dict: scale {sd['scale']!r} is no power of two in 2^-126 .. 2^126")
+        self._start = {k: (float(v) if k == "scale" else int(v)) for k, v in sd.items()}
+        if self._key is not None:
+            self._fill_state()
+
+    def _fill_state(self):
+        """write self._start into the records"""
+        st = self._start
+        (self._fields["skipped_steps"] if self._device_path else self._skipped).fill_(st["skipped_steps"])
+        if self.scaler is not None:
+            self._ls["scale"].fill_(st["scale"])
+            self._ls["good_steps"].fill_(st["good_steps"])
+            self._ls["backoffs"].fill_(st["backoffs"])
+            if self._device_path:
+                self._ls["inv_scale"].fill_(1.0 / st["scale"])
 
     # ------------------------------------------------------------------ buffers
     def _bind(self, opt, reducer=None):
@@ -429,18 +551,25 @@ class StepControl:
                 self._flat.append(flat)
                 for p, off in zip(ps, offs):
                     self._acc[p] = flat[off:off + p.numel()].view_as(p)
-        skipped = 0 if self._key is None else int(self.skipped_steps)      # (a re-layout keeps the count)
+        self._start = self.state_dict()            # (a re-layout keeps the count and the scale)
         if device_path:
             import ctypes
             self._record, self._fields = hip.step_ctl_record(dev)
-            self._fields["skipped_steps"].fill_(skipped)
+            if self.scaler is not None:
+                self._ls_record, self._ls = hip.loss_scale_record(dev, self._start["scale"])
             numel = (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat])
             nbytes = hip.grad_norm_workspace(numel, len(self._flat))
             self._workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         else:
             self._norm = torch.zeros((), dtype=params[0].dtype if params[0].dtype.is_floating_point else torch.float32, device=dev)
-            self._skipped = torch.full((), skipped, dtype=torch.int64, device=dev)
+            self._skipped = torch.zeros((), dtype=torch.int64, device=dev)
+            if self.scaler is not None:
+                self._ls_record = None
+                self._ls = {"scale": torch.zeros((), dtype=torch.float32, device=dev),
+                            "good_steps": torch.zeros((), dtype=torch.int32, device=dev),
+                            "backoffs": torch.zeros((), dtype=torch.int64, device=dev)}
         self._device_path, self._params, self._key, self._plans = device_path, params, key, {}
+        self._fill_state()
         self._dirty = set(params) if reducer is not None else set()    # own buffers start as zeros, a reducer's buckets may not
         return params
 
@@ -454,7 +583,17 @@ class StepControl:
     def _state_tensors(self):
         """every tensor of this object that a step rewrites (GraphedTrainStep saves and restores them around its warm-up)"""
         ts = [self._record] if self._device_path else [self._norm, self._skipped]
+        if self.scaler is not None:
+            ts += [self._ls_record] if self._device_path else list(self._ls.values())
         return ts + list(self._flat)
+
+    def _backward_seed(self, loss):
+        """what the backward of a micro-batch's loss starts from: None (ones), or the loss scale -- on the device a VIEW of
+        the record, so a captured backward reads the scale of the step it is replayed in"""
+        if self.scaler is None:
+            return None
+        scale = self._ls["scale"]
+        return scale if scale.dtype == loss.dtype and scale.shape == loss.shape else scale.to(loss.dtype).reshape(loss.shape)
 
     # ------------------------------------------------------------------ the two halves of a step
     def _accumulate(self, params, first, all_ranks):
@@ -518,20 +657,35 @@ class StepControl:
             if plan is None:
                 plan = self._plans["norm"] = (hip.pointer_array(self._flat),
                                               (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat]))
-            hip.grad_norm_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
-                              self._record, self._workspace)
+            if self.scaler is None:
+                hip.grad_norm_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
+                                  self._record, self._workspace)
+            else:
+                hip.grad_norm_scaled_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
+                                         self._record, self._ls_record, self._workspace)
             opt.step(gscale=self._fields["scale"], skip=self._fields["skip"])
+            if self.scaler is not None:
+                hip.loss_scale_update_raw(self._ls_record, self._record, *self.scaler.key())
             return
         with torch.no_grad():
             grads = [p.grad for p in used]
             finite = bool(torch.stack([torch.isfinite(g).all() for g in grads]).all()) if self.skip_nonfinite else True
             torch._foreach_div_(grads, float(count))
+            if self.scaler is not None:                # a power of two: the unscaled mean, bit for bit
+                scale, good = float(self._ls["scale"]), int(self._ls["good_steps"])
+                torch._foreach_mul_(grads, 1.0 / scale)
             norm = torch.nn.utils.clip_grad_norm_(used, float("inf") if self.clip_norm is None else self.clip_norm)
             self._norm.copy_(norm)
         if finite:
             opt.step()
         else:
             self._skipped += 1
+        if self.scaler is not None:
+            scale, good = self.scaler.moved(scale, good, not finite)
+            self._ls["scale"].fill_(scale)
+            self._ls["good_steps"].fill_(good)
+            if not finite:
+                self._ls["backoffs"] += 1
 
 
 def _micro_batches(images, label, control):
@@ -561,11 +715,12 @@ def _controlled_micro_batch(model, opt, images, label, control, params, first, a
     for g in opt.param_groups:
         for p in g["params"]:
             p.grad = None
+    seed = control._backward_seed(loss)              # the loss scale, constant over the micro-batches of a step
     if DEFER_SUMS:
         with hip.deferred_sums():
-            loss.backward()
+            loss.backward(gradient=seed)
     else:
-        loss.backward()
+        loss.backward(gradient=seed)
     control._accumulate(params, first, all_ranks)
     return loss.detach()
 
@@ -634,12 +789,17 @@ def _ckpt_dir(save_model, method):
     return os.path.join(save_model, method)
 
 
-def save_resume(save_model, method, model, opt, epoch):
-    """train.py:254-262 (written every 5th epoch there)."""
+def save_resume(save_model, method, model, opt, epoch, control=None):
+    """train.py:254-262 (written every 5th epoch there).  A `control` with a loss scale adds its state under the extra
+    key "step_control" (the reference's loader reads the three keys it knows and ignores a fourth); without one the file
+    holds the reference's three keys and nothing else."""
     d = _ckpt_dir(save_model, method)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, f"{method}_resume.pth")
-    torch.save({"model": model.state_dict(), "optimizer": opt.state_dict(), "epoch": epoch}, path)
+    ck = {"model": model.state_dict(), "optimizer": opt.state_dict(), "epoch": epoch}
+    if control is not None and control.scaler is not None:
+        ck["step_control"] = control.state_dict()
+    torch.save(ck, path)
     return path
 
 
@@ -652,15 +812,19 @@ def save_best(save_model, method, model, mae, epoch):
     return path
 
 
-def load_resume(resume, save_model, method, model, opt, map_location=None):
+def load_resume(resume, save_model, method, model, opt, map_location=None, control=None):
     """train.py:214-229.  resume=None -> 0; "last" -> the resume file (model + optimizer, continues at epoch+1);
-    anything else is a state_dict path whose file name ends in `_<epoch>.pth` (continues at that number)."""
+    anything else is a state_dict path whose file name ends in `_<epoch>.pth` (continues at that number).
+    `control`: a StepControl with a loss scale continues from the state `save_resume(..., control=)` wrote, when the file
+    has one (a file written without a scaler leaves the control as it is: a fresh one starts at its `init`)."""
     if resume is None:
         return 0
     if resume == "last":
         ck = torch.load(os.path.join(_ckpt_dir(save_model, method), f"{method}_resume.pth"), map_location=map_location)
         model.load_state_dict(ck["model"], strict=True)
         opt.load_state_dict(ck["optimizer"])
+        if control is not None and control.scaler is not None and "step_control" in ck:
+            control.load_state_dict(ck["step_control"])
         return ck["epoch"] + 1
     model.load_state_dict(torch.load(resume, map_location=map_location), strict=True)
     return int(os.path.basename(resume).split("_")[-1].split(".")[0])
@@ -690,7 +854,8 @@ def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_
     `graph=True` (single process, optimizer from `get_opt(..., capturable=True)`): every step is a hipGraph replay
     (tramba_amd.graph.GraphedTrainStep), re-captured by itself when the learning rate steps.
     `control` (StepControl): `control.accumulate` consecutive batches of `batches(epoch)` make one optimizer step; a short
-    last group is a step over the batches it has, as a short last batch is a step today.
+    last group is a step over the batches it has, as a short last batch is a step today.  With a loss scale its state
+    goes into the resume file (`save_resume(..., control=)`; hand the same control to `load_resume`).
     `loss` (SodLoss): the loss every step uses (None: `tramba_loss`)."""
     loss_fn = loss
     step_fn = train_step
@@ -716,7 +881,7 @@ def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_
             if is_main and (best_mae is None or mae < best_mae):
                 save_best(save_model, method, model, mae, epoch)
         if is_main and (epoch + 1) % 5 == 0:
-            save_resume(save_model, method, model, opt, epoch)
+            save_resume(save_model, method, model, opt, epoch, control=control)
         history.append({"epoch": epoch, "lr": lr, "loss": mean_loss, "mae": mae})
         if log is not None:
             log(history[-1])
