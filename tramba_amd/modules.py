@@ -1132,7 +1132,7 @@ class _SS2DCoreCL(torch.autograd.Function):
             gym = gym.float()
         # (dB / dC stay packed (B,K,L) arrays: accumulating them straight into the RG-strided columns of g_seq -- the
         # kernel can, `bc_stride` -- put every atomic on a cache line of its own and cost the scan backward 30 %)
-        gu, graw, g_b, g_c, gpar = hip.ss2d_scan_bwd_cl(x, xdbl, order, dt_w, dt_bias, a_neg, ds, gym, states=states)
+        gu, graw, g_b, g_c, gpar = _scan_bwd_graw32(x, xdbl, order, dt_w, dt_bias, a_neg, ds, gym, states=states)
         g_seq = torch.zeros((b, k, l, rg), dtype=torch.float32, device=x.device)   # x_dbl-row gradients, sequence order
         gx = hip.ss2d_merge_sum_cl(gu, order, x.dtype)
         # row (l, k) of xdbl viewed as (B, L*K, RG) that sequence position (k, i) reads: table[k][i] * K + k.  One gather
@@ -1153,7 +1153,7 @@ class _SS2DCoreCL(torch.autograd.Function):
             g_dtw = hip.wgrad_grouped_cl(graw, ranks.to(cd))                                # (K,D,R)
             dtw_t = torch.empty((k, r, d), dtype=cd, device=x.device).copy_(dt_w.transpose(1, 2))   # transpose + cast: 1 launch
             hip.rows_gemm_cl(graw.view(b * k, l, d), dtw_t, g_seq.view(b * k, l, rg), r)
-        else:   # fp32 validation mode: three passes on bf16 splits
+        else:   # graw in fp32 (fp32 validation mode, and fp16 activations: _scan_bwd_graw32): three passes on bf16 splits
             gh, gl = _split16(graw)
             rh, rl = _split16(ranks)
             wh, wl = _split16(dt_w.transpose(1, 2).contiguous())                            # (K, R, D)
@@ -1185,6 +1185,17 @@ class _SS2DCoreCL(torch.autograd.Function):
             g_xd.index_add_(1, flat, g_seq.view(b, k * l, rg))
         gp = hip.slab_sum(gpar)                                                           # (3,K,D): contiguous planes
         return (gx, g_xd.view(b, l, k * rg), g_dtw, gp[2].reshape(-1), gp[0].reshape(-1), gp[1].reshape(-1), None)
+
+
+def _scan_bwd_graw32(x, xdbl, order, dt_w, dt_bias, a, ds, gym, **kw):
+    """hip.ss2d_scan_bwd_cl as the autograd Functions call it.  fp16 activations: graw does not fit fp16 under any usable loss
+    scale, and the kernel stores it in the activation dtype -- so the scan backward runs its fp32 form on the same
+    values (saved states are fp32 whatever the activation dtype), graw comes back in fp32 for the split passes of the fp32
+    mode, gu goes back to fp16.  Every other dtype: the call as it is."""
+    if x.dtype != torch.float16:
+        return hip.ss2d_scan_bwd_cl(x, xdbl, order, dt_w, dt_bias, a, ds, gym, **kw)
+    gu, *rest = hip.ss2d_scan_bwd_cl(x.float(), xdbl, order, dt_w, dt_bias, a, ds, gym.float(), **kw)
+    return (gu.to(x.dtype), *rest)
 
 
 # ----------------------------------------------------------------------------- fused training path (round 3)
@@ -1607,16 +1618,19 @@ class _SS2DInnerNCL(torch.autograd.Function):
         gym = gym.contiguous()
         if gym.dtype not in (torch.float32, xs.dtype):
             gym = gym.float()
-        gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs, xdbl, order, dtw, dtb, a_neg, dsf, gym, bc_partials=True)
+        # fp16 activations: graw does not fit the activation dtype (see _SS2DInnerCL.backward): the scan backward
+        # runs its fp32 form on the same values, the projections take the split passes, gu goes back to fp16
+        gu, graw, bpart, cpart, gpar = _scan_bwd_graw32(xs, xdbl, order, dtw, dtb, a_neg, dsf, gym, bc_partials=True)
+        wide = graw.dtype == torch.float32
         cd = torch.bfloat16 if xs.dtype == torch.float32 else xs.dtype
-        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if xs.dtype == torch.float32 else cd, n)
-        if xs.dtype != torch.float32:
+        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if wide else cd, n)
+        if not wide:
             g_dtw = hip.wgrad_grouped_cl(graw, ranks, defer=ranks.shape[-1] == r and dtwdtype == torch.float32)
             dtw_t = ctx.dtw_t            # (K, R, D): the shadow written after the optimizer step, when current
             if dtw_t is None:
                 dtw_t = dtw.transpose(1, 2).to(cd).contiguous()
             hip.rows_gemm_cl(graw.view(b * k, l, d), dtw_t, gseq.view(b * k, l, rg), r)
-        else:   # fp32 validation mode: three passes on bf16 splits
+        else:   # graw in fp32 (fp32 validation mode, and fp16 activations: _scan_bwd_graw32): three passes on bf16 splits
             gh, gl = _split16(graw)
             rh, rl = _split16(ranks)
             wh, wl = _split16(dtw.transpose(1, 2).contiguous())                                    # (K, R, D)
