@@ -1,5 +1,5 @@
 """Forward + backward of the SS2D op under autograd per d_state: the fused channels-last training path
-(tramba_amd.fused_dstate_training(True): SS2D._forward_train_cl on _SS2DInnerNCL, hip.ss2d_scan_n_cl and the state-looped scan
+(tramba_amd.fused_dstate_training(True): SS2D._forward_train_cl on _SS2DInnerCL, hip.ss2d_scan_n_cl and the state-looped scan
 backward) against the plugin path on the same module in the same process -- as it runs by default (fp32 atomics in the scan
 backward) and under deterministic_scan(True).  bf16, N in {2, 4, 8, 16}, the shape classes of scripts/bench_ss2d_dstate.py:
   helix96   B = 4, 96 x 96, D = 256, R = 8, K = 8        raster96  the same map, K = 4

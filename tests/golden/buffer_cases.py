@@ -124,7 +124,7 @@ CLASSIFICATION = {
     ("infer.py", "static_in = torch.empty(cap_in"): (INTEGER, torch.int32, (0, 1), "csrc/frames.hip:250"),
     # inverse permutation of the flattened scan table: inv[flat] = arange writes every entry (flat is a permutation, checked
     # on the line above); read as a row index of a (B, K L, RG) tensor with K L >= 2
-    ("modules.py", "inv = torch.empty_like(flat)"): (INTEGER, torch.int64, (0, 1), "modules.py:1182"),
+    ("modules.py", "inv = torch.empty_like(flat)"): (INTEGER, torch.int64, (0, 1), "modules.py:1174"),
 }
 
 
@@ -145,7 +145,7 @@ CONSUMER_TEXT = {
     "csrc/ss2d_fused.hip:1862": "reinterpret_cast<float2 *>(workspace)",
     "csrc/ss2d_fused.hip:1940": "(float *)workspace",
     "csrc/train_gemm.hip:621": "(float *)workspace",
-    "modules.py:1182": "[:, inv]",
+    "modules.py:1174": "[:, inv]",
 }
 
 

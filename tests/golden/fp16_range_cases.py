@@ -226,7 +226,7 @@ def _core(cfg, regime, dtype):
 
 class ScanCase(Case):
     """hip.ss2d_scan_bwd_cl in the activation dtype: gu, graw stored in it; dB, dC, dA_logs, dD, dbias in fp32.  N = 1 as
-    _SS2DCoreCL calls it (the forward launch saves the tile-entry states), N > 1 as _SS2DInnerNCL does (bc_partials).  gym may
+    _SS2DCoreCL calls it (the forward launch saves the tile-entry states), N > 1 as _SS2DInnerCL does (bc_partials).  gym may
     arrive in fp32 or in the activation dtype; the bound and poison levels use the activation dtype, the overflow level
     fp32 (gu is of dy's magnitude, so 2^17 needs a dy beyond fp16).  Metric and tolerances: ss2d_dstate_train_cases.BASE_TOL."""
 
@@ -280,7 +280,7 @@ FN_CFGS = {"fn_core_raster": SCAN_CFGS["scan_n1_raster_trained"], "fn_inner_n_ra
 
 
 class FunctionCase(Case):
-    """modules._SS2DCoreCL (N = 1) and modules._SS2DInnerNCL (N > 1) under autograd: the gradient of dt_projs_weight is an fp32
+    """modules._SS2DCoreCL (N = 1) and modules._SS2DInnerCL (N > 1) under autograd: the gradient of dt_projs_weight is an fp32
     output computed from graw, which the kernels store in the activation dtype -- the 16-bit intermediate of DESIGN section 29.
     For fp16 the Functions therefore take the scan backward's fp32 form; each of these cases fails on dt_w at 2^-6 when they do
     not (the host test shows it on the exact restatement of the 16-bit graw: 4.2e-1, 2.0e-1, 3.5e-1 against 5e-2).
@@ -321,7 +321,7 @@ class FunctionCase(Case):
             a = req(cc.a_logs.to(dev))
             xw = cc.wx.float().to(dev)
             # z is unused without its gradient; xs = x: the Function's x_proj GEMM then reproduces the case's x_dbl rows
-            ym = M._SS2DInnerNCL.apply(x, x, xw, dtw, dtb.view(c.k, c.d), a, dsl, order)
+            ym = M._SS2DInnerCL.apply(x, x, xw, dtw, dtb.view(c.k, c.d), a, dsl, order)
         ym.backward(dy)
         return dict(dt_w=dtw.grad, dt_b=dtb.grad.reshape(c.k, c.d), a=a.grad, ds=dsl.grad)
 
@@ -677,7 +677,7 @@ TAIL_CFGS = {"tail_n1_raster": (2, 12, 64, 4, "raster", 1), "tail_segments_k8": 
 
 
 class TailCase(Case):
-    """ss2d_bwd_prep -> rows_gemm_cl -> ss2d_bwd_assemble as one chain, as the 16-bit route of _SS2DInnerCL / _SS2DInnerNCL
+    """ss2d_bwd_prep -> rows_gemm_cl -> ss2d_bwd_assemble as one chain, as the 16-bit route of _SS2DInnerCL (N = 1 and N > 1)
     runs it: graw (activation dtype) is the upstream gradient, the dB / dC per-channel-tile partials (fp32) ride the same
     scale; the output is g_xd, the x_dbl-row gradients in spatial order, stored in the activation dtype.  Max-relative, the
     5e-2 at which test_ss2d_core_training_gradients holds the x_dbl gradient.  dt_w is drawn 8 x larger than the scan cases

@@ -1,6 +1,6 @@
 """Block level: fp16 activations + LossScale(init=2^16) against bf16, for every kind of training block -- the check of
 tests/test_gpu_loss_scale.py::test_fp16_needs_the_scale_and_with_it_beats_bf16 (one MultiScaleDecoderBlock(32)) carried to
-the blocks that had never been held to it: the d_state > 1 block (_SS2DInnerNCL), an SS2D that takes _core_train_cl /
+the blocks that had never been held to it: the d_state > 1 block (_SS2DInnerCL), an SS2D that takes _core_train_cl /
 _SS2DCoreCL, the Swin and PVT blocks on the fused attention backward, a ResNet bottleneck and the PVT block on the library's
 encoder convolutions.
 
@@ -60,7 +60,7 @@ class _Spec:
 
 class _VssN16(_Spec):
     tag, cin, cout = "vss_dstate16", 16, 16
-    module = "VSSBlock(hidden_dim=16, ssm_d_state=16), fused d_state training on (_SS2DInnerNCL)"
+    module = "VSSBlock(hidden_dim=16, ssm_d_state=16), fused d_state training on (_SS2DInnerCL)"
 
     def make(self, stock):
         import tramba_amd as ta
@@ -232,7 +232,7 @@ def test_fp16_with_the_scale_beats_bf16_on_every_training_block(tag, monkeypatch
     spec = SPECS[tag]()
     reached = []
     if tag.startswith("vss"):
-        fn = M._SS2DInnerNCL if tag == "vss_dstate16" else M._SS2DCoreCL
+        fn = M._SS2DInnerCL if tag == "vss_dstate16" else M._SS2DCoreCL
         real = fn.apply
         monkeypatch.setattr(fn, "apply", staticmethod(lambda *a: (reached.append(1), real(*a))[1]))
     per_logit, errs = parity_errors(spec)
@@ -257,7 +257,7 @@ def test_fp16_with_the_scale_beats_bf16_on_every_training_block(tag, monkeypatch
 
 
 def test_bf16_function_at_dstate_16_is_undisturbed():
-    """_SS2DInnerNCL in bf16 (the route fp16 left): the merged output and every gradient equal, bit for bit, the launches
+    """_SS2DInnerCL in bf16 (the route fp16 left): the merged output and every gradient equal, bit for bit, the launches
     the Function made before fp16 had a route of its own, made by hand here -- the scan backward in the activation dtype,
     graw in bf16 into the grouped weight-gradient GEMM and rows_gemm_cl"""
     import ss2d_dstate_cases as sdc
@@ -272,7 +272,7 @@ def test_bf16_function_at_dstate_16_is_undisturbed():
     xs = torch.nn.functional.silu(z.detach().float()).to(BF16)
     xw, dtw, dtb, al, ds = (t.float().to(dev).requires_grad_() for t in (cc.wx, cc.wdt, cc.dtb, cc.a_logs, cc.ds))
     gym = tc.gym_of(sdc.core_as_scan_case(cc)).to(BF16).to(dev)
-    ym = M._SS2DInnerNCL.apply(z, xs, xw, dtw, dtb, al, ds, order)
+    ym = M._SS2DInnerCL.apply(z, xs, xw, dtw, dtb, al, ds, order)
     ym.backward(gym)
     f = lambda t: t.detach().float().contiguous()        # noqa: E731
     wa = M._xproj_padded(xw, BF16, n)[0]
@@ -300,7 +300,7 @@ def test_bf16_function_at_dstate_16_is_undisturbed():
 
 @pytest.mark.parametrize("name", ["fn_core_raster", "fn_inner_n_single_launch"])
 def test_only_fp16_leaves_the_scan_backward_call_as_it_was(name, monkeypatch):
-    """_SS2DCoreCL and _SS2DInnerNCL hand hip.ss2d_scan_bwd_cl their own tensors, untouched, for bf16 and fp32 activations (the
+    """_SS2DCoreCL and _SS2DInnerCL hand hip.ss2d_scan_bwd_cl their own tensors, untouched, for bf16 and fp32 activations (the
     call of the parent: same storage, same dtypes, same keywords) and fp32 copies for fp16 alone; graw then comes back in
     the activation dtype for bf16 and in fp32 otherwise"""
     import fp16_range_cases as rc

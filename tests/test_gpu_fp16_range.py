@@ -11,7 +11,7 @@ TRAMBA_WRITE_PROFILES=1 writes err, e_store and the bound per (case, dtype, outp
 Measured (MI355X, profiles/fp16_range.json; the table in DESIGN section 29): every kernel-level entry sits at its e_store
 at all three levels except the scan backward's gu (6.5e-3 against 1.9e-4, flat) and the attention backward at 2^-6 (worst
 element 2.6 u A against 0.84 u A at unit scale, inside 3 + 4 e_store).  The Function cases are what the 16-bit graw failed:
-dt_w at 2^-6 came out at 4.2e-1 (_SS2DCoreCL) and 3.5e-1 (_SS2DInnerNCL, single launch) against a bound of 5e-2 while passing
+dt_w at 2^-6 came out at 4.2e-1 (_SS2DCoreCL) and 3.5e-1 (_SS2DInnerCL, single launch) against a bound of 5e-2 while passing
 at 2^0 (1.3e-2, 9.1e-3); on the fp32 route they stand at 7e-6 at every level."""
 import json
 import os

@@ -1,6 +1,6 @@
 """The fused channels-last SS2D TRAINING path at d_state N = 2..16 (opt-in, tramba_amd.set_fused_dstate_training): the
 state-looped scan backward (hip.ss2d_scan_bwd_cl with a (K*D, N) `A`: ss2d_seg_n_bwd_kernel), the glue around it, the
-_SS2DInnerNCL Function and the modules that reach it, against fp64.
+_SS2DInnerCL Function and the modules that reach it, against fp64.
 
 Kernel level: every output against the fp64 adjoint of tests/golden/ss2d_dstate_train_cases.py, which
 tests/test_ss2d_dstate_train_host.py holds against autograd through oracle.ops.ss2d_core + cross_merge.  The bounds are the
@@ -8,6 +8,9 @@ project's for the N = 1 kernel (max |got - want| / max |want| <= 3e-4 for gu, 5e
 in 16 bit), and the host file shows that fp32 arithmetic in the kernel's documented form uses at most half of each on these
 inputs.  The long-memory cases (A = 0: the adjoint, like the state, crosses all segments undamped) use 8 x E32 (+ u for an
 output stored in 16 bits) throughout."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -223,7 +226,7 @@ def _function_inputs(o, dtype, dev):
 
 @pytest.mark.parametrize("name", ["segments_k8", "d40_window"])
 def test_function_against_fp64_autograd(name):
-    """_SS2DInnerNCL in fp32: the merged output within 2e-4 and the gradients of z (through the SiLU), the x_proj weight, dt_w,
+    """_SS2DInnerCL in fp32: the merged output within 2e-4 and the gradients of z (through the SiLU), the x_proj weight, dt_w,
     dt_bias, A_logs and Ds within 3e-4 / 5e-4 of autograd through oracle.ops.ss2d_core + cross_merge (max-relative); its
     forward equals the same launches made by hand bit for bit"""
     from tramba_amd import modules as M
@@ -233,7 +236,7 @@ def test_function_against_fp64_autograd(name):
     cc = o.case
     z, xs, pars = _function_inputs(o, F32, dev)
     order = H.scan_order(cc.fam, cc.h, cc.h, dev)
-    ym = M._SS2DInnerNCL.apply(z, xs, *pars, order)
+    ym = M._SS2DInnerCL.apply(z, xs, *pars, order)
     wa = H.pad_x_proj_weight(pars[0].detach(), cc.n).contiguous()
     xdbl = H.linear_cl(xs, wa, out_dtype=F32)
     a_neg = -torch.exp(pars[3].detach())
@@ -299,6 +302,196 @@ def test_function_at_dstate_1_is_undisturbed():
     t = M._dgrad(g_xd, wa, None).view(b, l, d)
     assert torch.equal(z.grad, H.ss2d_merge_grad_cl(gu, order, t, z.detach()))
     H.device_error()
+
+
+# ----------------------------------------------------------------------------- the one Function against its two parents
+def _inner_inputs(n_kind, dtype, dev):
+    """(order, n, gym, [z, xs, x_proj weight, dt_w, dt_bias, A_logs, Ds]) for _SS2DInnerCL.apply, fresh leaves: "n1" the raster
+    shape of test_function_at_dstate_1_is_undisturbed, "n16" CORE_CASES["segments_k8"] (helix, K = 8, 9 segments)"""
+    H = hip()
+    if n_kind == "n1":
+        g = torch.Generator().manual_seed(41)
+        b, h, d, r, k, n = 2, 12, 40, 3, 4, 1
+        order = H.scan_order("raster", h, h, dev)
+        z = torch.randn(b, h * h, d, generator=g).to(dtype)
+        pars = [torch.randn(k, r + 2, d, generator=g) * d ** -0.5, torch.randn(k, d, r, generator=g) * r ** -0.5,
+                torch.randn(k, d, generator=g) * 0.5 - 2, torch.log(0.5 + torch.rand(k * d, 1, generator=g)),
+                1 + 0.1 * torch.randn(k * d, generator=g)]
+        gym = torch.randn(b, h * h, d, generator=g).to(dtype)
+    else:
+        cc = sdc.core_case(tc.CORE_CASES["segments_k8"], dtype)
+        n = cc.n
+        order = H.scan_order(cc.fam, cc.h, cc.h, dev)
+        z = cc.x.permute(0, 2, 3, 1).reshape(cc.b, cc.l, cc.d).contiguous()
+        pars = [t.float() for t in (cc.wx, cc.wdt, cc.dtb, cc.a_logs, cc.ds)]
+        gym = tc.gym_of(sdc.core_as_scan_case(cc)).to(dtype)
+    z = z.to(dev).requires_grad_()
+    xs = torch.nn.functional.silu(z.detach().float()).to(dtype)
+    return order, n, gym.to(dev), [z, xs] + [p.to(dev).requires_grad_() for p in pars]
+
+
+@pytest.mark.parametrize("n_kind,dtype", [("n1", F16), ("n1", F32), ("n16", F16)], ids=IDS)
+def test_wide_routes_equal_the_parents_launches(n_kind, dtype):
+    """graw in fp32 (fp16 activations, fp32 validation mode): the output and the gradients of z, the x_proj weight, dt_w,
+    dt_bias, A_logs and Ds equal, bit for bit, the launches of the two Functions this one replaced, made by hand -- fp32
+    copies of xs / gym into the scan backward for fp16, ss2d_bwd_prep in fp32, the three split passes with passes two and
+    three written to a SEPARATE scratch tensor (the Function writes them into the dead fp32 rank rows)"""
+    from tramba_amd import modules as M
+    H = hip()
+    dev = torch.device(DEV)
+    order, n, gym, (z, xs, xw, dtw, dtb, al, ds) = _inner_inputs(n_kind, dtype, dev)
+    b, l, d = xs.shape
+    k, r = order.k, dtw.shape[-1]
+    ym = M._SS2DInnerCL.apply(z, xs, xw, dtw, dtb, al, ds, order)
+    ym.backward(gym)
+    f = lambda t: t.detach().float().contiguous()        # noqa: E731
+    rg, r8 = H.ss2d_group_stride(r, n), (r + 7) & ~7
+    wa = H.pad_x_proj_weight(xw.detach().to(dtype), n).contiguous()
+    xdbl = H.linear_cl(xs, wa, out_dtype=F32)
+    if n == 1:
+        a, states = f(al).reshape(-1), H.ss2d_scan_states(xs, order)
+        ys = H.ss2d_scan_cl(xs, xdbl, order, f(dtw), f(dtb).reshape(-1), a, f(ds), dtype, states=states, a_log=True)
+        kw = dict(states=states, a_log=True, bc_partials=True)
+    else:
+        a = torch.exp(f(al).reshape(-1, n)).neg_()
+        ys = H.ss2d_scan_n_cl(xs, xdbl, order, f(dtw), f(dtb).reshape(-1), a, f(ds), dtype)
+        kw = dict(bc_partials=True)
+    assert torch.equal(ym.detach(), H.ss2d_merge_sum_cl(ys, order, dtype))
+    x32, g32 = (xs.float(), gym.float()) if dtype == F16 else (xs, gym)
+    gu, graw, bpart, cpart, gpar = H.ss2d_scan_bwd_cl(x32, xdbl, order, f(dtw), f(dtb).reshape(-1), a, f(ds), g32, **kw)
+    gu = gu.to(dtype)
+    assert graw.dtype == F32
+    ranks, gseq = H.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, F32, n)
+    assert ranks.shape == (b, k, l, r8) and ranks.dtype == F32 and ranks.is_contiguous()
+    gh, gl = M._split16(graw)
+    rh, rl = M._split16(ranks)
+    wh, wl = M._split16(f(dtw).transpose(1, 2).contiguous())
+    g_dtw = H.wgrad_grouped_cl(gh, rh) + H.wgrad_grouped_cl(gh, rl) + H.wgrad_grouped_cl(gl, rh)
+    assert torch.equal(dtw.grad, g_dtw[..., :r].contiguous())
+    tmp = torch.zeros_like(gseq)
+    H.rows_gemm_cl(gh.view(b * k, l, d), wh, gseq.view(b * k, l, rg), r)
+    for ga_, wa_ in ((gh, wl), (gl, wh)):
+        H.rows_gemm_cl(ga_.view(b * k, l, d), wa_, tmp.view(b * k, l, rg), r)
+        gseq[..., :r] += tmp[..., :r]
+    g_xd = H.ss2d_bwd_assemble(gseq, order, r, dtype, n).view(b * l, k * rg)
+    t = M._dgrad(g_xd, wa, None).view(b, l, d)
+    assert torch.equal(z.grad, H.ss2d_merge_grad_cl(gu, order, t, z.detach()))
+    if dtype != F32:
+        segs = [s_ for g in range(k) for s_ in ((g * rg, r), (g * rg + r8, 2 * n))]
+        gxw = H.wgrad_rows_cl(g_xd, xs.view(b * l, d), segs).view(k, r + 2 * n, d)
+    else:
+        gp_ = M._wgrad(g_xd, xs.view(b * l, d))[0].view(k, rg, d)
+        gxw = torch.cat((gp_[:, :r], gp_[:, r8:r8 + 2 * n]), dim=1)
+    assert torch.equal(xw.grad, gxw)
+    gp, kd = H.slab_sum(gpar).reshape(-1), k * d
+    assert torch.equal(dtb.grad, gp[kd * (n + 1):].reshape(k, d)) and torch.equal(al.grad, gp[:kd * n].reshape(kd, n))
+    assert torch.equal(ds.grad, gp[kd * n:kd * (n + 1)])
+    for t_ in (ym, z.grad, xw.grad, dtw.grad, dtb.grad, al.grad, ds.grad):
+        assert bool(torch.isfinite(t_.float()).all())
+    H.device_error()
+
+
+def test_the_scan_backward_call_at_dstate_1(monkeypatch):
+    """_SS2DInnerCL at N = 1 hands hip.ss2d_scan_bwd_cl exactly the keywords states, a_log, bc_partials, and with them its own
+    tensors, untouched, for bf16 and fp32 activations (same storage, same dtypes) and fp32 copies for fp16 alone; graw comes
+    back in the activation dtype for bf16 and in fp32 otherwise"""
+    from tramba_amd import modules as M
+    H = hip()
+    dev = torch.device(DEV)
+    real, calls = H.ss2d_scan_bwd_cl, []
+
+    def spy(x, xdbl, order, dt_w, dt_b, a, ds, gym, **kw):
+        res = real(x, xdbl, order, dt_w, dt_b, a, ds, gym, **kw)
+        calls.append((x, gym, a, kw, res[1].dtype))
+        return res
+
+    monkeypatch.setattr(H, "ss2d_scan_bwd_cl", spy)
+    for dtype in (BF16, F32, F16):
+        order, n, gym, (z, xs, xw, dtw, dtb, al, ds) = _inner_inputs("n1", dtype, dev)
+        del calls[:]
+        M._SS2DInnerCL.apply(z, xs, xw, dtw, dtb, al, ds, order).backward(gym)
+        assert len(calls) == 1
+        x, gy, a, kw, graw_dtype = calls[0]
+        assert set(kw) == {"states", "a_log", "bc_partials"} and kw["a_log"] is True and kw["bc_partials"] is True
+        assert kw["states"].dtype == torch.uint8 and kw["states"].numel() == H.ss2d_scan_states(xs, order).numel()
+        assert a.data_ptr() == al.data_ptr() and a.dtype == F32 and a.shape == (al.numel(),)      # A_logs itself
+        if dtype == F16:
+            assert x.dtype == gy.dtype == graw_dtype == F32 and torch.equal(x, xs.float()) and torch.equal(gy, gym.float())
+        else:
+            assert x.data_ptr() == xs.data_ptr() and x.dtype == dtype and gy.data_ptr() == gym.data_ptr() and gy.dtype == dtype
+            assert graw_dtype == (BF16 if dtype == BF16 else F32)
+    H.device_error()
+
+
+LAUNCH_CASES = {"bf16_n1": ("n1", BF16), "bf16_n16": ("n16", BF16), "fp16_n1": ("n1", F16), "fp16_n16": ("n16", F16)}
+LAUNCH_PROFILE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "ss2d_inner_launches.json")
+
+
+def inner_launches(function, n_kind, dtype):
+    """{kernel name: launches} of one forward + backward of `function` called directly (fresh leaves, no shadows), counted with
+    torch.profiler as tests/test_gpu_step_control.py::_kernel_counts does, after one call that is not counted (the shared
+    zero constants, the scan order's tables)"""
+    from torch.profiler import ProfilerActivity, profile
+    dev = torch.device(DEV)
+
+    def once():
+        order, n, gym, args = _inner_inputs(n_kind, dtype, dev)
+        torch.cuda.synchronize()
+        return lambda: function.apply(*args, order).backward(gym)
+
+    once()()
+    run = once()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        run()
+        torch.cuda.synchronize()
+    counts = {}
+    for ev in prof.key_averages():
+        if not ev.key.startswith("hip"):        # (the runtime's own calls -- hipLaunchKernel, hipDeviceSynchronize -- are no kernels)
+            counts[ev.key] = counts.get(ev.key, 0) + ev.count
+    return counts
+
+
+def _launch_class(name):
+    """the framework's copy / cast kernels, its fills, everything else (the library's kernels among it)"""
+    return "copy" if "copy" in name.lower() else "fill" if "fill" in name.lower() else "other"
+
+
+@pytest.mark.parametrize("case", list(LAUNCH_CASES))
+def test_launches_equal_the_parent_commits(case):
+    """one forward + backward of the Function makes the launches the parent commit's pair of Functions made, name by name
+    (profiles/ss2d_inner_launches.json, "parent": this counting code run on the parent commit; TRAMBA_WRITE_PROFILES=1 writes
+    this tree's counts beside them as "head").  Two differences are allowed, both at N > 1 and both a launch LESS: the
+    fallback transposed dt_projs_weight of the 16-bit route is one transposing cast, as the parent's N = 1 Function made it
+    (there: a cast, then a transposing copy), so the copy / cast kernels are one fewer in all and the only name that may gain
+    a launch is one the parent's N = 1 record of that dtype holds; and a wide route has one fill fewer (no zeroed scratch).
+    Every other name, and everything at N = 1, equals the record."""
+    from tramba_amd import modules as M
+    n_kind, dtype = LAUNCH_CASES[case]
+    got = inner_launches(M._SS2DInnerCL, n_kind, dtype)
+    with open(LAUNCH_PROFILE) as f:
+        record = json.load(f)
+    for name in sorted(got):
+        print(case, got[name], name)
+    if os.environ.get("TRAMBA_WRITE_PROFILES") == "1":
+        record.setdefault("head", {})[case] = got
+        with open(LAUNCH_PROFILE, "w") as f:
+            json.dump(record, f, indent=1, sort_keys=True)
+    want = record["parent"][case]
+    wide = dtype != BF16
+    fewer = {"copy": int(n_kind != "n1" and not wide), "fill": int(n_kind != "n1" and wide), "other": 0}
+    by_class = lambda c: {cls: sum(v for k_, v in c.items() if _launch_class(k_) == cls) for cls in fewer}   # noqa: E731
+    assert {cls: v + fewer[cls] for cls, v in by_class(got).items()} == by_class(want), (by_class(got), by_class(want))
+    n1_record = record["parent"][case.replace("n16", "n1")]
+    for name in set(got) | set(want):
+        g, w, cls = got.get(name, 0), want.get(name, 0), _launch_class(name)
+        if not fewer[cls]:
+            assert g == w, (name, g, w)
+        elif cls == "copy":
+            assert g <= w + 1 and (g <= w or name in n1_record), (name, g, w)
+        else:
+            assert g <= w, (name, g, w)
+    assert sum(max(got.get(k_, 0) - want.get(k_, 0), 0) for k_ in got) <= fewer["copy"]
 
 
 # ----------------------------------------------------------------------------- module level

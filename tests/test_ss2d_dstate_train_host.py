@@ -204,7 +204,7 @@ def test_no_new_uninitialised_allocation_site():
     sites = [s for (f, line), s in bc.SITE_LINES.items() if f == "hip.py" and start < line <= stop]
     assert len(sites) == 9 and all(any(s.startswith(frag) for frag in known) for s in sites), sites
     src = open(os.path.join(ROOT, "tramba_amd", "modules.py")).read()
-    body = src[src.index("class _SS2DInnerNCL("):src.index("class SS2D(nn.Module)")]
+    body = src[src.index("def _xproj_padded("):src.index("class SS2D(nn.Module)")]
     for name in bc.TORCH_ALLOCATORS:
         assert "." + name + "(" not in body, name
 

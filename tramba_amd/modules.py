@@ -426,22 +426,26 @@ def restamp_lowp_shadows(model):
     restamp_dw_packs(model)
 
 
+def _shadow(p, dtype):
+    """p's entry of _lowp_shadow while it is current -- cast to `dtype` at p's present version, for this very object -- else
+    None"""
+    ent = _lowp_shadow.get(id(p))
+    return ent if ent is not None and ent[1] == p._version and ent[0].dtype == dtype and ent[2]() is p else None
+
+
 def _lowp(p, dtype):
     """p cast to dtype: the shadow when it is current, a fresh cast otherwise"""
     if p.dtype == dtype:
         return p
-    ent = _lowp_shadow.get(id(p))
-    if ent is not None and ent[1] == p._version and ent[0].dtype == dtype and ent[2]() is p:
-        return ent[0]
-    return p.to(dtype)
+    ent = _shadow(p, dtype)
+    return p.to(dtype) if ent is None else ent[0]
 
 
 def _lowp_t(p, dtype):
-    """p^T cast to dtype when a current shadow holds it, else None (the caller transposes)"""
-    ent = _lowp_shadow.get(id(p))
-    if ent is not None and ent[1] == p._version and ent[0].dtype == dtype and ent[2]() is p:
-        return ent[3]
-    return None
+    """p^T cast to dtype when a current shadow holds it, else None (the caller transposes).  dt_projs_weight (K, D, R): its
+    per-direction transposes (K, R, D), the only shadow it has"""
+    ent = _shadow(p, dtype)
+    return None if ent is None else ent[3]
 
 
 class _LinearTrainCL(torch.autograd.Function):
@@ -1066,22 +1070,10 @@ class _XProjCL(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w):
-        k, r2, d = w.shape
-        r = r2 - 2
-        rg = hip.ss2d_group_stride(r)
-        ent = _lowp_shadow.get(id(w))
-        if (ent is not None and ent[1] == w._version and ent[0].dtype == x.dtype and ent[2]() is w
-                and ent[0].shape == (k * rg, d)):
-            wa, ctx.wa_t = ent[0], ent[3]       # padded weight and its transpose, written after the optimizer step
-        else:
-            wl = w.detach().to(x.dtype)
-            parts = [wl[:, :r]]
-            if rg - 4 - r:
-                parts.append(_zeros_const((k, rg - 4 - r, d), x.dtype, x.device))
-            parts += [wl[:, r:], _zeros_const((k, 2, d), x.dtype, x.device)]
-            wa, ctx.wa_t = torch.cat(parts, dim=1).view(k * rg, d), None
+        k, r = w.shape[0], w.shape[1] - 2
+        wa, ctx.wa_t = _xproj_padded(w, x.dtype, 1)     # the shadows written after the optimizer step, when current
         ctx.save_for_backward(x, wa)
-        ctx.meta = (w.dtype, k, r, rg)
+        ctx.meta = (w.dtype, k, r, hip.ss2d_group_stride(r))
         return hip.linear_cl(x.contiguous(), wa, out_dtype=torch.float32)
 
     @staticmethod
@@ -1464,9 +1456,8 @@ def _xproj_padded(w, dtype, n=1):
     r = r2 - 2 * n
     rg = hip.ss2d_group_stride(r, n)
     r8 = (r + 7) & ~7
-    ent = _lowp_shadow.get(id(w)) if n == 1 else None
-    if (ent is not None and ent[1] == w._version and ent[0].dtype == dtype and ent[2]() is w
-            and ent[0].shape == (k * rg, d)):
+    ent = _shadow(w, dtype) if n == 1 else None
+    if ent is not None and ent[0].shape == (k * rg, d):
         return ent[0], ent[3]
     wl = w.detach().to(dtype)
     parts = [wl[:, :r]]
@@ -1482,59 +1473,64 @@ class _SS2DInnerCL(torch.autograd.Function):
     """SiLU -> x_proj -> scan gather + dt_proj + selective scan -> CrossMerge of forward_corev2 (vmamba.py:230-262) on
     channels-last tensors under autograd, every launch the library's.  Inputs: z (B,L,D) the pre-activation of the SiLU in
     front of the core and xs = silu(z) (both from _DwConvActCL; this Function owns the SiLU's backward), the RAW parameters
-    x_proj_weight (K,R+2,D), dt_projs_weight (K,D,R), dt_projs_bias (K,D), A_logs (K*D,1), Ds (K*D).  Returns the merged map
-    (B,L,D) before out_norm.
-    Forward: x_proj once in spatial order (GEMM, fp32 rows) -> tramba_ss2d_scan_cl (A = -exp(A_logs) formed in the kernel,
-    tile-entry states saved) -> merge.  Backward: tramba_ss2d_scan_bwd_cl (dB / dC as per-channel-tile partials, no atomics)
-    -> tramba_ss2d_bwd_prep_cl (rank rows gathered, partials summed) -> the two per-direction projections on the grouped
-    matrix-core kernels -> tramba_ss2d_bwd_assemble_cl (x_dbl-row gradients back to spatial order through the inverse
-    table, deterministic) -> x_proj input gradient (GEMM) -> tramba_ss2d_merge_grad_cl: (merge(gu) + that) * silu'(z)."""
+    x_proj_weight (K,R+2N,D), dt_projs_weight (K,D,R), dt_projs_bias (K,D), A_logs (K*D,N), Ds (K*D), d_state N = 1..16
+    (N > 1 is opt-in: ops.set_fused_dstate_training).  Returns the merged map (B,L,D) before out_norm.
+    Forward: x_proj once in spatial order (GEMM, fp32 rows in the [R8 ranks | B_0.. | C_0.. | pad] layout) -> the fused scan
+    -> merge.  Backward: tramba_ss2d_scan_bwd_cl / tramba_ss2d_scan_n_bwd_cl (dB_n / dC_n as per-channel-tile partials,
+    dA_logs / dD / dbias as slabs, no atomics) -> tramba_ss2d_bwd_prep_n_cl (rank rows gathered, partials summed) -> the two
+    per-direction projections on the grouped matrix-core kernels -> tramba_ss2d_bwd_assemble_n_cl (x_dbl-row gradients back
+    to spatial order through the inverse table, deterministic) -> x_proj input gradient (GEMM) ->
+    tramba_ss2d_merge_grad_cl: (merge(gu) + that) * silu'(z).
+    N enters in one place, the forward's scan, because the kernels differ there: tramba_ss2d_scan_cl (N = 1) forms
+    -exp(A_logs) itself and saves the tile-entry states for its backward; tramba_ss2d_scan_n_cl takes A negated and its
+    backward recomputes the states.  Everything else takes N as a number.  Nothing that must survive from forward to
+    backward lives in the per-stream scan workspace: only saved tensors."""
 
     @staticmethod
     def forward(ctx, z, xs, xw, dt_w, dt_b, a_logs, ds, order):
         z, xs = z.contiguous(), xs.contiguous()
-        wa, wa_t = _xproj_padded(xw, xs.dtype)
+        n = a_logs.shape[-1]
+        wa, wa_t = _xproj_padded(xw, xs.dtype, n)          # (no shadows at n > 1: wa_t is None there)
         xdbl = hip.linear_cl(xs, wa, out_dtype=torch.float32)
         dtw, dtb = dt_w.detach().float().contiguous(), dt_b.detach().float().reshape(-1).contiguous()
-        al, dsf = a_logs.detach().float().reshape(-1).contiguous(), ds.detach().float().contiguous()
-        states = hip.ss2d_scan_states(xs, order)
-        ys = hip.ss2d_scan_cl(xs, xdbl, order, dtw, dtb, al, dsf, xs.dtype, states=states, a_log=True)
-        ctx.save_for_backward(z, xs, xdbl, dtw, dtb, al, dsf, states, wa)
+        dsf = ds.detach().float().contiguous()
+        # the one branch on n, imposed by the kernels (see the docstring); `a` is what the backward launch is given too
+        if n == 1:
+            a = a_logs.detach().float().reshape(-1).contiguous()                        # A_logs itself
+            states = hip.ss2d_scan_states(xs, order)
+            ys = hip.ss2d_scan_cl(xs, xdbl, order, dtw, dtb, a, dsf, xs.dtype, states=states, a_log=True)
+        else:
+            a = torch.exp(a_logs.detach().float().reshape(-1, n)).neg_()                # (K*D, N), vmamba.py:246
+            states = None
+            ys = hip.ss2d_scan_n_cl(xs, xdbl, order, dtw, dtb, a, dsf, xs.dtype)
+        ctx.save_for_backward(z, xs, xdbl, dtw, dtb, a, dsf, states, wa)
         ctx.wa_t, ctx.order = wa_t, order
-        ent = _lowp_shadow.get(id(dt_w))
-        ctx.dtw_t = ent[3] if (ent is not None and ent[1] == dt_w._version and ent[2]() is dt_w
-                               and ent[3] is not None and ent[3].dtype == xs.dtype) else None
-        ctx.meta = (xw.dtype, xw.shape, dt_w.dtype, dt_b.shape, a_logs.shape)
+        ctx.dtw_t = _lowp_t(dt_w, xs.dtype)     # (K, R, D): the shadow written after the optimizer step, when current
+        ctx.meta = (xw.dtype, n, dt_w.dtype, dt_b.shape, a_logs.shape)
         ctx.par_f32 = dt_b.dtype == a_logs.dtype == ds.dtype == torch.float32    # (deferred sums go to fp32 leaves only)
         return hip.ss2d_merge_sum_cl(ys, order, xs.dtype)
 
     @staticmethod
     def backward(ctx, gym):
-        z, xs, xdbl, dtw, dtb, al, dsf, states, wa = ctx.saved_tensors
+        z, xs, xdbl, dtw, dtb, a, dsf, states, wa = ctx.saved_tensors
         order = ctx.order
-        xwdtype, xwshape, dtwdtype, dtbshape, alshape = ctx.meta
+        xwdtype, n, dtwdtype, dtbshape, alshape = ctx.meta
         b, l, d = xs.shape
         k, r = order.k, dtw.shape[-1]
-        rg = hip.ss2d_group_stride(r)
-        r8 = rg - 4
+        rg = hip.ss2d_group_stride(r, n)
+        r8 = (r + 7) & ~7
         gym = gym.contiguous()
         if gym.dtype not in (torch.float32, xs.dtype):
             gym = gym.float()
         # fp16 activations: the gradient of the raw time step is the smallest quantity of the whole pass (measured: most of it
         # below fp16's normal range even under a loss scale of 2^16, 13 % relative error in d(dt_projs_weight), DESIGN §29),
         # and the kernel stores it in the activation dtype.  The scan backward therefore runs its fp32 form on the same values
-        # (graw comes out in fp32) and the two projections take the split passes of the fp32 mode; gu goes back to fp16.
-        wide = xs.dtype == torch.float16
-        if wide:
-            gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs.float(), xdbl, order, dtw, dtb, al, dsf, gym.float(),
-                                                               states=states, a_log=True, bc_partials=True)
-            gu = gu.to(xs.dtype)
-        else:
-            gu, graw, bpart, cpart, gpar = hip.ss2d_scan_bwd_cl(xs, xdbl, order, dtw, dtb, al, dsf, gym, states=states,
-                                                               a_log=True, bc_partials=True)
-        wide = wide or xs.dtype == torch.float32
+        # (_scan_bwd_graw32: graw comes out in fp32) and the two projections take the split passes of the fp32 mode.
+        scan_kw = dict(states=states, a_log=True, bc_partials=True) if n == 1 else dict(bc_partials=True)
+        gu, graw, bpart, cpart, gpar = _scan_bwd_graw32(xs, xdbl, order, dtw, dtb, a, dsf, gym, **scan_kw)
+        wide = graw.dtype == torch.float32
         cd = torch.bfloat16 if xs.dtype == torch.float32 else xs.dtype
-        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if wide else cd)
+        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if wide else cd, n)
         # the two per-direction projections on the (B,K,L,.) tensors as they are:
         #   d(dt_projs_weight)[k] = sum_{b,l} graw^T ranks   (TN, tramba_wgrad_cl with groups = K, batches = B)
         #   d(ranks)              = graw @ dt_w[k]           (tramba_rows_gemm_cl into the first R floats of every gseq row)
@@ -1542,23 +1538,23 @@ class _SS2DInnerCL(torch.autograd.Function):
             # (K, D, R8); a leaf's gradient, handed on as it is when no columns are cut and no cast follows: its slab sums
             # join the step's batched ones
             g_dtw = hip.wgrad_grouped_cl(graw, ranks, defer=ranks.shape[-1] == r and dtwdtype == torch.float32)
-            dtw_t = ctx.dtw_t            # (K, R, D): the shadow written after the optimizer step, when current
+            dtw_t = ctx.dtw_t
             if dtw_t is None:
-                dtw_t = torch.empty((k, r, d), dtype=cd, device=xs.device).copy_(dtw.transpose(1, 2))   # transpose + cast
+                dtw_t = dtw.transpose(1, 2).to(cd, memory_format=torch.contiguous_format)   # (K, R, D), transpose + cast: 1 launch
             hip.rows_gemm_cl(graw.view(b * k, l, d), dtw_t, gseq.view(b * k, l, rg), r)
-        else:   # fp32 validation mode: three passes on bf16 splits
+        else:   # graw in fp32 (fp32 validation mode, and fp16 activations: _scan_bwd_graw32): three passes on bf16 splits
             gh, gl = _split16(graw)
             rh, rl = _split16(ranks)
             wh, wl = _split16(dtw.transpose(1, 2).contiguous())                                    # (K, R, D)
             g_dtw = hip.wgrad_grouped_cl(gh, rh) + hip.wgrad_grouped_cl(gh, rl) + hip.wgrad_grouped_cl(gl, rh)
-            tmp = torch.empty_like(gseq)
             hip.rows_gemm_cl(gh.view(b * k, l, d), wh, gseq.view(b * k, l, rg), r)
+            # the fp32 `ranks` (B, K, L, R8 >= r) is dead from here on (only its splits were read): scratch of passes two and three
             for ga_, wa_ in ((gh, wl), (gl, wh)):
-                hip.rows_gemm_cl(ga_.view(b * k, l, d), wa_, tmp.view(b * k, l, rg), r)
-                gseq[..., :r] += tmp[..., :r]
+                hip.rows_gemm_cl(ga_.view(b * k, l, d), wa_, ranks.view(b * k, l, r8), r)
+                gseq[..., :r] += ranks[..., :r]
         if g_dtw.shape[-1] != r:
             g_dtw = g_dtw[..., :r].contiguous()
-        g_xd = hip.ss2d_bwd_assemble(gseq, order, r, xs.dtype).view(b * l, k * rg)        # spatial order, activation dtype
+        g_xd = hip.ss2d_bwd_assemble(gseq, order, r, xs.dtype, n).view(b * l, k * rg)     # spatial order, activation dtype
         gz = None
         if ctx.needs_input_grad[0]:
             t = _dgrad(g_xd, wa, ctx.wa_t).view(b, l, d)                                   # the x_proj branch's share
@@ -1566,90 +1562,8 @@ class _SS2DInnerCL(torch.autograd.Function):
         gxw = None
         if ctx.needs_input_grad[2]:
             if xs.dtype != torch.float32:
-                # the GEMM's rows are in the scan kernels' padded layout (K x RG rows: R ranks, pad, B, C, pad); the parameter
-                # keeps (K, R + 2, D): its row ranges are summed from the partial slabs straight into place
-                segs = [s_ for g in range(k) for s_ in ((g * rg, r), (g * rg + r8, 2))]
-                gxw = hip.wgrad_rows_cl(g_xd, xs.view(b * l, d), segs, defer=xwdtype == torch.float32).view(k, r + 2, d)
-                gxw = gxw.to(xwdtype)
-            else:
-                gp_ = _wgrad(g_xd, xs.view(b * l, d))[0].view(k, rg, d)
-                gxw = torch.cat((gp_[:, :r], gp_[:, r8:r8 + 2]), dim=1).to(xwdtype)
-        gp = hip.slab_sum(gpar, defer=ctx.par_f32)                                             # (3,K,D): contiguous planes, leaf gradients
-        return (gz, None, gxw, g_dtw.to(dtwdtype), gp[2].reshape(dtbshape), gp[0].reshape(alshape), gp[1].reshape(-1), None)
-
-
-class _SS2DInnerNCL(torch.autograd.Function):
-    """_SS2DInnerCL at d_state N = 2..16 (opt-in, ops.set_fused_dstate_training): same inputs with x_proj_weight (K,R+2N,D)
-    and A_logs (K*D,N), same launch sequence.  Forward: x_proj once in spatial order (GEMM, fp32 rows in the
-    [R8 ranks | B_0.. | C_0.. | pad] layout) -> A = -exp(A_logs) -> tramba_ss2d_scan_n_cl -> merge.  Backward:
-    tramba_ss2d_scan_n_bwd_cl (recomputes the states from the saved x, x_dbl rows and A; dB_n / dC_n as per-channel-tile
-    partials, dA_logs / dD / dbias as per-(batch, segment) slabs, no atomics) -> tramba_ss2d_bwd_prep_n_cl -> the two
-    per-direction projections -> tramba_ss2d_bwd_assemble_n_cl -> x_proj input gradient -> tramba_ss2d_merge_grad_cl.
-    Nothing that must survive from forward to backward lives in the per-stream scan workspace: only saved tensors."""
-
-    @staticmethod
-    def forward(ctx, z, xs, xw, dt_w, dt_b, a_logs, ds, order):
-        z, xs = z.contiguous(), xs.contiguous()
-        n = a_logs.shape[-1]
-        wa, _ = _xproj_padded(xw, xs.dtype, n)
-        xdbl = hip.linear_cl(xs, wa, out_dtype=torch.float32)
-        dtw, dtb = dt_w.detach().float().contiguous(), dt_b.detach().float().reshape(-1).contiguous()
-        dsf = ds.detach().float().contiguous()
-        a_neg = torch.exp(a_logs.detach().float().reshape(-1, n)).neg_()            # (K*D, N), vmamba.py:246
-        ys = hip.ss2d_scan_n_cl(xs, xdbl, order, dtw, dtb, a_neg, dsf, xs.dtype)
-        ctx.save_for_backward(z, xs, xdbl, dtw, dtb, a_neg, dsf, wa)
-        ctx.order = order
-        ent = _lowp_shadow.get(id(dt_w))
-        ctx.dtw_t = ent[3] if (ent is not None and ent[1] == dt_w._version and ent[2]() is dt_w
-                               and ent[3] is not None and ent[3].dtype == xs.dtype) else None
-        ctx.meta = (xw.dtype, xw.shape, dt_w.dtype, dt_b.shape, a_logs.shape)
-        ctx.par_f32 = dt_b.dtype == a_logs.dtype == ds.dtype == torch.float32
-        return hip.ss2d_merge_sum_cl(ys, order, xs.dtype)
-
-    @staticmethod
-    def backward(ctx, gym):
-        z, xs, xdbl, dtw, dtb, a_neg, dsf, wa = ctx.saved_tensors
-        order = ctx.order
-        xwdtype, xwshape, dtwdtype, dtbshape, alshape = ctx.meta
-        b, l, d = xs.shape
-        k, r, n = order.k, dtw.shape[-1], a_neg.shape[1]
-        rg = hip.ss2d_group_stride(r, n)
-        r8 = (r + 7) & ~7
-        gym = gym.contiguous()
-        if gym.dtype not in (torch.float32, xs.dtype):
-            gym = gym.float()
-        # fp16 activations: graw does not fit the activation dtype (see _SS2DInnerCL.backward, DESIGN §29): the scan backward
-        # runs its fp32 form on the same values, the projections take the split passes, gu goes back to fp16
-        gu, graw, bpart, cpart, gpar = _scan_bwd_graw32(xs, xdbl, order, dtw, dtb, a_neg, dsf, gym, bc_partials=True)
-        wide = graw.dtype == torch.float32
-        cd = torch.bfloat16 if xs.dtype == torch.float32 else xs.dtype
-        ranks, gseq = hip.ss2d_bwd_prep(xdbl, order, bpart, cpart, r, torch.float32 if wide else cd, n)
-        if not wide:
-            g_dtw = hip.wgrad_grouped_cl(graw, ranks, defer=ranks.shape[-1] == r and dtwdtype == torch.float32)
-            dtw_t = ctx.dtw_t            # (K, R, D): the shadow written after the optimizer step, when current
-            if dtw_t is None:
-                dtw_t = dtw.transpose(1, 2).to(cd).contiguous()
-            hip.rows_gemm_cl(graw.view(b * k, l, d), dtw_t, gseq.view(b * k, l, rg), r)
-        else:   # graw in fp32 (fp32 validation mode, and fp16 activations: _scan_bwd_graw32): three passes on bf16 splits
-            gh, gl = _split16(graw)
-            rh, rl = _split16(ranks)
-            wh, wl = _split16(dtw.transpose(1, 2).contiguous())                                    # (K, R, D)
-            g_dtw = hip.wgrad_grouped_cl(gh, rh) + hip.wgrad_grouped_cl(gh, rl) + hip.wgrad_grouped_cl(gl, rh)
-            tmp = torch.zeros_like(gseq)             # (validation mode only; the 16-bit path above allocates nothing here)
-            hip.rows_gemm_cl(gh.view(b * k, l, d), wh, gseq.view(b * k, l, rg), r)
-            for ga_, wa_ in ((gh, wl), (gl, wh)):
-                hip.rows_gemm_cl(ga_.view(b * k, l, d), wa_, tmp.view(b * k, l, rg), r)
-                gseq[..., :r] += tmp[..., :r]
-        if g_dtw.shape[-1] != r:
-            g_dtw = g_dtw[..., :r].contiguous()
-        g_xd = hip.ss2d_bwd_assemble(gseq, order, r, xs.dtype, n).view(b * l, k * rg)     # spatial order, activation dtype
-        gz = None
-        if ctx.needs_input_grad[0]:
-            t = _dgrad(g_xd, wa, None).view(b, l, d)                                       # the x_proj branch's share
-            gz = hip.ss2d_merge_grad_cl(gu, order, t, z)                                   # (merge(gu) + t) * silu'(z)
-        gxw = None
-        if ctx.needs_input_grad[2]:
-            if xs.dtype != torch.float32:
+                # the GEMM's rows are in the scan kernels' padded layout (K x RG rows: R ranks, pad, B_n, C_n, pad); the
+                # parameter keeps (K, R + 2N, D): its row ranges are summed from the partial slabs straight into place
                 segs = [s_ for g in range(k) for s_ in ((g * rg, r), (g * rg + r8, 2 * n))]
                 gxw = hip.wgrad_rows_cl(g_xd, xs.view(b * l, d), segs, defer=xwdtype == torch.float32).view(k, r + 2 * n, d)
                 gxw = gxw.to(xwdtype)
@@ -1657,10 +1571,10 @@ class _SS2DInnerNCL(torch.autograd.Function):
                 gp_ = _wgrad(g_xd, xs.view(b * l, d))[0].view(k, rg, d)
                 gxw = torch.cat((gp_[:, :r], gp_[:, r8:r8 + 2 * n]), dim=1).to(xwdtype)
         kd = k * d
-        gp = hip.slab_sum(gpar, defer=ctx.par_f32)              # [dA_logs (K*D, N) | dD | dbias]: contiguous leaf gradients
+        # [dA_logs (K*D, N) | dD | dbias]: contiguous leaf gradients (at N = 1 the three planes of the (3, K, D) table)
+        gp = hip.slab_sum(gpar, defer=ctx.par_f32).reshape(-1)
         return (gz, None, gxw, g_dtw.to(dtwdtype), gp[kd * (n + 1):].reshape(dtbshape), gp[:kd * n].reshape(alshape),
                 gp[kd * n:kd * (n + 1)], None)
-
 
 
 class SS2D(nn.Module):
@@ -1705,12 +1619,15 @@ class SS2D(nn.Module):
         self.Ds = D_init(d_inner, copies=k_group, merge=True)  # (K*D)
 
     # -- the two core paths -----------------------------------------------------------------
+    def _family_ok(self):
+        """what every fused core asks of the module: a built-in scan family with its own merge, K = k_group, dt_rank <= 64"""
+        return (self.dt_rank <= 64 and getattr(self.scan, "_tramba_family", None) is not None
+                and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
+                and self.scan._tramba_k == self.k_group)
+
     def _fused_ok(self, x):
         # d_state 2..16: the state-looped wave-segment scan (hip.ss2d_scan_n_cl, DESIGN section 26)
-        return (1 <= self.d_state <= 16 and self.dt_rank <= 64
-                and getattr(self.scan, "_tramba_family", None) is not None
-                and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
-                and self.scan._tramba_k == self.k_group
+        return (1 <= self.d_state <= 16 and self._family_ok()
                 and _infer(x, self.x_proj_weight, self.dt_projs_weight, self.A_logs))
 
     def _padded_x_proj(self, dtype):
@@ -1748,10 +1665,7 @@ class SS2D(nn.Module):
         return y.view(b, h, w, d)
 
     def _train_fused_ok(self, x):
-        return (x.is_cuda and self.d_state == 1 and self.dt_rank <= 64
-                and getattr(self.scan, "_tramba_family", None) is not None
-                and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
-                and self.scan._tramba_k == self.k_group)
+        return x.is_cuda and self.d_state == 1 and self._family_ok()
 
     def _core_train_cl(self, x):
         """Training path of forward_corev2 without leaving channels-last: x_proj once in spatial order (autograd
@@ -1789,13 +1703,8 @@ class SS2D(nn.Module):
 
     def _train_fused_n_ok(self, x):
         """d_state 2..16 on the fused training path: only with ops.set_fused_dstate_training(True)"""
-        if not (x.is_cuda and 2 <= self.d_state <= 16):
-            return False
         from . import ops
-        return (ops.get_fused_dstate_training() and self.dt_rank <= 64
-                and getattr(self.scan, "_tramba_family", None) is not None
-                and getattr(self.merge, "_tramba_family", None) == self.scan._tramba_family
-                and self.scan._tramba_k == self.k_group)
+        return x.is_cuda and 2 <= self.d_state <= 16 and ops.get_fused_dstate_training() and self._family_ok()
 
     def _train_path_ok(self, x):
         """the fused training path: built-in scan family, N = 1 (N = 2..16 when opted in), depth-wise conv present, autograd on"""
@@ -1812,9 +1721,8 @@ class SS2D(nn.Module):
         xi = _LinearTrainCL.apply(xn, self.in_proj.weight, self.in_proj.bias)
         z, xs = _DwConvActCL.apply(xi, self.conv2d.weight, self.conv2d.bias, hip.ACT_SILU)
         order = hip.scan_order(self.scan._tramba_family, h, w, xn.device)
-        inner = _SS2DInnerCL if self.d_state == 1 else _SS2DInnerNCL
-        ym = inner.apply(z.view(b, h * w, d), xs.view(b, h * w, d), self.x_proj_weight, self.dt_projs_weight,
-                         self.dt_projs_bias, self.A_logs, self.Ds, order)
+        ym = _SS2DInnerCL.apply(z.view(b, h * w, d), xs.view(b, h * w, d), self.x_proj_weight, self.dt_projs_weight,
+                                self.dt_projs_bias, self.A_logs, self.Ds, order)
         # out_norm and the GELU of vmamba.py:270 in one pass; out_proj's input-gradient GEMM carries the GELU's gradient
         _, yn, ya = _AddLayerNormCL.apply(ym.view(b, h, w, d), None, None, self.out_norm.weight, self.out_norm.bias,
                                           self.out_norm.eps, hip.ACT_GELU, False)
