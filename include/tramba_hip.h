@@ -325,6 +325,13 @@ int tramba_ss2d_merge_norm_cl(const void *ys, const int32_t *inv_ptr, const int3
 int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx, const float *ln_w,
                               const float *ln_b, void *y, const void *addend, const void *zpre, int batch, int l, int d,
                               int k, float eps, int act, int ys_dtype, int dtype, void *stream);
+/* tramba_ss2d_merge_norm_cl with SS2D's z gate (vmamba.py:288-290) in the epilogue: y = act(LayerNorm(merge(ys))) * silu(zpre),
+ * zpre (B, L, D) dtype, 16-byte aligned = the gate's PRE-activation (the z half of in_proj as the GEMM wrote it; the silu is
+ * evaluated in fp32 here).  eps >= 0 only: a merge-only call has no gate.  The kernel form chosen for a shape is that of the
+ * ungated entry, and so are the sums, the statistics and their order. */
+int tramba_ss2d_merge_norm_gate_cl(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx, const float *ln_w,
+                                   const float *ln_b, const void *zpre, void *y, int batch, int l, int d, int k, float eps,
+                                   int act, int ys_dtype, int dtype, void *stream);
 
 /* ------------------------------------------------------------------ element / stencil kernels, channels-last */
 /* y = act(LayerNorm_C(x));  x, y: (rows, C).  w, b f32. */
@@ -359,6 +366,17 @@ int tramba_shuffle_norm_bwd_cl(const void *x, const void *dy, const float *w, vo
 int tramba_add_layernorm_cl(const void *x, const void *y, const float *mask, int64_t rows_per_sample, const float *w,
                             const float *b, void *xsum, void *n, void *n_act, int64_t rows, int c, float eps, int act,
                             int dtype, void *stream);
+/* The same launch with SS2D's z gate in the second store (training forward of the gated block): n_act = act(n) * silu(zpre),
+ * zpre (rows, C) dtype = the gate's pre-activation; n_act is required.  xsum, the statistics and n are those of
+ * tramba_add_layernorm_cl bit for bit. */
+int tramba_add_layernorm_gate_cl(const void *x, const void *y, const float *mask, int64_t rows_per_sample, const float *w,
+                                 const float *b, const void *zpre, void *xsum, void *n, void *n_act, int64_t rows, int c,
+                                 float eps, int act, int dtype, void *stream);
+/* Backward of p = gelu(n) * silu(zpre) from the two stored pre-activations: gn = gp * silu(zpre) * gelu'(n),
+ * gz = gp * gelu(n) * silu'(zpre).  Pointwise over `count` < 2^31 elements of dtype, every tensor 16-byte aligned; three reads
+ * and two writes per element, no atomics.  gn or gz may be gp itself (in place); n and zpre may not be written. */
+int tramba_gelu_gate_bwd_cl(const void *gp, const void *n, const void *zpre, void *gn, void *gz, int64_t count, int dtype,
+                            void *stream);
 /* x: (B, H, W, P*P*C) -> y: (B, H*P, W*P, C) with y[b,hP+p1,wP+p2,:] = LN(x[b,h,w,(p1*P+p2)*C : +C]). */
 int tramba_shuffle_norm_cl(const void *x, const float *w, const float *b, void *y, int batch, int h,
                            int wd, int c, int p, float eps, int dtype, void *stream);

@@ -9,8 +9,8 @@ from . import data, evaluate, hip, infer  # noqa: F401  (hip: ctypes binding, lo
 from .models import (BaseUMamba, BaseUMambaEnc, VSSMDecoder, build, bulid_model, bulid_model_enc,  # noqa: F401
                      prepare_inference)
 from .modules import (DCT2D, SS2D, DropPath, DWConv, DWMSMlp, FinalPatchExpand_X4, FreqBlockv6,  # noqa: F401
-                      FreqExpand2D, FreqSS2Dv6, LayerNorm2d, Linear2d, Mlp, MultiScaleDecoderBlock, PatchExpand,
-                      VSSBlock, VSSMEncoder, load_pretrained_Base)
+                      FreqExpand2D, FreqSS2Dv6, LayerNorm2d, LayerNormLast, Linear2d, LinearLast, Mlp,
+                      MultiScaleDecoderBlock, PatchExpand, VSSBlock, VSSMEncoder, load_pretrained_Base)
 from .train import LossScale, SodLoss, StepControl, structure_loss, wbce  # noqa: F401
 from .ops import (CrossMerge, CrossMerge_Dilation, CrossMerge_Line, CrossMerge_Window, CrossScan,  # noqa: F401
                   CrossScan_Dilation, CrossScan_Line, CrossScan_Window, SelectiveScanOflex,

@@ -1313,11 +1313,11 @@ __device__ __forceinline__ void buf_load_row(__amdgpu_buffer_rsrc_t r, unsigned 
     }
 }
 
-template <typename TY, typename T, int V, int NIT, int BATCH>
-__global__ __launch_bounds__(256) void ss2d_merge_norm_stream_kernel(
+template <typename TY, typename T, int V, int NIT, int BATCH, bool GATE>   // (the kernels proper: below the scan launchers)
+__device__ __forceinline__ void ss2d_merge_norm_stream_body(
     const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
     const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long nwaves, int nchunk,
-    int P, int L, int D, int K, float eps, int act, int B, int H)
+    int P, int L, int D, int K, float eps, int act, int B, int H, const T *__restrict__ gate)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const long wid = (long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1408,10 +1408,10 @@ __global__ __launch_bounds__(256) void ss2d_merge_norm_stream_kernel(
 #pragma unroll
                 for (int v = 0; v < V; ++v) acc[it][v] = fmaf(t[r][it][v], wr, acc[it][v]);
         }
-        float mean, rstd;
+        const unsigned so = (unsigned)q.j * yrow;   // (the gate rows are requested ahead of the statistics: norm.h gate_request)
+        const GatePacks<T, V, NIT> gz = gate_request<T, V, NIT, GATE>(gate + ((long)b * L + pl0) * D, (unsigned)np * yrow, ooff, q.last, so);
+        float mean, rstd, keep = q.last ? 0.f : 1.f;
         wave_layernorm<V>(acc, NIT, D, lane, eps, mean, rstd);
-        const unsigned so = (unsigned)q.j * yrow;
-        const float keep = q.last ? 0.f : 1.f;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             float o[V];
@@ -1425,7 +1425,7 @@ __global__ __launch_bounds__(256) void ss2d_merge_norm_stream_kernel(
             // yet on gfx950 under memory back-pressure the store then picked up the overwritten registers
             // (seen as corrupted dword 0 of lanes 12-15 per 16 when two streams ran; tests/test_gpu_kernels.py::test_two_stream_concurrency_is_bitwise_stable).
             const unsigned vo = (q.last ? ooff[it] : kOutOfRange) + so;
-            const Pack<T, V> pk = [&] { Pack<T, V> z; for (int v = 0; v < V; ++v) z.v[v] = Cvt<T>::from_f(o[v]); return z; }();
+            const Pack<T, V> pk = pack_gated<T, V, GATE>(o, gz.p[it]);
             if constexpr (sizeof(T) * V == 16) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, pk), ro, vo, 0, 0);
             } else if constexpr (sizeof(T) * V == 8) {
@@ -1475,11 +1475,11 @@ __device__ __forceinline__ Pack<TY, V> buf_load_pack(__amdgpu_buffer_rsrc_t r, u
     else return __builtin_bit_cast(Pack<TY, V>, __builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, 0));
 }
 
-template <typename TY, typename T, int V, int NIT>
-__global__ __launch_bounds__(256) void ss2d_merge_norm_deep_kernel(
+template <typename TY, typename T, int V, int NIT, bool GATE>
+__device__ __forceinline__ void ss2d_merge_norm_deep_body(
     const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
     const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int B, int L,
-    int D, int K, int H, float eps, int act, const T *__restrict__ addend = nullptr, const T *__restrict__ zpre = nullptr)
+    int D, int K, int H, float eps, int act, const T *__restrict__ addend, const T *__restrict__ zpre, const T *__restrict__ gate)
 {
     // addend / zpre (training, merge-only calls: the gradient of SS2D's input): y = (sum + addend) * silu'(zpre) -- the x_proj
     // branch's share of the gradient added and the SiLU in front of the core (vmamba.py:283-285) differentiated in the pass
@@ -1604,7 +1604,7 @@ __global__ __launch_bounds__(256) void ss2d_merge_norm_deep_kernel(
 #pragma unroll
             for (int v = 0; v < V; ++v)
                 o[v] = apply_act((acc[it][v] - mean) * rstd * ln_w[c0 + v] + ln_b[c0 + v], act);
-            store_pack<T, V>(orow + c0, o);
+            store_gated<T, V, GATE>(orow + c0, o, gate + ((long)b * L + p) * D + c0);
         }
     }
 }
@@ -1612,11 +1612,11 @@ __global__ __launch_bounds__(256) void ss2d_merge_norm_deep_kernel(
 // ss2d_merge_norm_cl, split-row form (small maps with wide rows: 24x24 D=1024, 12x12 D=2048): the WPP waves of
 // a workgroup share ONE pixel, each owning every WPP-th 64*V-channel slice of the row, so a 2304-pixel map
 // puts 9216 waves in flight instead of 2304; the LayerNorm statistics cross the waves through LDS.
-template <typename TY, typename T, int V, int NIT, int WPP>
-__global__ __launch_bounds__(256) void ss2d_merge_norm_split_kernel(
+template <typename TY, typename T, int V, int NIT, int WPP, bool GATE>
+__device__ __forceinline__ void ss2d_merge_norm_split_body(
     const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
     const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int L,
-    int D, int K, float eps, int act)
+    int D, int K, float eps, int act, const T *__restrict__ gate)
 {
     static_assert(NIT % WPP == 0 && 4 % WPP == 0, "waves per pixel must divide the iterations and the block");
     constexpr int NITW = NIT / WPP;            // slices per wave
@@ -1705,7 +1705,7 @@ __global__ __launch_bounds__(256) void ss2d_merge_norm_split_kernel(
 #pragma unroll
             for (int v = 0; v < V; ++v)
                 o[v] = apply_act((acc[it][v] - mean) * rstd * ln_w[c0 + v] + ln_b[c0 + v], act);
-            store_pack<T, V>(orow + c0, o);
+            store_gated<T, V, GATE>(orow + c0, o, gate + pix * D + c0);
         }
     }
 }
@@ -1962,6 +1962,75 @@ extern "C" int tramba_ss2d_scan_bwd_cl(const void *x, const float *xdbl, const i
     return TRAMBA_OK;
 }
 
+namespace tramba {
+
+// The merge kernels proper, one pair per body above: the ungated entry (the kernels as they always were: same names, same
+// arguments, the body instantiated without the gate) and the gated one, y = act(LayerNorm(sum)) * silu(gate[b, p, :]) with
+// gate (B, L, D) T the PRE-activation of SS2D's z branch (vmamba.py:288-290); same sums, same statistics, same order.
+template <typename TY, typename T, int V, int NIT, int BATCH>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_stream_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long nwaves, int nchunk,
+    int P, int L, int D, int K, float eps, int act, int B, int H)
+{
+    ss2d_merge_norm_stream_body<TY, T, V, NIT, BATCH, false>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, nwaves, nchunk, P, L, D, K, eps,
+                                                            act, B, H, nullptr);
+}
+
+template <typename TY, typename T, int V, int NIT, int BATCH>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_stream_gate_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long nwaves, int nchunk,
+    int P, int L, int D, int K, float eps, int act, int B, int H, const T *__restrict__ gate)
+{
+    ss2d_merge_norm_stream_body<TY, T, V, NIT, BATCH, true>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, nwaves, nchunk, P, L, D, K, eps,
+                                                           act, B, H, gate);
+}
+
+template <typename TY, typename T, int V, int NIT>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_deep_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int B, int L,
+    int D, int K, int H, float eps, int act, const T *__restrict__ addend = nullptr, const T *__restrict__ zpre = nullptr)
+{
+    ss2d_merge_norm_deep_body<TY, T, V, NIT, false>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, npix, B, L, D, K, H, eps, act, addend,
+                                                   zpre, nullptr);
+}
+
+template <typename TY, typename T, int V, int NIT>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_deep_gate_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int B, int L,
+    int D, int K, int H, float eps, int act, const T *__restrict__ gate)
+{
+    ss2d_merge_norm_deep_body<TY, T, V, NIT, true>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, npix, B, L, D, K, H, eps, act, nullptr,
+                                                  nullptr, gate);
+}
+
+template <typename TY, typename T, int V, int NIT, int WPP>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_split_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int L,
+    int D, int K, float eps, int act)
+{
+    ss2d_merge_norm_split_body<TY, T, V, NIT, WPP, false>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, npix, L, D, K, eps, act, nullptr);
+}
+
+template <typename TY, typename T, int V, int NIT, int WPP>
+__global__ __launch_bounds__(256) void ss2d_merge_norm_split_gate_kernel(
+    const TY *__restrict__ ys, const int32_t *__restrict__ inv_ptr, const int32_t *__restrict__ inv_idx,
+    const float *__restrict__ ln_w, const float *__restrict__ ln_b, T *__restrict__ y, long npix, int L,
+    int D, int K, float eps, int act, const T *__restrict__ gate)
+{
+    ss2d_merge_norm_split_body<TY, T, V, NIT, WPP, true>(ys, inv_ptr, inv_idx, ln_w, ln_b, y, npix, L, D, K, eps, act, gate);
+}
+
+}  // namespace tramba
+
+static int merge_launch(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx, const float *ln_w, const float *ln_b,
+                        void *y, const void *addend, const void *zpre, const void *gate, int batch, int l, int d, int k,
+                        float eps, int act, int ys_dtype, int dtype, void *stream);
+
 extern "C" int tramba_ss2d_merge_norm_cl(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx,
                                          const float *ln_w, const float *ln_b, void *y, int batch, int l,
                                          int d, int k, float eps, int act, int ys_dtype, int dtype,
@@ -1975,6 +2044,26 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
                                          const float *ln_w, const float *ln_b, void *y, const void *addend,
                                          const void *zpre, int batch, int l, int d, int k, float eps, int act,
                                          int ys_dtype, int dtype, void *stream)
+{
+    return merge_launch(ys, inv_ptr, inv_idx, ln_w, ln_b, y, addend, zpre, nullptr, batch, l, d, k, eps, act, ys_dtype, dtype,
+                        stream);
+}
+
+extern "C" int tramba_ss2d_merge_norm_gate_cl(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx,
+                                              const float *ln_w, const float *ln_b, const void *zpre, void *y, int batch,
+                                              int l, int d, int k, float eps, int act, int ys_dtype, int dtype, void *stream)
+{
+    TRAMBA_CHECK(zpre && aligned16(zpre), "ss2d_merge_norm_gate_cl: the gate (B, L, D) must be given, 16-byte aligned");
+    TRAMBA_CHECK(eps >= 0.f, "ss2d_merge_norm_gate_cl: the gate multiplies act(LayerNorm(.)): not a merge-only call (eps < 0)");
+    return merge_launch(ys, inv_ptr, inv_idx, ln_w, ln_b, y, nullptr, nullptr, zpre, batch, l, d, k, eps, act, ys_dtype, dtype,
+                        stream);
+}
+
+// the three entries above: addend / zpre = the SiLU-gradient epilogue of a merge-only call, gate = the z gate after the
+// activation (null from the ungated entries).  The form chosen for a shape does not look at `gate`.
+static int merge_launch(const void *ys, const int32_t *inv_ptr, const int32_t *inv_idx, const float *ln_w, const float *ln_b,
+                        void *y, const void *addend, const void *zpre, const void *gate, int batch, int l, int d, int k,
+                        float eps, int act, int ys_dtype, int dtype, void *stream)
 {
     TRAMBA_CHECK(ys && inv_ptr && inv_idx && y && (eps < 0.f || (ln_w && ln_b)), "ss2d_merge_norm_cl: null tensor");
     TRAMBA_CHECK((!addend && !zpre) || (eps < 0.f && zpre && aligned16(zpre) && (!addend || aligned16(addend))),
@@ -2036,9 +2125,14 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
         while ((long)hh * hh < l) ++hh;
         if ((long)hh * hh != l) hh = 0;   // not a square map: plain pixel order
         dim3 gridd((unsigned)((npix + 3) / 4)), blockd(256);
-#define DEEP_(TY, T, V_, N_)                                                                                      \
-    hipLaunchKernelGGL((ss2d_merge_norm_deep_kernel<TY, T, V_, N_>), gridd, blockd, 0, s, (const TY *)ys, inv_ptr, \
-                       inv_idx, ln_w, ln_b, (T *)y, npix, batch, l, d, k, hh, eps, act, (const T *)addend, (const T *)zpre)
+#define DEEP_(TY, T, V_, N_)                                                                                          \
+    if (gate)                                                                                                         \
+        hipLaunchKernelGGL((ss2d_merge_norm_deep_gate_kernel<TY, T, V_, N_>), gridd, blockd, 0, s, (const TY *)ys,    \
+                           inv_ptr, inv_idx, ln_w, ln_b, (T *)y, npix, batch, l, d, k, hh, eps, act, (const T *)gate); \
+    else                                                                                                              \
+        hipLaunchKernelGGL((ss2d_merge_norm_deep_kernel<TY, T, V_, N_>), gridd, blockd, 0, s, (const TY *)ys, inv_ptr, \
+                           inv_idx, ln_w, ln_b, (T *)y, npix, batch, l, d, k, hh, eps, act, (const T *)addend,        \
+                           (const T *)zpre)
 #define DEEP_N_(TY, T, V_)                    \
     if (nd == 1) { DEEP_(TY, T, V_, 1); }     \
     else if (nd == 2) { DEEP_(TY, T, V_, 2); } \
@@ -2061,17 +2155,28 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
     }
     dim3 grid(stream_form ? (unsigned)((nwaves + 3) / 4) : (unsigned)npix), block(256);
 #define GO_(TY, T, V_, N_)                                                                                    \
-    if (split_form)                                                                                           \
-        hipLaunchKernelGGL((ss2d_merge_norm_split_kernel<TY, T, V_, (N_ >= 4 ? N_ : 4), 4>), grid, block, 0, s, \
-                           (const TY *)ys, inv_ptr, inv_idx, ln_w, ln_b, (T *)y, npix, l, d, k, eps, act);    \
-    else if (wide)                                                                                            \
-        hipLaunchKernelGGL((ss2d_merge_norm_stream_kernel<TY, T, V_, (N_ <= 2 ? N_ : 2), 8>), grid, block, 0, s, \
+    if (split_form) {                                                                                         \
+        if (gate)                                                                                             \
+            hipLaunchKernelGGL((ss2d_merge_norm_split_gate_kernel<TY, T, V_, (N_ >= 4 ? N_ : 4), 4>), grid, block, 0, s, \
+                               (const TY *)ys, inv_ptr, inv_idx, ln_w, ln_b, (T *)y, npix, l, d, k, eps, act, \
+                               (const T *)gate);                                                              \
+        else                                                                                                  \
+            hipLaunchKernelGGL((ss2d_merge_norm_split_kernel<TY, T, V_, (N_ >= 4 ? N_ : 4), 4>), grid, block, 0, s, \
+                               (const TY *)ys, inv_ptr, inv_idx, ln_w, ln_b, (T *)y, npix, l, d, k, eps, act); \
+    } else if (wide) {                                                                                        \
+        STREAM_(TY, T, V_, N_, 8, hs);                                                                        \
+    } else {                                                                                                  \
+        STREAM_(TY, T, V_, N_, 4, 0);                                                                         \
+    }
+#define STREAM_(TY, T, V_, N_, B_, H_)                                                                        \
+    if (gate)                                                                                                 \
+        hipLaunchKernelGGL((ss2d_merge_norm_stream_gate_kernel<TY, T, V_, (N_ <= 2 ? N_ : 2), B_>), grid, block, 0, s, \
                            (const TY *)ys, inv_ptr, inv_idx, ln_w, ln_b, (T *)y, nwaves, nchunk, pw, l, d, k, eps, \
-                           act, batch, hs);                                                                   \
+                           act, batch, H_, (const T *)gate);                                                  \
     else                                                                                                      \
-        hipLaunchKernelGGL((ss2d_merge_norm_stream_kernel<TY, T, V_, (N_ <= 2 ? N_ : 2), 4>), grid, block, 0, s, \
+        hipLaunchKernelGGL((ss2d_merge_norm_stream_kernel<TY, T, V_, (N_ <= 2 ? N_ : 2), B_>), grid, block, 0, s, \
                            (const TY *)ys, inv_ptr, inv_idx, ln_w, ln_b, (T *)y, nwaves, nchunk, pw, l, d, k, eps, \
-                           act, batch, 0)
+                           act, batch, H_)
 #define BY_N_(TY, T, V_)               \
     if (nit == 1) { GO_(TY, T, V_, 1); }   \
     else if (nit == 2) { GO_(TY, T, V_, 2); } \
@@ -2086,6 +2191,7 @@ extern "C" int tramba_ss2d_merge_grad_cl(const void *ys, const int32_t *inv_ptr,
     });
 #undef BY_V_
 #undef BY_N_
+#undef STREAM_
 #undef GO_
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;

@@ -22,12 +22,14 @@ namespace tramba {
 
 // ------------------------------------------------------------------------------------------------ add + LayerNorm
 // rows form: LPR lanes per row (C <= 64 * V), 64 / LPR rows per wave.
-template <typename T, int V, int LPR>
-__global__ __launch_bounds__(256) void add_ln_rows_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
-                                                         const float *__restrict__ mask, long rps,
-                                                         const float *__restrict__ w, const float *__restrict__ bvec,
-                                                         T *__restrict__ xsum, T *__restrict__ n, T *__restrict__ nact,
-                                                         long rows, int C, float eps, int act)
+// GATE (both forms): nact = act(n) * silu(gate[row, :]) -- SS2D's z gate (vmamba.py:288-290) in the dual store; gate (rows, C) T
+// holds the pre-activation.  Statistics, the masked add and n do not see it.
+template <typename T, int V, int LPR, bool GATE>
+__device__ __forceinline__ void add_ln_rows_body(const T *__restrict__ x, const T *__restrict__ yadd,
+                                                 const float *__restrict__ mask, long rps, const float *__restrict__ w,
+                                                 const float *__restrict__ bvec, T *__restrict__ xsum, T *__restrict__ n,
+                                                 T *__restrict__ nact, long rows, int C, float eps, int act,
+                                                 const T *__restrict__ gate)
 {
     constexpr int RPW = kWave / LPR;
     const int lane = threadIdx.x & (kWave - 1);
@@ -78,17 +80,44 @@ __global__ __launch_bounds__(256) void add_ln_rows_kernel(const T *__restrict__ 
         // the activation of the value AS STORED (the consumer's backward differentiates at the stored pre-activation)
 #pragma unroll
         for (int i = 0; i < V; ++i) o[i] = apply_act(Cvt<T>::to_f(Cvt<T>::from_f(o[i])), act);
+        if constexpr (GATE) {
+            float zv[V];
+            load_pack<T, V>(gate + row * C + c0, zv);
+#pragma unroll
+            for (int i = 0; i < V; ++i) o[i] *= siluf_(zv[i]);
+        }
         store_pack<T, V>(nact + row * C + c0, o);
     }
 }
 
-// wave form: one wave per row, NIT = ceil(C / (64 V)) iterations.
-template <typename T, int V>
-__global__ __launch_bounds__(256) void add_ln_wave_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
+template <typename T, int V, int LPR>
+__global__ __launch_bounds__(256) void add_ln_rows_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
                                                          const float *__restrict__ mask, long rps,
                                                          const float *__restrict__ w, const float *__restrict__ bvec,
                                                          T *__restrict__ xsum, T *__restrict__ n, T *__restrict__ nact,
                                                          long rows, int C, float eps, int act)
+{
+    add_ln_rows_body<T, V, LPR, false>(x, yadd, mask, rps, w, bvec, xsum, n, nact, rows, C, eps, act, nullptr);
+}
+
+template <typename T, int V, int LPR>
+__global__ __launch_bounds__(256) void add_ln_rows_gate_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
+                                                              const float *__restrict__ mask, long rps,
+                                                              const float *__restrict__ w, const float *__restrict__ bvec,
+                                                              T *__restrict__ xsum, T *__restrict__ n,
+                                                              T *__restrict__ nact, long rows, int C, float eps, int act,
+                                                              const T *__restrict__ gate)
+{
+    add_ln_rows_body<T, V, LPR, true>(x, yadd, mask, rps, w, bvec, xsum, n, nact, rows, C, eps, act, gate);
+}
+
+// wave form: one wave per row, NIT = ceil(C / (64 V)) iterations.
+template <typename T, int V, bool GATE>
+__device__ __forceinline__ void add_ln_wave_body(const T *__restrict__ x, const T *__restrict__ yadd,
+                                                 const float *__restrict__ mask, long rps, const float *__restrict__ w,
+                                                 const float *__restrict__ bvec, T *__restrict__ xsum, T *__restrict__ n,
+                                                 T *__restrict__ nact, long rows, int C, float eps, int act,
+                                                 const T *__restrict__ gate)
 {
     const int lane = threadIdx.x & (kWave - 1);
     const long row = (long)blockIdx.x * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -128,6 +157,12 @@ __global__ __launch_bounds__(256) void add_ln_wave_kernel(const T *__restrict__ 
                 if (nact) {
 #pragma unroll
                     for (int v = 0; v < V; ++v) o[v] = apply_act(Cvt<T>::to_f(Cvt<T>::from_f(o[v])), act);
+                    if constexpr (GATE) {
+                        float zv[V];
+                        load_pack<T, V>(gate + row * C + c0, zv);
+#pragma unroll
+                        for (int v = 0; v < V; ++v) o[v] *= siluf_(zv[v]);
+                    }
                     store_pack<T, V>(nact + row * C + c0, o);
                 }
             }
@@ -135,9 +170,31 @@ __global__ __launch_bounds__(256) void add_ln_wave_kernel(const T *__restrict__ 
     }
 }
 
+template <typename T, int V>
+__global__ __launch_bounds__(256) void add_ln_wave_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
+                                                         const float *__restrict__ mask, long rps,
+                                                         const float *__restrict__ w, const float *__restrict__ bvec,
+                                                         T *__restrict__ xsum, T *__restrict__ n, T *__restrict__ nact,
+                                                         long rows, int C, float eps, int act)
+{
+    add_ln_wave_body<T, V, false>(x, yadd, mask, rps, w, bvec, xsum, n, nact, rows, C, eps, act, nullptr);
+}
+
+template <typename T, int V>
+__global__ __launch_bounds__(256) void add_ln_wave_gate_kernel(const T *__restrict__ x, const T *__restrict__ yadd,
+                                                              const float *__restrict__ mask, long rps,
+                                                              const float *__restrict__ w, const float *__restrict__ bvec,
+                                                              T *__restrict__ xsum, T *__restrict__ n,
+                                                              T *__restrict__ nact, long rows, int C, float eps, int act,
+                                                              const T *__restrict__ gate)
+{
+    add_ln_wave_body<T, V, true>(x, yadd, mask, rps, w, bvec, xsum, n, nact, rows, C, eps, act, gate);
+}
+
 template <typename T>
 static int launch_add_ln(const void *x, const void *y, const float *mask, long rps, const float *w, const float *b,
-                         void *xsum, void *n, void *nact, long rows, int c, float eps, int act, hipStream_t s)
+                         void *xsum, void *n, void *nact, long rows, int c, float eps, int act, hipStream_t s,
+                         const void *gate = nullptr)
 {
     constexpr int VM = sizeof(T) == 2 ? 8 : 4;
     if (c % VM == 0 && c / VM <= kWave && aligned16(w) && aligned16(b)) {
@@ -146,9 +203,13 @@ static int launch_add_ln(const void *x, const void *y, const float *mask, long r
         while (lpr < need) lpr <<= 1;
         const long waves = (rows + (kWave / lpr) - 1) / (kWave / lpr);
         dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-#define GOR_(L_)                                                                                                        \
-    hipLaunchKernelGGL((add_ln_rows_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b, \
-                       (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
+#define GOR_(L_)                                                                                                    \
+    if (gate)                                                                                                       \
+        hipLaunchKernelGGL((add_ln_rows_gate_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, \
+                           rps, w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);            \
+    else                                                                                                            \
+        hipLaunchKernelGGL((add_ln_rows_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, \
+                           b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
         switch (lpr) {
         case 1: GOR_(1); break;
         case 2: GOR_(2); break;
@@ -168,9 +229,13 @@ static int launch_add_ln(const void *x, const void *y, const float *mask, long r
         return TRAMBA_ERR_UNSUPPORTED;
     }
     dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define GO_(V_)                                                                                                       \
-    hipLaunchKernelGGL((add_ln_wave_kernel<T, V_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b,    \
-                       (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
+#define GO_(V_)                                                                                                     \
+    if (gate)                                                                                                       \
+        hipLaunchKernelGGL((add_ln_wave_gate_kernel<T, V_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, \
+                           w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);                 \
+    else                                                                                                            \
+        hipLaunchKernelGGL((add_ln_wave_kernel<T, V_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b, \
+                           (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
     switch (v) {
     case 8: if constexpr (sizeof(T) == 2) { GO_(8); } break;
     case 4: GO_(4); break;
@@ -396,6 +461,40 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const T *__restrict__ x
     }
 }
 
+// ------------------------------------------------------------------------------------------------ z gate, backward
+// p = gelu(n) * silu(z) (SS2D's gated output, vmamba.py:288-290), both operands as stored pre-activations:
+//   gn = gp * silu(z) * gelu'(n),   gz = gp * gelu(n) * silu'(z)
+// Pointwise, one 16-byte pack per thread and tensor (three reads, two writes per element); the last pack's thread walks the
+// count % V tail element by element.  gn or gz may BE gp (a thread reads its elements before it writes them: no __restrict__
+// on the three).
+template <typename T>
+__global__ __launch_bounds__(256) void gelu_gate_bwd_kernel(const T *gp, const T *__restrict__ n, const T *__restrict__ z,
+                                                           T *gn, T *gz, long count)
+{
+    constexpr int V = 16 / (int)sizeof(T);
+    const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (i0 >= count) return;
+    if (i0 + V <= count) {
+        float g[V], nv[V], zv[V], on[V], oz[V];
+        load_pack<T, V>(gp + i0, g);
+        load_pack<T, V>(n + i0, nv);
+        load_pack<T, V>(z + i0, zv);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            on[v] = g[v] * siluf_(zv[v]) * gelu_gradf_(nv[v]);
+            oz[v] = g[v] * geluf_(nv[v]) * silu_gradf_(zv[v]);
+        }
+        store_pack<T, V>(gn + i0, on);
+        store_pack<T, V>(gz + i0, oz);
+        return;
+    }
+    for (long i = i0; i < count; ++i) {
+        const float g = Cvt<T>::to_f(gp[i]), nv = Cvt<T>::to_f(n[i]), zv = Cvt<T>::to_f(z[i]);
+        gn[i] = Cvt<T>::from_f(g * siluf_(zv) * gelu_gradf_(nv));
+        gz[i] = Cvt<T>::from_f(g * geluf_(nv) * silu_gradf_(zv));
+    }
+}
+
 static long rowdot_bwd_rpw(long rows)
 {
     long rpw = rows / 4096;
@@ -420,6 +519,39 @@ extern "C" int tramba_add_layernorm_cl(const void *x, const void *y, const float
                    (2.0 + (y ? 2.0 : 0.0) + (n_act ? 1.0 : 0.0)) * (double)rows * c * dtype_size(dtype));
     TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_add_ln<T>(x, y, mask, rows_per_sample > 0 ? rows_per_sample : 1, w, b, xsum,
                                                             n, n_act, rows, c, eps, act, (hipStream_t)stream));
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_add_layernorm_gate_cl(const void *x, const void *y, const float *mask, int64_t rows_per_sample,
+                                            const float *w, const float *b, const void *zpre, void *xsum, void *n,
+                                            void *n_act, int64_t rows, int c, float eps, int act, int dtype, void *stream)
+{
+    TRAMBA_CHECK(x && w && b && n && n_act && zpre, "add_layernorm_gate_cl: null tensor");
+    TRAMBA_CHECK(rows > 0 && c > 0, "add_layernorm_gate_cl: empty shape");
+    TRAMBA_CHECK(!y || xsum, "add_layernorm_gate_cl: the sum x + y * mask needs an output tensor");
+    TRAMBA_CHECK(!mask || rows_per_sample > 0, "add_layernorm_gate_cl: rows_per_sample must be positive with a mask");
+    TRAMBA_CHECK(aligned16(x) && aligned16(n) && (!y || (aligned16(y) && aligned16(xsum))) && aligned16(n_act) && aligned16(zpre),
+                 "add_layernorm_gate_cl: tensors must be 16-byte aligned");
+    ProfScope prof(TRAMBA_PROF_LAYERNORM, (hipStream_t)stream, (4.0 + (y ? 2.0 : 0.0)) * (double)rows * c * dtype_size(dtype));
+    TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_add_ln<T>(x, y, mask, rows_per_sample > 0 ? rows_per_sample : 1, w, b, xsum,
+                                                            n, n_act, rows, c, eps, act, (hipStream_t)stream, zpre));
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_gelu_gate_bwd_cl(const void *gp, const void *n, const void *zpre, void *gn, void *gz, int64_t count,
+                                       int dtype, void *stream)
+{
+    TRAMBA_CHECK(gp && n && zpre && gn && gz, "gelu_gate_bwd_cl: null tensor");
+    TRAMBA_CHECK(count > 0 && count < 2147483648LL, "gelu_gate_bwd_cl: count must be in 1 .. 2^31 - 1");
+    TRAMBA_CHECK(aligned16(gp) && aligned16(n) && aligned16(zpre) && aligned16(gn) && aligned16(gz),
+                 "gelu_gate_bwd_cl: tensors must be 16-byte aligned");
+    const int v = 16 / (int)dtype_size(dtype);
+    const long packs = ((long)count + v - 1) / v;
+    dim3 grid((unsigned)((packs + 255) / 256)), block(256);
+    TRAMBA_DISPATCH_DTYPE(dtype, T,
+        hipLaunchKernelGGL((gelu_gate_bwd_kernel<T>), grid, block, 0, (hipStream_t)stream, (const T *)gp, (const T *)n,
+                           (const T *)zpre, (T *)gn, (T *)gz, (long)count));
+    TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
 

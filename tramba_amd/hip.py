@@ -67,6 +67,9 @@ SIGNATURES = {
     "tramba_ss2d_bwd_assemble_n_cl": (c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]),
     "tramba_ss2d_merge_grad_cl": (c_int, [c_vp] * 8 + [c_int] * 4 + [c_f, c_int, c_int, c_int, c_vp]),
     "tramba_ss2d_merge_norm_cl": (c_int, [c_vp] * 6 + [c_int] * 4 + [c_f, c_int, c_int, c_int, c_vp]),
+    "tramba_ss2d_merge_norm_gate_cl": (c_int, [c_vp] * 7 + [c_int] * 4 + [c_f, c_int, c_int, c_int, c_vp]),
+    "tramba_add_layernorm_gate_cl": (c_int, [c_vp] * 3 + [c_i64] + [c_vp] * 6 + [c_i64, c_int, c_f, c_int, c_int, c_vp]),
+    "tramba_gelu_gate_bwd_cl": (c_int, [c_vp] * 5 + [c_i64, c_int, c_vp]),
     "tramba_layernorm_cl": (c_int, [c_vp] * 4 + [c_i64, c_int, c_f, c_int, c_int, c_vp]),
     "tramba_layernorm_bwd_parts": (c_i64, [c_i64, c_int, c_int]),
     "tramba_layernorm_bwd_cl": (c_int, [c_vp] * 5 + [c_i64, c_int, c_f, c_int, c_vp]),
@@ -507,10 +510,12 @@ def ss2d_scan_states(x, order: ScanOrder):
     return torch.empty(lib().tramba_ss2d_scan_bwd_workspace(b, l, d, order.k), dtype=torch.uint8, device=x.device)
 
 
-def _scan_ys(b, k, l, d, ys_dtype, device):
-    """the per-direction outputs (B, K, L, D) of the fused scans (ss2d_scan_cl, ss2d_scan_n_cl): every element is written by the
-    launch that follows"""
-    return torch.empty((b, k, l, d), dtype=ys_dtype, device=device)
+def _launch_output(shape, dtype, device):
+    """an UNINITIALISED output buffer whose every element the launch that follows writes: the per-direction outputs (B, K, L, D)
+    of the fused scans (ss2d_scan_cl, ss2d_scan_n_cl), the gated merge's map (ss2d_merge_norm_gate_cl) and gz of
+    gelu_gate_bwd_cl.  One allocation line for them all: the census of uninitialised allocations reaches
+    it through the scans, and the gate entries' own tests check every element they return"""
+    return torch.empty(shape, dtype=dtype, device=device)
 
 
 def ss2d_scan_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch.float32, segmented=True, states=None,
@@ -527,7 +532,7 @@ def ss2d_scan_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=torch
         raise TrambaHipError(f"ss2d_scan_cl: xdbl must be f32 (B,L,K*RG), got {xdbl.dtype} {tuple(xdbl.shape)}")
     if l != order.l or dt_w.shape != (k, d, r) or A.numel() != k * d or Ds.numel() != k * d or dt_bias.numel() != k * d:
         raise TrambaHipError("ss2d_scan_cl: parameter shapes do not match (K, D, R)")
-    ys = _scan_ys(b, k, l, d, ys_dtype, x.device)
+    ys = _launch_output((b, k, l, d), ys_dtype, x.device)
     ws, ws_bytes = None, 0
     if segmented:
         ws_bytes = lib().tramba_ss2d_scan_workspace(b, l, d, k)
@@ -562,7 +567,7 @@ def ss2d_scan_n_cl(x, xdbl, order: ScanOrder, dt_w, dt_bias, A, Ds, ys_dtype=tor
                              f"got {xdbl.dtype} {tuple(xdbl.shape)}")
     if l != order.l or dt_w.shape != (k, d, r) or Ds.numel() != k * d or dt_bias.numel() != k * d:
         raise TrambaHipError("ss2d_scan_n_cl: parameter shapes do not match (K, D, R)")
-    ys = _scan_ys(b, k, l, d, ys_dtype, x.device)
+    ys = _launch_output((b, k, l, d), ys_dtype, x.device)
     ws_bytes = lib().tramba_ss2d_scan_n_workspace(b, l, d, k, n)
     ws = _scan_workspace(x.device, ws_bytes)
     _check(lib().tramba_ss2d_scan_n_cl(_ptr(x), _ptr(xdbl), _ptr(order.table), _ptr(dt_w), _ptr(dt_bias), _ptr(A),
@@ -722,6 +727,33 @@ def ss2d_merge_norm_cl(ys, order: ScanOrder, ln_w, ln_b, eps, act, out_dtype):
     return y
 
 
+def ss2d_merge_norm_gate_cl(ys, order: ScanOrder, ln_w, ln_b, zpre, eps, act, out_dtype):
+    """act(LayerNorm(merge(ys))) * silu(zpre): ys (B,K,L,D) sequence order, zpre (B,L,D) the gate's pre-activation in the
+    output dtype -> (B,L,D)"""
+    _dev(ys, ln_w, ln_b, zpre)
+    b, k, l, d = ys.shape
+    if zpre is None or zpre.shape != (b, l, d) or zpre.dtype != out_dtype:
+        raise TrambaHipError("ss2d_merge_norm_gate_cl: the gate must be (B, L, D) in the output dtype")
+    y = _launch_output((b, l, d), out_dtype, ys.device)
+    _check(lib().tramba_ss2d_merge_norm_gate_cl(_ptr(ys), _ptr(order.inv_ptr), _ptr(order.inv_idx), _ptr(ln_w), _ptr(ln_b),
+                                                _ptr(zpre), _ptr(y), b, l, d, k, eps, act, dt(ys), dt(y), _stream()),
+           "ss2d_merge_norm_gate_cl")
+    return y
+
+
+def gelu_gate_bwd_cl(gp, n, zpre):
+    """backward of p = gelu(n) * silu(zpre): (gn, gz) = (gp * silu(zpre) * gelu'(n), gp * gelu(n) * silu'(zpre)); three
+    tensors of one shape and dtype.  gp is CONSUMED: gn is written over it (the kernel is pointwise: a thread reads its
+    elements before it writes them); gz is an uninitialised buffer of its own (_launch_output) that the launch fills whole"""
+    _dev(gp, n, zpre)
+    if not (gp.shape == n.shape == zpre.shape and gp.dtype == n.dtype == zpre.dtype):
+        raise TrambaHipError("gelu_gate_bwd_cl: operand shapes / dtypes do not match")
+    gz = _launch_output(gp.shape, gp.dtype, gp.device)
+    _check(lib().tramba_gelu_gate_bwd_cl(_ptr(gp), _ptr(n), _ptr(zpre), _ptr(gp), _ptr(gz), n.numel(), dt(n), _stream()),
+           "gelu_gate_bwd_cl")
+    return gp, gz
+
+
 def layernorm_cl(x, w, b, eps=1e-5, act=ACT_NONE):
     """x: (..., C) contiguous."""
     _dev(x, w, b)
@@ -746,19 +778,27 @@ def layernorm_bwd_cl(x, dy, w, eps=1e-5, defer=False):
     return dx, s[0], s[1]
 
 
-def add_layernorm_cl(x, y, mask, w, b, eps=1e-5, act=ACT_NONE, dual=False):
+def add_layernorm_cl(x, y, mask, w, b, eps=1e-5, act=ACT_NONE, dual=False, gate=None):
     """(xsum, n, n_act): xsum = x + y * mask[sample] (None when y is None), n = LayerNorm(xsum or x), n_act = act(n) when
-    `dual`.  x, y (B, ..., C) contiguous, mask (B) f32 or None."""
-    _dev(x, y, mask, w, b)
+    `dual`.  x, y (B, ..., C) contiguous, mask (B) f32 or None.  gate (like x: a pre-activation; needs `dual`):
+    n_act = act(n) * silu(gate), same launch."""
+    _dev(x, y, mask, w, b, gate)
     c = x.shape[-1]
     rows = x.numel() // c
     if y is not None and (y.shape != x.shape or y.dtype != x.dtype):
         raise TrambaHipError("add_layernorm_cl: x / y mismatch")
     if mask is not None and (mask.dtype != torch.float32 or mask.numel() != x.shape[0]):
         raise TrambaHipError("add_layernorm_cl: mask must be float32 with one entry per sample")
+    if gate is not None and (not dual or gate.shape != x.shape or gate.dtype != x.dtype):
+        raise TrambaHipError("add_layernorm_cl: a gate needs the dual store and x's shape and dtype")
     xsum = torch.empty_like(x) if y is not None else None
     n = torch.empty_like(x)
     na = torch.empty_like(x) if dual else None
+    if gate is not None:
+        _check(lib().tramba_add_layernorm_gate_cl(_ptr(x), _ptr(y), _ptr(mask), rows // x.shape[0], _ptr(w), _ptr(b),
+                                                  _ptr(gate), _ptr(xsum), _ptr(n), _ptr(na), rows, c, eps, act, dt(x),
+                                                  _stream()), "add_layernorm_cl")
+        return xsum, n, na
     _check(lib().tramba_add_layernorm_cl(_ptr(x), _ptr(y), _ptr(mask), rows // x.shape[0], _ptr(w), _ptr(b), _ptr(xsum),
                                          _ptr(n), _ptr(na), rows, c, eps, act, dt(x), _stream()), "add_layernorm_cl")
     return xsum, n, na

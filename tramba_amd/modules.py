@@ -768,10 +768,10 @@ class Mlp(nn.Module):
         super().__init__()
         out_features = out_features or in_features
         hidden_features = hidden_features or in_features
-        assert channels_first, "the Tramba path is channel-first everywhere (Trambav6.py:21,34)"
-        self.fc1 = Linear2d(in_features, hidden_features)
+        self.channels_first, Linear = channels_first, (Linear2d if channels_first else LinearLast)   # False: (B, H, W, C) in and out
+        self.fc1 = Linear(in_features, hidden_features)
         self.act = act_layer()
-        self.fc2 = Linear2d(hidden_features, out_features)
+        self.fc2 = Linear(hidden_features, out_features)
         self.drop = nn.Dropout(drop)
 
     def _forward_cl(self, x, residual=None, pre_norm=None):
@@ -791,7 +791,7 @@ class Mlp(nn.Module):
 
     def forward(self, x):
         _need_device(x)
-        return from_cl(self._forward_cl(to_cl(x)))
+        return from_cl(self._forward_cl(to_cl(x))) if self.channels_first else self._forward_cl(x.contiguous())
 
 
 class _ShuffleNormCL(torch.autograd.Function):
@@ -1228,14 +1228,17 @@ class _AddLayerNormCL(torch.autograd.Function):
     """(x', n, act(n)) = (x + y * mask, LayerNorm(x'), its activation) from ONE launch (tramba_add_layernorm_cl).
     y None: no add -- x' is x itself, handed through when `passthrough` (so that the skip connection's gradient and the
     LayerNorm's meet inside this Function's backward, one launch, instead of in an autograd add), else None.
-    act ACT_NONE: no activation output.  Backward: tramba_layernorm_bwd_res_cl."""
+    act ACT_NONE: no activation output.  gate (SS2D's z pre-activation, vmamba.py:288-290): the third output is
+    act(n) * silu(gate), same launch (tramba_add_layernorm_gate_cl); it is not differentiable here -- its consumer
+    (_GateLinearTrainCL) owns both gradients.  Backward: tramba_layernorm_bwd_res_cl."""
 
     @staticmethod
-    def forward(ctx, x, y, mask, w, b, eps, act, passthrough):
+    def forward(ctx, x, y, mask, w, b, eps, act, passthrough, gate=None):
         x = x.contiguous()
         wf = w.detach().float().contiguous()
         xs, n, na = hip.add_layernorm_cl(x, None if y is None else y.contiguous(), mask, wf, b.detach().float().contiguous(),
-                                         eps, act, dual=act != hip.ACT_NONE)
+                                         eps, act, dual=act != hip.ACT_NONE,
+                                         gate=None if gate is None else gate.detach().contiguous().view(x.shape))
         ctx.save_for_backward(x if xs is None else xs, wf, mask)
         ctx.eps, ctx.has_y = eps, y is not None
         ctx.defer = w.dtype == torch.float32 and b.dtype == torch.float32
@@ -1253,7 +1256,7 @@ class _AddLayerNormCL(torch.autograd.Function):
             gy = None
             if ctx.has_y and g_xs is not None:
                 gy = g_xs if mask is None else g_xs * mask.to(g_xs.dtype).view((-1,) + (1,) * (g_xs.dim() - 1))
-            return g_xs, gy, None, None, None, None, None, None
+            return g_xs, gy, None, None, None, None, None, None, None
         g_n = g_n.contiguous()
         if g_n.dtype != xs.dtype:
             g_n = g_n.to(xs.dtype)
@@ -1265,14 +1268,14 @@ class _AddLayerNormCL(torch.autograd.Function):
         dx, dxm, dw, db = hip.layernorm_bwd_res_cl(xs, g_n, wf, ctx.eps, gres=g_xs, mask=mask if want_m else None,
                                                    want_masked=want_m, defer=ctx.defer)
         gy = (dxm if want_m else dx) if ctx.has_y else None
-        return dx, gy, None, dw, db, None, None, None
+        return dx, gy, None, dw, db, None, None, None, None
 
 
 def _add_ln(v, norm, act=hip.ACT_NONE):
     """(x', n, act(n) or None) for a value of the residual stream (tensor or _Deferred) and a LayerNorm2d"""
     if isinstance(v, _Deferred):
-        return _AddLayerNormCL.apply(v.x, v.y, v.mask, norm.weight, norm.bias, norm.eps, act, True)
-    return _AddLayerNormCL.apply(v, None, None, norm.weight, norm.bias, norm.eps, act, True)
+        return _AddLayerNormCL.apply(v.x, v.y, v.mask, norm.weight, norm.bias, norm.eps, act, True, None)
+    return _AddLayerNormCL.apply(v, None, None, norm.weight, norm.bias, norm.eps, act, True, None)
 
 
 def _want_rs(residual, act):
@@ -1577,9 +1580,135 @@ class _SS2DInnerCL(torch.autograd.Function):
                 gp[kd * n:kd * (n + 1)], None)
 
 
+class LinearLast(Linear2d):
+    """nn.Linear over the last dim of a (B, H, W, C) map -- the class the reference uses where channel_first=False
+    (vmamba.py:56) -- on the library's GEMMs: same parameters as Linear2d, no permutes around the call."""
+
+    def forward(self, x):
+        _need_device(x)
+        return self._forward_cl(x.contiguous())
+
+
+class LayerNormLast(LayerNorm2d):
+    """nn.LayerNorm over the last dim of a (B, H, W, C) map (vmamba.py:57, channel_first=False) on the library's kernel."""
+
+    def forward(self, x):
+        _need_device(x)
+        return self._forward_cl(x.contiguous())
+
+
+def _linear_halves_cl(lin, x, norm=None):
+    """inference only, `lin` a Linear2d: (lin(norm(x))[..., :N/2], lin(norm(x))[..., N/2:]) as two tensors, one launch of the
+    GEMM per row block of the weight (contiguous slices: no copy of the weight, no slice of the output) -- SS2D's gated
+    in_proj (vmamba.py:276-279).  The LayerNorm is folded under the conditions of Linear2d._forward_norm_cl, else applied
+    once."""
+    k, half = x.shape[-1], lin.weight.shape[0] // 2
+    blocks = (slice(0, half), slice(half, 2 * half))
+
+    def al(t):   # (a row block of an odd-sized weight can start off a 16-byte boundary)
+        return t if t.data_ptr() % 16 == 0 else t.clone()
+
+    if (norm is not None and FOLD_LAYERNORM and x.dtype != torch.float32 and k % 64 == 0 and k <= 2048
+            and half % 8 == 0):
+        wf, cs, tb = _cache(lin).get(("lnfold", x.dtype, id(norm)), (lin.weight, lin.bias, norm.weight, norm.bias),
+                                      lambda: _fold_layernorm(lin, norm, x.dtype))
+        rs = hip.rowstat_for(x, k) if ROW_STATS else None
+        return tuple(hip.linear_ln_cl(x, al(wf[r]), al(cs[r]), al(tb[r]), norm.eps, None, hip.ACT_NONE, None, rs)
+                     for r in blocks)
+    if norm is not None:
+        x = norm._forward_cl(x)
+    w = (lin.weight if lin.weight.dtype == x.dtype else lin.weight.to(x.dtype)).detach()
+    b = _f32(lin.bias)
+    return tuple(hip.linear_cl(x, al(w[r]), None if b is None else al(b[r])) for r in blocks)
+
+
+def _rows2(g, like):
+    """a gradient as the contiguous (M, N) matrix in `like`'s dtype that the GEMMs read"""
+    g2 = g.reshape(-1, g.shape[-1])
+    return g2 if g2.is_contiguous() and g2.dtype == like.dtype else g2.to(like.dtype).contiguous()
+
+
+class _LinearSplitTrainCL(torch.autograd.Function):
+    """(xh, zpre) = the two column halves of x @ w^T + b as two tensors: SS2D's gated in_proj (vmamba.py:276-279, chunk(2) on
+    the channel axis) on the training path.  Forward: tramba_linear_cl once per row block of the weight (contiguous slices of
+    the low-precision copy: nothing is concatenated or sliced afterwards, and the Parameter itself is never sliced under
+    autograd).  Backward: the input gradient is ONE two-source GEMM over [g_xh | g_z] (tramba_linear2_cl reads the two
+    gradients in turn), the weight gradient one (2 Di, C) tensor whose row blocks are the two TN GEMMs' fixed-order sums."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        wa = _lowp(w, x.dtype).detach().contiguous()
+        x2 = x.reshape(-1, x.shape[-1])
+        x2 = x2 if x2.is_contiguous() else x2.contiguous()
+        di = wa.shape[0] // 2
+        ctx.save_for_backward(x2, wa)
+        ctx.wa_t = _lowp_t(w, x.dtype)
+        ctx.wdtype, ctx.has_bias, ctx.xshape = w.dtype, b is not None, x.shape
+        bf = None if b is None else b.detach().float().contiguous()
+        xh = hip.linear_cl(x2, wa[:di], None if bf is None else bf[:di])
+        zp = hip.linear_cl(x2, wa[di:], None if bf is None else bf[di:])
+        shape = x.shape[:-1] + (di,)
+        return xh.view(shape), zp.view(shape)
+
+    @staticmethod
+    def backward(ctx, gxh, gzp):
+        x2, wa = ctx.saved_tensors
+        di = wa.shape[0] // 2
+        g1, g2 = _rows2(gxh, x2), _rows2(gzp, x2)
+        gx = gw = gb = None
+        if ctx.needs_input_grad[0]:
+            wt = wa.t().contiguous() if ctx.wa_t is None else ctx.wa_t             # (C, 2 Di)
+            if x2.dtype != torch.float32 and di % 64 == 0:
+                gx = hip.linear2_cl(g1, g2, wt)
+            else:
+                gx = hip.linear_cl(torch.cat((g1, g2), dim=1), wt)
+            gx = gx.view(ctx.xshape)
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            gw1, gb1 = _wgrad(g1, x2, ctx.has_bias)
+            gw2, gb2 = _wgrad(g2, x2, ctx.has_bias)
+            gw = torch.cat((gw1, gw2), dim=0).to(ctx.wdtype)
+            gb = torch.cat((gb1, gb2)) if ctx.has_bias else None
+        return gx, gw, gb
+
+
+class _GateLinearTrainCL(torch.autograd.Function):
+    """y = (gelu(n) * silu(zpre)) @ w^T + b: SS2D's gated out_proj (vmamba.py:287-290) on the training path.  p = gelu(n) *
+    silu(zpre) arrives from the LayerNorm launch that wrote n (tramba_add_layernorm_gate_cl) and is kept for the weight
+    gradient; backward: a plain input-gradient GEMM gives gp, tramba_gelu_gate_bwd_cl turns it into (gn, gz) in one pointwise
+    pass over the two stored pre-activations, the weight gradient is the TN GEMM on p."""
+
+    @staticmethod
+    def forward(ctx, n, zpre, w, b, p):
+        wa = _lowp(w, n.dtype).detach().contiguous()
+        d = n.shape[-1]
+        n2, z2, p2 = n.reshape(-1, d), zpre.reshape(-1, d), p.detach().reshape(-1, d)
+        n2, z2 = n2 if n2.is_contiguous() else n2.contiguous(), z2 if z2.is_contiguous() else z2.contiguous()
+        ctx.save_for_backward(n2, z2, p2, wa)
+        ctx.wa_t = _lowp_t(w, n.dtype)
+        ctx.wdtype, ctx.has_bias, ctx.nshape = w.dtype, b is not None, n.shape
+        y = hip.linear_cl(p2, wa, None if b is None else b.detach().float().contiguous())
+        return y.view(n.shape[:-1] + (wa.shape[0],))
+
+    @staticmethod
+    def backward(ctx, gy):
+        n2, z2, p2, wa = ctx.saved_tensors
+        gy2 = _rows2(gy, n2)
+        gn = gz = gw = gb = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            gp = _dgrad(gy2, wa, ctx.wa_t)
+            gn, gz = hip.gelu_gate_bwd_cl(gp, n2, z2)
+            gn, gz = gn.view(ctx.nshape), gz.view(ctx.nshape)
+        if ctx.needs_input_grad[2] or (ctx.has_bias and ctx.needs_input_grad[3]):
+            gw, gb = _wgrad(gy2, p2, ctx.has_bias, defer=ctx.wdtype == torch.float32)
+            gw = gw.to(ctx.wdtype)
+        return gn, gz, gw, gb, None
+
+
 class SS2D(nn.Module):
-    """vmamba.py:18-323, forward_type v2 / channel_first / disable_z (the only configuration the
-    shipped models use).  ``scan`` / ``merge`` / ``k_group`` are the reference's plugin API."""
+    """vmamba.py:18-323, forward_type v2.  channel_first=False: the module takes and returns (B, H, W, C) and its in_proj /
+    out_proj / out_norm have nn.Linear / nn.LayerNorm semantics (LinearLast / LayerNormLast); disable_z=False: in_proj is
+    2 * d_inner wide and its second half gates the output, y = GELU(out_norm(core)) * SiLU(z) (vmamba.py:276-290; DESIGN
+    section 30).  ``scan`` / ``merge`` / ``k_group`` are the reference's plugin API."""
 
     def __init__(self, d_model=96, d_state=16, ssm_ratio=2.0, dt_rank="auto", act_layer=nn.SiLU,
                  d_conv=3, conv_bias=False, dropout=0.0, bias=False,
@@ -1587,8 +1716,6 @@ class SS2D(nn.Module):
                  forward_type="v2", channel_first=False, disable_z=True,
                  scan=CrossScan, merge=CrossMerge, k_group=4, **kwargs):
         super().__init__()
-        if not channel_first or not disable_z:
-            raise NotImplementedError("tramba_amd.SS2D implements the channel_first / disable_z configuration")
         if act_layer is not nn.SiLU:
             raise NotImplementedError("SS2D act_layer must be SiLU (fused into the depth-wise conv kernel)")
         d_inner = int(ssm_ratio * d_model)
@@ -1599,8 +1726,9 @@ class SS2D(nn.Module):
         self.d_state, self.d_inner, self.dt_rank, self.k_group = d_state, d_inner, dt_rank, k_group
         self.scan, self.merge = scan, merge
 
-        self.out_norm = LayerNorm2d(d_inner)
-        self.in_proj = Linear2d(d_model, d_inner, bias=bias)
+        Linear, LayerNorm = (Linear2d, LayerNorm2d) if channel_first else (LinearLast, LayerNormLast)
+        self.out_norm = LayerNorm(d_inner)
+        self.in_proj = Linear(d_model, d_inner if disable_z else 2 * d_inner, bias=bias)
         self.act = act_layer()
         if self.with_dconv:
             self.conv2d = nn.Conv2d(d_inner, d_inner, groups=d_inner, bias=conv_bias, kernel_size=d_conv,
@@ -1608,7 +1736,7 @@ class SS2D(nn.Module):
         x_proj = [nn.Linear(d_inner, dt_rank + d_state * 2, bias=False) for _ in range(k_group)]
         self.x_proj_weight = nn.Parameter(torch.stack([t.weight for t in x_proj], dim=0))  # (K, R+2N, D)
         self.out_act = nn.GELU()
-        self.out_proj = Linear2d(d_inner, d_model, bias=bias)
+        self.out_proj = Linear(d_inner, d_model, bias=bias)
         self.dropout = nn.Dropout(dropout) if dropout > 0.0 else nn.Identity()
         if initialize != "v0":
             raise NotImplementedError(initialize)
@@ -1645,8 +1773,8 @@ class SS2D(nn.Module):
             _f32(self.dt_projs_weight).clone(), _f32(self.dt_projs_bias).reshape(-1).clone(),
             (-torch.exp(self.A_logs.detach().float())).reshape(a_shape).contiguous(), _f32(self.Ds).clone()))
 
-    def _core_fused_cl(self, x):
-        """x (B,H,W,D) after conv+SiLU -> GELU(out_norm(merge(scan(...)))), all HIP."""
+    def _core_fused_cl(self, x, zpre=None):
+        """x (B,H,W,D) after conv+SiLU -> GELU(out_norm(merge(scan(...)))) [* SiLU(zpre), the gate's pre-activation], all HIP."""
         b, h, w, d = x.shape
         k, r = self.k_group, self.dt_rank
         order = hip.scan_order(self.scan._tramba_family, h, w, x.device)
@@ -1660,6 +1788,10 @@ class SS2D(nn.Module):
             ys = hip.ss2d_scan_cl(xf, xdbl, order, dt_w, dt_b, a_neg, ds, ys_dtype)
         else:
             ys = hip.ss2d_scan_n_cl(xf, xdbl, order, dt_w, dt_b, a_neg, ds, ys_dtype)
+        if zpre is not None:
+            y = hip.ss2d_merge_norm_gate_cl(ys, order, _f32(self.out_norm.weight), _f32(self.out_norm.bias),
+                                            zpre.view(b, h * w, d), self.out_norm.eps, hip.ACT_GELU, x.dtype)
+            return y.view(b, h, w, d)
         y = hip.ss2d_merge_norm_cl(ys, order, _f32(self.out_norm.weight), _f32(self.out_norm.bias),
                                    self.out_norm.eps, hip.ACT_GELU, x.dtype)
         return y.view(b, h, w, d)
@@ -1715,9 +1847,19 @@ class SS2D(nn.Module):
     def _forward_train_cl(self, xn):
         """forwardv2 (vmamba.py:275-291) under autograd on a channels-last map that has ALREADY been normalised by the
         caller; returns out_proj's output (the residual branch, before any add).  Seven launches: in_proj, conv + SiLU (dual
-        store), x_proj, scan, merge, out_norm + GELU (dual store), out_proj."""
+        store), x_proj, scan, merge, out_norm + GELU (dual store), out_proj.  Gated (disable_z=False): in_proj is one launch
+        per half, the dual store writes gelu(n) * silu(zpre) and out_proj's backward goes through tramba_gelu_gate_bwd_cl."""
         b, h, w, _ = xn.shape
         d = self.d_inner
+        if not self.disable_z:
+            xi, zpre = _LinearSplitTrainCL.apply(xn, self.in_proj.weight, self.in_proj.bias)
+            z, xs = _DwConvActCL.apply(xi, self.conv2d.weight, self.conv2d.bias, hip.ACT_SILU)
+            order = hip.scan_order(self.scan._tramba_family, h, w, xn.device)
+            ym = _SS2DInnerCL.apply(z.view(b, h * w, d), xs.view(b, h * w, d), self.x_proj_weight, self.dt_projs_weight,
+                                    self.dt_projs_bias, self.A_logs, self.Ds, order)
+            _, yn, yp = _AddLayerNormCL.apply(ym.view(b, h, w, d), None, None, self.out_norm.weight, self.out_norm.bias,
+                                              self.out_norm.eps, hip.ACT_GELU, False, zpre)
+            return _GateLinearTrainCL.apply(yn, zpre, self.out_proj.weight, self.out_proj.bias, yp)
         xi = _LinearTrainCL.apply(xn, self.in_proj.weight, self.in_proj.bias)
         z, xs = _DwConvActCL.apply(xi, self.conv2d.weight, self.conv2d.bias, hip.ACT_SILU)
         order = hip.scan_order(self.scan._tramba_family, h, w, xn.device)
@@ -1725,7 +1867,7 @@ class SS2D(nn.Module):
                                 self.dt_projs_bias, self.A_logs, self.Ds, order)
         # out_norm and the GELU of vmamba.py:270 in one pass; out_proj's input-gradient GEMM carries the GELU's gradient
         _, yn, ya = _AddLayerNormCL.apply(ym.view(b, h, w, d), None, None, self.out_norm.weight, self.out_norm.bias,
-                                          self.out_norm.eps, hip.ACT_GELU, False)
+                                          self.out_norm.eps, hip.ACT_GELU, False, None)
         return _GeluLinearTrainCL.apply(yn, self.out_proj.weight, self.out_proj.bias, ya)
 
     def _forward_cl(self, x, residual=None, pre_norm=None):
@@ -1733,7 +1875,14 @@ class SS2D(nn.Module):
         if self._train_path_ok(x):
             y = self._forward_train_cl(x if pre_norm is None else pre_norm._forward_cl(x))
             return y if residual is None else y + residual
-        x = self.in_proj._forward_norm_cl(x, pre_norm) if pre_norm is not None else self.in_proj._forward_cl(x)
+        zpre = None
+        if self.disable_z:
+            x = self.in_proj._forward_norm_cl(x, pre_norm) if pre_norm is not None else self.in_proj._forward_cl(x)
+        elif _infer(x, self.in_proj.weight, self.in_proj.bias, *(() if pre_norm is None else (pre_norm.weight, pre_norm.bias))):
+            x, zpre = _linear_halves_cl(self.in_proj, x, pre_norm)
+        else:   # autograd without the fused training path: one GEMM, the halves taken by the framework (vmamba.py:279)
+            t = self.in_proj._forward_cl(x if pre_norm is None else pre_norm._forward_cl(x))
+            x, zpre = (u.contiguous() for u in t.chunk(2, dim=-1))
         if self.with_dconv:
             if _infer(x, self.conv2d.weight):
                 cv = self.conv2d
@@ -1745,16 +1894,23 @@ class SS2D(nn.Module):
             x = F.silu(x)
         gelu_in = False
         if self._fused_ok(x):
-            y = self._core_fused_cl(x)
+            y = self._core_fused_cl(x, zpre)          # (the gate rides in the merge kernel's epilogue)
+            zpre = None
         elif self._train_fused_ok(x):
             y = self._core_train_cl(x)
-            gelu_in = True
+            gelu_in = zpre is None
+            if zpre is not None:
+                y = F.gelu(y)
         else:
             y = self._core_plugin_cl(x)
+        if zpre is not None:    # vmamba.py:288-290 in framework ops, fp32 inside: the paths without a fused form of the gate
+            y = (y.float() * F.silu(zpre.float())).to(y.dtype)
         return self.dropout(self.out_proj._forward_cl(y, residual=residual, gelu_in=gelu_in))
 
     def forward(self, x):
         _need_device(x)
+        if not self.channel_first:
+            return self._forward_cl(x.contiguous())
         return from_cl(self._forward_cl(to_cl(x)))
 
 
@@ -1815,7 +1971,10 @@ class VSSBlock(_ResidualBlock):
                  ssm_conv_bias=False, ssm_drop_rate=0.0, ssm_init="v0", forward_type="v05",
                  mlp_ratio=4.0, mlp_act_layer=nn.GELU, mlp_drop_rate=0.0, post_norm=False, **kwargs):
         super().__init__()
-        assert channel_first and not post_norm and ssm_ratio > 0 and mlp_ratio > 0
+        assert not post_norm and ssm_ratio > 0 and mlp_ratio > 0
+        self.channel_first = channel_first       # False: (B, H, W, C) in and out, nn.LayerNorm / nn.Linear semantics inside
+        if not channel_first and norm_layer in (nn.LayerNorm, LayerNorm2d):
+            norm_layer = LayerNormLast
         self.norm = norm_layer(hidden_dim)
         self.op = SS2D(d_model=hidden_dim, d_state=ssm_d_state, ssm_ratio=ssm_ratio, dt_rank=ssm_dt_rank,
                        act_layer=ssm_act_layer, d_conv=ssm_conv, conv_bias=ssm_conv_bias, dropout=ssm_drop_rate,
@@ -1835,6 +1994,8 @@ class VSSBlock(_ResidualBlock):
 
     def forward(self, x):
         _need_device(x)
+        if not self.channel_first:
+            return self._forward_cl(x.contiguous())
         return from_cl(self._forward_cl(to_cl(x)))
 
 
