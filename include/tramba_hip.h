@@ -802,6 +802,36 @@ int tramba_grad_norm_scaled(const float *const *grads, const int64_t *numel, int
  * inverses (2^-126 .. 2^126); growth_interval >= 1.  Anything else is refused (< 0, tramba_last_error()). */
 int tramba_loss_scale_update(tramba_loss_scale *ls, const tramba_step_ctl *ctl, double growth, double backoff,
                              int growth_interval, double min_scale, double max_scale, void *stream);
+/* ---- per-step learning-rate schedule and weight average: a third record, owned by the caller like the other two ----
+ * (No reference counterpart: utils/lr.py changes the rate at listed epochs, on the host.)  The optimizer kernel reads the
+ * record when it runs, so a replayed hipGraph follows a schedule that moves at every step.  The caller fills the record
+ * before the first step (step, the factor and the weight of that step). */
+typedef struct tramba_step_sched {
+    int64_t step;            /* optimizer steps ATTEMPTED since the record was filled (skipped ones included) */
+    double lr_factor;        /* what every group's lr is multiplied by in the step under way */
+    float ema_weight;        /* w of  ema += w * (p - ema)  in the step under way */
+    int32_t reserved;
+} tramba_step_sched;
+/* The record's move after a step (a one-lane launch behind the optimizer's and behind tramba_loss_scale_update):
+ *   step += 1;  lr_factor = lr_table[min(step, n_lr - 1)];  ema_weight = ema_table[min(step, n_ema - 1)].
+ * lr_table: doubles, ema_table: floats, both in device memory.  lr_table == NULL: lr_factor = 1.0; ema_table == NULL:
+ * ema_weight stays.  The move does not look at the skip flag: a schedule ends at the step it was planned to end at.
+ * A non-NULL table with n < 1 is refused (< 0, tramba_last_error()).  No allocation, no synchronisation. */
+int tramba_step_sched_advance(tramba_step_sched *rec, const double *lr_table, int64_t n_lr, const float *ema_table,
+                              int64_t n_ema, void *stream);
+/* tramba_adam_step_ctl with the record (sched == NULL && ema == NULL is tramba_adam_step_ctl bit for bit):
+ *   sched: a device pointer.  The bias-corrected step size is formed in fp64 from lr * sched->lr_factor (a double product)
+ *          instead of lr and nothing else changes: the call equals tramba_adam_step_ctl at lr' = lr * factor bit for bit,
+ *          the factor read when the kernel runs.
+ *   ema:   a HOST array of `count` device pointers, one fp32 tensor of the parameter's size each (needs sched).  After the
+ *          parameter's update, in the same pass:  e = fmaf(w, p_new - e, e),  w = sched->ema_weight  (36 B per parameter
+ *          instead of 28; the vector path when all five tensors are 16-byte aligned).  skip[0] != 0 leaves e as it is,
+ *          with everything else.
+ * 64 tensors per launch. */
+int tramba_adam_step_sched(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
+                           float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, const float *gscale, const int *skip, float *const *ema,
+                           const tramba_step_sched *sched, void *stream);
 
 /* ------------------------------------------------------------------ fused attention (Tramba-S / -P encoders, inference) */
 /* Both entries: K and V of one (problem, head) are staged whole in LDS (at most 256 keys), scores on MFMA with f32

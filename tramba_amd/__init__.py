@@ -11,7 +11,7 @@ from .models import (BaseUMamba, BaseUMambaEnc, VSSMDecoder, build, bulid_model,
 from .modules import (DCT2D, SS2D, DropPath, DWConv, DWMSMlp, FinalPatchExpand_X4, FreqBlockv6,  # noqa: F401
                       FreqExpand2D, FreqSS2Dv6, LayerNorm2d, LayerNormLast, Linear2d, LinearLast, Mlp,
                       MultiScaleDecoderBlock, PatchExpand, VSSBlock, VSSMEncoder, load_pretrained_Base)
-from .train import LossScale, SodLoss, StepControl, structure_loss, wbce  # noqa: F401
+from .train import LossScale, LrSchedule, SodLoss, StepControl, WeightEMA, structure_loss, wbce  # noqa: F401
 from .ops import (CrossMerge, CrossMerge_Dilation, CrossMerge_Line, CrossMerge_Window, CrossScan,  # noqa: F401
                   CrossScan_Dilation, CrossScan_Line, CrossScan_Window, SelectiveScanOflex,
                   deterministic_scan, fused_dstate_training, get_fused_dstate_training, selective_scan_cuda_oflex,

@@ -494,6 +494,136 @@ __global__ __launch_bounds__(kAdamThreads) void adam_kernel(AdamArgs a)
     if (al) adam_chunk<true>(t, off, c); else adam_chunk<false>(t, off, c);
 }
 
+// ------------------------------------------------------------------------------------------------- scheduled Adam (+ EMA)
+// tramba_adam_step_sched: adam_kernel's step with the learning rate multiplied by a factor that lives in a device record
+// (tramba_step_sched) and, when the tensor has one, an exponential moving average of the parameter moved in the same pass:
+// e = fmaf(w, p_new - e, e), one more read and write per element (36 B instead of 28).  A tensor carries a seventh
+// pointer here, so a launch holds fewer of them; adam_kernel and its argument struct stay as they are.
+constexpr int kAdamSchedTensors = 64;
+struct AdamSchedTensor {
+    float *p;
+    const float *g;
+    float *m, *v;
+    const float *step;
+    long n;
+    float *e;                      // the average (null: this tensor keeps none)
+};
+struct AdamSchedArgs {
+    AdamSchedTensor t[kAdamSchedTensors];
+    int first[kAdamSchedTensors + 1];
+    int count;
+    double lr, beta1, beta2, eps, weight_decay;
+    const float *gscale;
+    const int *skip;
+    const tramba_step_sched *sched;   // never null here (the entry hands a call without one to adam_kernel)
+};
+static_assert(sizeof(AdamSchedArgs) <= 4096, "kernel arguments are limited to 4 KB");
+
+template <bool ALIGNED, bool EMA>
+__device__ __forceinline__ void adam_sched_chunk(const AdamSchedTensor &t, long off, const AdamCoef &c, float w)
+{
+    const long left = t.n - off;
+    const int here = left < kAdamChunk ? (int)left : kAdamChunk;
+    const int nvec = here >> 2;
+    float *p = t.p + off, *m = t.m + off, *v = t.v + off, *e = EMA ? t.e + off : nullptr;
+    const float *g = t.g + off;
+    constexpr int U = 4;
+    for (int j0 = threadIdx.x; j0 < nvec; j0 += U * kAdamThreads) {
+        adam_f4 pp[U], gg[U], mm[U], vv[U], ee[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * kAdamThreads;
+            if (j < nvec) {
+                gg[u] = adam_load<ALIGNED>(g + 4 * j);
+                pp[u] = adam_load<ALIGNED>(p + 4 * j);
+                mm[u] = adam_load<ALIGNED>(m + 4 * j);
+                vv[u] = adam_load<ALIGNED>(v + 4 * j);
+                if constexpr (EMA) ee[u] = adam_load<ALIGNED>(e + 4 * j);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int j = j0 + u * kAdamThreads;
+            if (j < nvec) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float pe = pp[u][k], me = mm[u][k], ve = vv[u][k];
+                    adam_math(pe, gg[u][k], me, ve, c);
+                    pp[u][k] = pe;
+                    mm[u][k] = me;
+                    vv[u][k] = ve;
+                    if constexpr (EMA) ee[u][k] = fmaf(w, pe - ee[u][k], ee[u][k]);
+                }
+                adam_store<ALIGNED>(p + 4 * j, pp[u]);
+                adam_store<ALIGNED>(m + 4 * j, mm[u]);
+                adam_store<ALIGNED>(v + 4 * j, vv[u]);
+                if constexpr (EMA) adam_store<ALIGNED>(e + 4 * j, ee[u]);
+            }
+        }
+    }
+    const int j = (nvec << 2) + threadIdx.x;     // < 4 trailing elements of the tensor
+    if (j < here) {
+        float pe = p[j], me = m[j], ve = v[j];
+        adam_math(pe, g[j], me, ve, c);
+        p[j] = pe;
+        m[j] = me;
+        v[j] = ve;
+        if constexpr (EMA) e[j] = fmaf(w, pe - e[j], e[j]);
+    }
+}
+
+__global__ __launch_bounds__(kAdamThreads) void adam_sched_kernel(AdamSchedArgs a)
+{
+    __shared__ float corr[2];
+    if (a.skip && *a.skip) return;                // (uniform over the grid: the averages keep their bits with everything else)
+    int lo = 0, hi = a.count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    const AdamSchedTensor t = a.t[lo];
+    const long off = (long)((int)blockIdx.x - a.first[lo]) * kAdamChunk;
+    if (threadIdx.x == 0) {                       // adam_kernel's corrections at lr * factor: one more double product
+        const double s = (double)*t.step;
+        const double lr = a.lr * a.sched->lr_factor;
+        corr[0] = (float)(lr / (1.0 - pow(a.beta1, s)));
+        corr[1] = (float)sqrt(1.0 - pow(a.beta2, s));
+    }
+    __syncthreads();
+    AdamCoef c;
+    c.step_size = corr[0];
+    c.bc2_sqrt = corr[1];
+    c.b1w = (float)(1.0 - a.beta1);
+    c.beta2 = (float)a.beta2;
+    c.b2w = (float)(1.0 - a.beta2);
+    c.eps = (float)a.eps;
+    c.wd = (float)a.weight_decay;
+    c.scaled = a.gscale != nullptr;
+    c.gs = c.scaled ? *a.gscale : 1.f;
+    const uintptr_t bits = reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
+                           reinterpret_cast<uintptr_t>(t.v) | reinterpret_cast<uintptr_t>(t.e);
+    const bool al = (bits & 15) == 0;
+    if (t.e) {
+        const float w = a.sched->ema_weight;
+        if (al) adam_sched_chunk<true, true>(t, off, c, w); else adam_sched_chunk<false, true>(t, off, c, w);
+    } else {
+        if (al) adam_sched_chunk<true, false>(t, off, c, 0.f); else adam_sched_chunk<false, false>(t, off, c, 0.f);
+    }
+}
+
+// The schedule record's move after a step: one lane, behind the optimizer's launches (and the loss scale's move).  It does
+// not read the skip flag: the index counts the steps that were attempted.
+__global__ void step_sched_advance_kernel(tramba_step_sched *rec, const double *lr_table, long n_lr, const float *ema_table,
+                                          long n_ema)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const long step = (long)rec->step + 1;
+    const long at = step < 0 ? 0 : step;          // (a record filled with a negative count reads the first entries)
+    rec->step = step;
+    rec->lr_factor = lr_table ? lr_table[at < n_lr - 1 ? at : n_lr - 1] : 1.0;
+    if (ema_table) rec->ema_weight = ema_table[at < n_ema - 1 ? at : n_ema - 1];
+}
+
 // ------------------------------------------------------------------------------------------------- step control
 // Tensors of a launch are dealt like Adam's: by value in the kernel arguments, a workgroup per chunk of kAdamChunk elements.
 constexpr int kAccTensors = 128, kNormTensors = 160, kNormThreads = 256;
@@ -951,6 +1081,71 @@ extern "C" int tramba_adam_step_ctl(float *const *params, const float *const *gr
 {
     return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, gscale,
                           skip, stream);
+}
+
+extern "C" int tramba_adam_step_sched(float *const *params, const float *const *grads, float *const *exp_avg,
+                                      float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr,
+                                      double beta1, double beta2, double eps, double weight_decay, const float *gscale,
+                                      const int *skip, float *const *ema, const tramba_step_sched *sched, void *stream)
+{
+    TRAMBA_CHECK(sched || !ema, "adam_step_sched: an average needs the schedule record (its weight lives there)");
+    if (!sched)
+        return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, gscale,
+                              skip, stream);
+    TRAMBA_CHECK(params && grads && exp_avg && exp_avg_sq && steps && numel && count > 0, "adam_step_sched: empty input");
+    TRAMBA_CHECK(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0,
+                 "adam_step_sched: bad hyper-parameters");
+    hipStream_t s = (hipStream_t)stream;
+    for (int i = 0; i < count; ++i) {
+        TRAMBA_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && steps[i] && numel[i] > 0,
+                     "adam_step_sched: tensor %d: null pointer or no elements", i);
+        TRAMBA_CHECK(!ema || ema[i], "adam_step_sched: tensor %d: null average", i);
+    }
+    for (int base = 0; base < count; base += kBumpTensors) {
+        BumpArgs b;
+        b.count = count - base < kBumpTensors ? count - base : kBumpTensors;
+        for (int i = 0; i < kBumpTensors; ++i) b.step[i] = i < b.count ? steps[base + i] : nullptr;
+        b.skip = skip;
+        hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(kBumpTensors), 0, s, b);
+        TRAMBA_LAUNCH_CHECK();
+    }
+    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAdamSchedTensors);
+    for (size_t l = 0; l < bins.size(); ++l) {
+        AdamSchedArgs a;
+        long blocks = 0;
+        const int c = (int)bins[l].size();           // <= kAdamSchedTensors by construction
+        for (int i = 0; i < c; ++i) {
+            const int j = bins[l][i];
+            const long nb = (numel[j] + kAdamChunk - 1) / kAdamChunk;
+            TRAMBA_CHECK(blocks + nb < 2147483647L, "adam_step_sched: too many workgroups");
+            a.t[i] = AdamSchedTensor{params[j], grads[j], exp_avg[j], exp_avg_sq[j], steps[j], (long)numel[j],
+                                     ema ? ema[j] : nullptr};
+            a.first[i] = (int)blocks;
+            blocks += nb;
+        }
+        a.count = c;
+        for (int i = c; i <= kAdamSchedTensors; ++i) a.first[i] = (int)blocks;
+        for (int i = c; i < kAdamSchedTensors; ++i) a.t[i] = AdamSchedTensor{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
+        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
+        a.gscale = gscale;
+        a.skip = skip;
+        a.sched = sched;
+        hipLaunchKernelGGL(adam_sched_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
+        TRAMBA_LAUNCH_CHECK();
+    }
+    return TRAMBA_OK;
+}
+
+extern "C" int tramba_step_sched_advance(tramba_step_sched *rec, const double *lr_table, int64_t n_lr, const float *ema_table,
+                                         int64_t n_ema, void *stream)
+{
+    TRAMBA_CHECK(rec, "step_sched_advance: null record");
+    TRAMBA_CHECK(!lr_table || n_lr >= 1, "step_sched_advance: an lr table of %lld entries (at least 1)", (long long)n_lr);
+    TRAMBA_CHECK(!ema_table || n_ema >= 1, "step_sched_advance: an ema table of %lld entries (at least 1)", (long long)n_ema);
+    hipLaunchKernelGGL(step_sched_advance_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, rec, lr_table, (long)n_lr,
+                       ema_table, (long)n_ema);
+    TRAMBA_LAUNCH_CHECK();
+    return TRAMBA_OK;
 }
 
 // chunks (= workgroups) over all tensors of a call, -1 beyond what a grid holds

@@ -88,6 +88,11 @@ class GraphedTrainStep:
     the scale in the device record, the update graph ends with the scale's move, and the scaler's hyper-parameters are
     host scalars of that launch and so part of the update graph's key; the scaler record is put back after the warm-up
     with the rest.
+    A control with a schedule or an EMA (StepControl(schedule=..., ema=...)) never re-captures for the learning rate: the
+    groups' `lr` values stay where they are, the optimizer launches of the update graph read the factor (and the EMA
+    weight) from the schedule record, and the graph ends with the record's move to the next table entries.  The tables'
+    addresses and lengths are arguments of that launch and so part of the update graph's key; the record and the averages
+    are put back after the warm-up with the rest.
 
     `loss` (tramba_amd.train.SodLoss; None: `tramba_loss`) is what `train_step(..., loss=loss)` takes; it is recorded into
     the graphs, so it is fixed here, at construction."""
@@ -237,6 +242,8 @@ class GraphedTrainStep:
             entry = self._graphs[shape_key] = {"static": None, "mid": None, "update": {}, "pool": torch.cuda.graph_pool_handle()}
         need_mid = count > 1 and entry["mid"] is None
         update_key = (count, control.clip_norm, control.skip_nonfinite, None if control.scaler is None else control.scaler.key())
+        if control._scheduled:                      # the tables' addresses and lengths are arguments of the advance launch
+            update_key += tuple(None if t is None else (t.data_ptr(), t.numel()) for t in control._tables(x0.device))
         need_update = update_key not in entry["update"]
         if need_mid or need_update:
             if entry["static"] is None:

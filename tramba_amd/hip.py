@@ -154,6 +154,8 @@ SIGNATURES = {
     "tramba_grad_norm_scaled": (c_int, [c_vp] * 2 + [c_int, ctypes.c_double, ctypes.c_double, c_int, c_vp, c_vp, c_vp,
                                         ctypes.c_size_t, c_vp]),
     "tramba_loss_scale_update": (c_int, [c_vp] * 2 + [ctypes.c_double] * 2 + [c_int] + [ctypes.c_double] * 2 + [c_vp]),
+    "tramba_step_sched_advance": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "tramba_adam_step_sched": (c_int, [c_vp] * 6 + [c_int] + [ctypes.c_double] * 5 + [c_vp] * 5),
     "tramba_window_attn_cl": (c_int, [c_vp] * 3 + [c_int] * 8 + [c_vp]),
     "tramba_kv_attn_cl": (c_int, [c_vp] * 3 + [c_int, c_i64] + [c_int] * 4 + [c_vp]),
     "tramba_window_attn_bwd_work": (ctypes.c_size_t, [c_int] * 6),
@@ -1516,6 +1518,77 @@ def loss_scale_update_raw(ls, ctl, growth, backoff, growth_interval, min_scale, 
     (tramba_loss_scale_update; a one-lane launch)"""
     _check(lib().tramba_loss_scale_update(ls.data_ptr(), ctl.data_ptr(), float(growth), float(backoff), int(growth_interval),
                                           float(min_scale), float(max_scale), _stream()), "loss_scale_update")
+
+
+STEP_SCHED_BYTES = 24    # struct tramba_step_sched: int64 step, double lr_factor, float ema_weight, int32 reserved
+
+
+def step_sched_record(device, step=0, lr_factor=1.0, ema_weight=0.0):
+    """a tramba_step_sched on `device` and typed 0-dim views of its fields:
+    (record, {"step": int64, "lr_factor": fp64, "ema_weight": fp32})"""
+    rec = torch.zeros(STEP_SCHED_BYTES // 8, dtype=torch.int64, device=device)
+    fields = {"step": rec[0], "lr_factor": rec.view(torch.float64)[1], "ema_weight": rec.view(torch.float32)[4]}
+    fields["step"].fill_(int(step))
+    fields["lr_factor"].fill_(float(lr_factor))
+    fields["ema_weight"].fill_(float(ema_weight))
+    return rec, fields
+
+
+def _sched_table(what, table, dtype):
+    if table is None:
+        return None, 0
+    if table.dtype != dtype or not table.is_cuda or table.dim() != 1 or not table.is_contiguous() or table.numel() < 1:
+        raise TrambaHipError(f"step_sched_advance: the {what} table is a non-empty contiguous 1-d {dtype} tensor on the device")
+    return table.data_ptr(), table.numel()
+
+
+def step_sched_advance_raw(rec, lr_table=None, ema_table=None):
+    """the schedule record's move after an optimizer step (tramba_step_sched_advance; a one-lane launch): step += 1, then
+    lr_factor / ema_weight from the tables' entries at min(step, n - 1).  `lr_table` (fp64) / `ema_table` (fp32): device
+    tensors; None: the factor becomes 1.0 / the weight stays."""
+    lp, ln = _sched_table("lr", lr_table, torch.float64)
+    ep, en = _sched_table("ema", ema_table, torch.float32)
+    _check(lib().tramba_step_sched_advance(rec.data_ptr(), lp, ln, ep, en, _stream()), "step_sched_advance")
+
+
+def adam_step_sched_raw(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, lr, beta1, beta2, eps, weight_decay=0.0,
+                        gscale=None, skip=None, ema=None, sched=None):
+    """`adam_step_raw` with a schedule record (tramba_adam_step_sched).  `sched`: the record tensor of `step_sched_record`
+    -- the step runs at lr * its lr_factor, read on the device when the kernel runs.  `ema`: a pointer array of fp32
+    averages, one per parameter, moved in the same pass by the record's ema_weight (needs `sched`).  Both None:
+    tramba_adam_step_ctl."""
+    if gscale is not None and (gscale.dtype != torch.float32 or not gscale.is_cuda):
+        raise TrambaHipError("adam_step_sched: gscale is an fp32 scalar on the device")
+    if skip is not None and (skip.dtype != torch.int32 or not skip.is_cuda):
+        raise TrambaHipError("adam_step_sched: skip is an int32 scalar on the device")
+    if sched is not None and (sched.dtype != torch.int64 or not sched.is_cuda or sched.numel() * 8 < STEP_SCHED_BYTES):
+        raise TrambaHipError("adam_step_sched: sched is a tramba_step_sched record on the device (step_sched_record)")
+    _check(lib().tramba_adam_step_sched(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
+                                        float(beta2), float(eps), float(weight_decay), _ptr(gscale), _ptr(skip), ema,
+                                        _ptr(sched), _stream()), "adam_step_sched")
+
+
+def adam_step_sched(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay=0.0, gscale=None,
+                    skip=None, ema=None, sched=None):
+    """One scheduled Adam step on lists of fp32 device tensors (`adam_step_sched_raw` builds on pointer arrays): `ema` is a
+    list of fp32 averages, one per parameter, or None; `sched` the record tensor or None."""
+    n = len(params)
+    if n == 0:
+        return
+    lists = (params, grads, exp_avgs, exp_avg_sqs) + (() if ema is None else (ema,))
+    if not all(len(group) == n for group in lists + (steps,)):
+        raise TrambaHipError("adam_step_sched: the tensor lists differ in length")
+    for group in lists + (steps,):
+        for t in group:
+            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
+                raise TrambaHipError("adam_step_sched: contiguous fp32 tensors on a HIP device only")
+    for group in lists[1:]:
+        for p, t in zip(params, group):
+            if t.numel() != p.numel():
+                raise TrambaHipError("adam_step_sched: gradient / state / average of another size than the parameter")
+    adam_step_sched_raw(pointer_array(params), pointer_array(grads), pointer_array(exp_avgs), pointer_array(exp_avg_sqs),
+                        pointer_array(steps), (ctypes.c_int64 * n)(*[t.numel() for t in params]), n, lr, beta1, beta2, eps,
+                        weight_decay, gscale=gscale, skip=skip, ema=None if ema is None else pointer_array(ema), sched=sched)
 
 
 def im2col3x3_cl(x, stride, pad, ckp):

@@ -279,10 +279,16 @@ class Adam(torch.optim.Adam):
         return plan
 
     @torch.no_grad()
-    def step(self, closure=None, gscale=None, skip=None):
+    def step(self, closure=None, gscale=None, skip=None, sched=None, ema=None):
         """`gscale` (fp32) / `skip` (int32): 0-dim device tensors read by the kernel when it runs -- every gradient is
         multiplied by the first before anything else, a non-zero second leaves parameters, moments and step counters as
-        they are (StepControl hands both over; a captured step follows their values at replay)."""
+        they are (StepControl hands both over; a captured step follows their values at replay).
+        `sched`: a tramba_step_sched record on the device (hip.step_sched_record) -- every group steps at its lr times
+        the record's lr_factor, read when the kernel runs.  `ema` (needs `sched`): a mapping parameter -> fp32 average of
+        its size; the averages of the parameters this step updates move in the same pass by the record's ema_weight.
+        With neither, the step runs the launches it always ran."""
+        if ema is not None and sched is None:
+            raise hip.TrambaHipError("Adam: an EMA needs the schedule record (its weight lives there)")
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -299,8 +305,20 @@ class Adam(torch.optim.Adam):
                     raise hip.TrambaHipError("Adam: dense contiguous fp32 gradients only")
             plan = self._plan(gi, ps)
             b1, b2 = group["betas"]
-            hip.adam_step_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps), group["lr"], b1, b2,
-                              group["eps"], group["weight_decay"], gscale=gscale, skip=skip)
+            if sched is None:
+                hip.adam_step_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps), group["lr"], b1,
+                                  b2, group["eps"], group["weight_decay"], gscale=gscale, skip=skip)
+            else:
+                avgs = None
+                if ema is not None:
+                    avgs = [ema[p] for p in ps]
+                    for p, e in zip(ps, avgs):
+                        if e.dtype != torch.float32 or e.device != p.device or not e.is_contiguous() or e.numel() != p.numel():
+                            raise hip.TrambaHipError("Adam: an average is a contiguous fp32 tensor of its parameter's size and device")
+                    avgs = hip.pointer_array(avgs)
+                hip.adam_step_sched_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps),
+                                        group["lr"], b1, b2, group["eps"], group["weight_decay"], gscale=gscale, skip=skip,
+                                        ema=avgs, sched=sched)
             # the kernel writes through raw pointers: bump the version counters as an in-place torch op would (every
             # derived-weight cache of the inference path is keyed on them)
             torch.autograd.graph.increment_version(ps)
@@ -388,6 +406,248 @@ class LossScale:
                 f"{self.growth_interval!r}, min_scale={self.min_scale!r}, max_scale={self.max_scale!r})")
 
 
+class LrSchedule:
+    """A learning-rate schedule as an immutable table of fp64 factors indexed by optimizer step and clamped to its last
+    entry: in step t every group's rate is its own `lr` times `factor(t)`.  The table is built on the host once and
+    uploaded once per device; StepControl(schedule=...) keeps the index in a device record, so the groups' `lr` values
+    never move and a captured step is never re-captured for them.  The index counts the steps that were ATTEMPTED: a step
+    skipped for a non-finite gradient uses up its entry, and a schedule ends at the step it was planned to end at.
+
+    Constructors (t = 0, 1, ... is the optimizer step; the ramp of `warmup` steps is (t + 1) / (warmup + 1)):
+      LrSchedule(factors)                         any sequence of non-negative finite numbers
+      from_callable(fn, total)                    [fn(t) for t in range(total)]
+      warmup_cosine(total, warmup, floor)         floor + (1 - floor) sin^2(pi / 2 * r),  r = (total - t) / (total - warmup)
+                                                  (= floor + (1 - floor) (1 + cos(pi (t - warmup) / (total - warmup))) / 2,
+                                                  in the form that keeps its precision at the end), total + 1 entries: the
+                                                  last one, for every step from `total` on, is `floor`
+      warmup_poly(total, warmup, power, floor)    floor + (1 - floor) r^power, same r and the same last entry
+      step_decay(steps_per_epoch, epochs, decay_epochs, decay_factors)
+                                                  `adjust_learning_rate` as a table: the factor of the latest listed
+                                                  epoch reached, 1.0 before the first; with it the decoder group's rate
+                                                  is that function's base_lr * f bit for bit"""
+
+    def __init__(self, factors):
+        import math
+        fs = tuple(float(f) for f in factors)
+        if not fs:
+            raise ValueError("LrSchedule: an empty table")
+        for t, f in enumerate(fs):
+            if not math.isfinite(f) or f < 0:
+                raise ValueError(f"LrSchedule: factor {f!r} at step {t}: finite and not negative")
+        self._factors = fs
+        self._tables = {}
+
+    def __len__(self):
+        return len(self._factors)
+
+    @property
+    def factors(self):
+        return self._factors
+
+    def factor(self, t):
+        """the host value of step t's factor"""
+        return self._factors[min(max(int(t), 0), len(self._factors) - 1)]
+
+    def table(self, device):
+        """the fp64 table on `device` (uploaded at the first call)"""
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = torch.tensor(self._factors, dtype=torch.float64).to(device)
+        return self._tables[key]
+
+    @classmethod
+    def from_callable(cls, fn, total):
+        if int(total) != total or total < 1:
+            raise ValueError(f"LrSchedule.from_callable: total must be a positive integer (got {total!r})")
+        return cls([fn(t) for t in range(int(total))])
+
+    @staticmethod
+    def _ramp(what, total, warmup, floor):
+        if int(total) != total or int(warmup) != warmup or not 0 <= warmup < total:
+            raise ValueError(f"LrSchedule.{what}: 0 <= warmup < total, both integers (got warmup={warmup!r}, total={total!r})")
+        if not 0.0 <= floor <= 1.0:
+            raise ValueError(f"LrSchedule.{what}: floor in [0, 1] (got {floor!r})")
+        return int(total), int(warmup), float(floor)
+
+    @classmethod
+    def warmup_cosine(cls, total, warmup=0, floor=0.0):
+        import math
+        total, warmup, floor = cls._ramp("warmup_cosine", total, warmup, floor)
+        fs = [(t + 1) / (warmup + 1) for t in range(warmup)]
+        fs += [floor + (1.0 - floor) * math.sin(0.5 * math.pi * ((total - t) / (total - warmup))) ** 2 for t in range(warmup, total + 1)]
+        return cls(fs)
+
+    @classmethod
+    def warmup_poly(cls, total, warmup=0, power=0.9, floor=0.0):
+        total, warmup, floor = cls._ramp("warmup_poly", total, warmup, floor)
+        if not power > 0:
+            raise ValueError(f"LrSchedule.warmup_poly: power must be positive (got {power!r})")
+        fs = [(t + 1) / (warmup + 1) for t in range(warmup)]
+        fs += [floor + (1.0 - floor) * ((total - t) / (total - warmup)) ** float(power) for t in range(warmup, total + 1)]
+        return cls(fs)
+
+    @classmethod
+    def step_decay(cls, steps_per_epoch, epochs, decay_epochs, decay_factors):
+        if int(steps_per_epoch) != steps_per_epoch or steps_per_epoch < 1 or int(epochs) != epochs or epochs < 1:
+            raise ValueError("LrSchedule.step_decay: steps_per_epoch and epochs are positive integers")
+        decay_epochs, decay_factors = list(decay_epochs), list(decay_factors)
+        if len(decay_epochs) != len(decay_factors):
+            raise ValueError("LrSchedule.step_decay: one factor per listed epoch")
+        fs, f = [], 1.0
+        for epoch in range(int(epochs)):
+            if epoch in decay_epochs:
+                f = float(decay_factors[decay_epochs.index(epoch)])
+            fs += [f] * int(steps_per_epoch)
+        return cls(fs)
+
+    def __repr__(self):
+        return f"LrSchedule({len(self._factors)} steps, {self._factors[0]!r} .. {self._factors[-1]!r})"
+
+
+class WeightEMA:
+    """An exponential moving average of the weights, moved by the optimizer step itself: ema += w_t * (p - ema) after the
+    parameter's update of step t, with w_t = 1 - min(decay, (1 + t) / (10 + t)) (`warmup=True`: the average follows the
+    weights closely while it is young) or w_t = 1 - decay (`warmup=False`).  The weights are a table, evaluated in fp64,
+    rounded to fp32 and as long as it takes to reach 1 - decay; t is the schedule index of StepControl, which counts
+    attempted steps.
+
+    Hand it to StepControl(ema=...).  It owns one tensor per optimizer parameter (fp32 on the device path; the
+    parameter's dtype where torch's optimizer runs), initialised to the parameter when the control first binds.  On the
+    device path the optimizer kernel moves the average in the pass that updates the parameter (36 B per parameter instead
+    of 28, no further launch), and a step that is skipped for a non-finite gradient leaves the averages alone.  Only
+    parameters the optimizer updates in a step have their average moved in that step: one without a gradient (frozen, or
+    unused in that forward) keeps its average as it is, which is where an average of a parameter that does not move
+    would stay anyway.  Buffers (BatchNorm's running statistics) are not averaged: evaluation under `applied` uses the
+    live model's."""
+
+    def __init__(self, decay=0.999, warmup=True):
+        import numpy as np
+        if not 0.0 <= decay < 1.0:
+            raise ValueError(f"WeightEMA: decay in [0, 1) (got {decay!r})")
+        self.decay, self.warmup = float(decay), bool(warmup)
+        ws, t = [], 0
+        while True:
+            d = min(self.decay, (1 + t) / (10 + t)) if self.warmup else self.decay
+            ws.append(float(np.float32(1.0 - d)))
+            if d >= self.decay:
+                break
+            t += 1
+        self._weights = tuple(ws)
+        self._tables = {}
+        self._avg = {}              # parameter -> its average
+        self._order = []            # the parameters in optimizer order
+        self._pending = None        # tensors handed to load_state_dict before the parameters were known
+
+    @property
+    def weights(self):
+        return self._weights
+
+    def weight(self, t):
+        """the host value of step t's weight (an fp32 number)"""
+        return self._weights[min(max(int(t), 0), len(self._weights) - 1)]
+
+    def table(self, device):
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = torch.tensor(self._weights, dtype=torch.float32).to(device)
+        return self._tables[key]
+
+    def _bind(self, opt):
+        """averages for the optimizer's parameters that have none yet, initialised to the parameter (or to what
+        load_state_dict left); the tensors of known parameters stay where they are"""
+        params = [p for g in opt.param_groups for p in g["params"]]
+        fresh = [p for p in params if p not in self._avg]
+        self._order = params
+        if self._pending is not None and len(self._pending) != len(params):
+            raise ValueError(f"WeightEMA.load_state_dict: {len(self._pending)} tensors for {len(params)} optimizer parameters")
+        with torch.no_grad():
+            for p in fresh:
+                self._avg[p] = p.detach().clone(memory_format=torch.contiguous_format)
+            if self._pending is not None:
+                for p, t in zip(params, self._pending):
+                    if t.shape != p.shape:
+                        raise ValueError(f"WeightEMA.load_state_dict: a tensor of shape {tuple(t.shape)} for a parameter of {tuple(p.shape)}")
+                    self._avg[p].copy_(t)
+                self._pending = None
+        return bool(fresh)
+
+    def tensors(self):
+        """the averages in optimizer parameter order"""
+        return [self._avg[p] for p in self._order]
+
+    def average(self, p):
+        return self._avg[p]
+
+    def state_dict(self):
+        return {"decay": self.decay, "warmup": self.warmup, "tensors": [t.detach().clone() for t in self.tensors()]}
+
+    def load_state_dict(self, sd):
+        if set(sd) != {"decay", "warmup", "tensors"}:
+            raise ValueError(f"WeightEMA.load_state_dict: keys {sorted(sd)}")
+        tensors = list(sd["tensors"])
+        if self._order:
+            if len(tensors) != len(self._order):
+                raise ValueError(f"WeightEMA.load_state_dict: {len(tensors)} tensors for {len(self._order)} optimizer parameters")
+            with torch.no_grad():
+                for p, t in zip(self._order, tensors):
+                    self._avg[p].copy_(t)
+        else:
+            self._pending = tensors
+
+    def _model_params(self, model):
+        ps = [p for p in model.parameters() if p in self._avg]
+        if not ps:
+            raise RuntimeError("WeightEMA: no parameter of this model has an average yet (they are laid out by the first "
+                               "step of the StepControl that holds this object)")
+        return ps
+
+    def applied(self, model):
+        """`with ema.applied(model):` -- the model computes with the averaged weights inside the block.  The averages are
+        put into the parameters BY CONTENT: the live values are saved, the averages copied in (an in-place torch op, so the
+        version counters move and the low-precision shadows, packed stencils and every other derived-weight cache are
+        rebuilt), and on exit the live bits are copied back and the caches rebuilt again.  The data pointers never
+        change, so captured graphs of the training step stay valid."""
+        return _EmaApplied(self, model)
+
+    def model_state_dict(self, model):
+        """model.state_dict() with every averaged parameter replaced by (a copy of) its average; buffers are the live ones"""
+        sd = model.state_dict()
+        for name, p in model.named_parameters():
+            if p in self._avg and name in sd:
+                sd[name] = self._avg[p].detach().clone().to(sd[name].dtype).view_as(sd[name])
+        return sd
+
+    def __repr__(self):
+        return f"WeightEMA(decay={self.decay!r}, warmup={self.warmup!r})"
+
+
+def _refresh_derived(model):
+    refresh_lowp_shadows(model, getattr(model, "compute_dtype", None))
+    if any(p.is_cuda for p in model.parameters()):
+        refresh_dw_packs(model)
+
+
+class _EmaApplied:
+    def __init__(self, ema, model):
+        self.ema, self.model, self.live = ema, model, None
+
+    def __enter__(self):
+        ps = self.ema._model_params(self.model)
+        with torch.no_grad():
+            self.live = [(p, p.detach().clone()) for p in ps]
+            torch._foreach_copy_([p.detach() for p in ps], [self.ema._avg[p].to(p.dtype).view_as(p) for p in ps])
+        _refresh_derived(self.model)
+        return self.model
+
+    def __exit__(self, *exc):
+        with torch.no_grad():
+            ps = [p for p, _ in self.live]
+            torch._foreach_copy_([p.detach() for p in ps], [v for _, v in self.live])
+        self.live = None
+        _refresh_derived(self.model)
+        return False
+
+
 class StepControl:
     """What an optimisation step built from several micro-batches needs to keep between them, and between replays of a
     captured step:
@@ -422,9 +682,25 @@ class StepControl:
     holds the SCALED sum over the micro-batches (p.grad / loss_scale-at-that-step / micro-batches is the mean gradient);
     on the host path it is the unscaled clipped mean as before.  `loss_scale` and `scale_backoffs` are 0-dim tensors like
     the two above (the scale the NEXT step will use; how often it was cut); `state_dict()` / `load_state_dict()` carry
-    scale, good_steps, backoffs and skipped_steps across a restart."""
+    scale, good_steps, backoffs and skipped_steps across a restart.
 
-    def __init__(self, accumulate=1, clip_norm=None, skip_nonfinite=None, loss_scale=None):
+      schedule        None or an LrSchedule: in optimizer step t every group steps at its own `lr` times schedule.factor(t);
+      ema             None or a WeightEMA: an exponential moving average of the weights, moved by the optimizer step.
+
+    With either, the device path keeps a third 24-byte record (tramba_step_sched: the steps attempted so far, the factor
+    and the EMA weight of the step under way).  The optimizer kernel reads it when it runs (tramba_adam_step_sched: the
+    step size is formed from lr * factor in fp64, the average moves in the pass that updates the parameter) and
+    tramba_step_sched_advance moves it to the next table entries behind the optimizer's launches and the scale's move --
+    no host decision, the groups' `lr` never change, and a captured step is never captured again for the rate.  The index
+    counts ATTEMPTED steps: a skipped step uses up its entry, but leaves the averages as they are.  Without either, the
+    step issues the launches it always issued.  `lr_factor` (the factor the next step will use) and `sched_step` are 0-dim
+    tensors like the others; `state_dict()` gains `sched_step` (only then), the averages travel in `ema.state_dict()`."""
+
+    def __init__(self, accumulate=1, clip_norm=None, skip_nonfinite=None, loss_scale=None, schedule=None, ema=None):
+        if schedule is not None and not isinstance(schedule, LrSchedule):
+            raise TypeError(f"StepControl: schedule={schedule!r}: None or an LrSchedule")
+        if ema is not None and not isinstance(ema, WeightEMA):
+            raise TypeError(f"StepControl: ema={ema!r}: None or a WeightEMA")
         if int(accumulate) != accumulate or accumulate < 1:
             raise ValueError(f"StepControl: accumulate must be a positive integer (got {accumulate!r})")
         if clip_norm is not None and not clip_norm > 0:
@@ -441,6 +717,8 @@ class StepControl:
         self.clip_norm = None if clip_norm is None else float(clip_norm)
         self.skip_nonfinite = bool(skip_nonfinite) or loss_scale is not None
         self.scaler = loss_scale
+        self.schedule, self.ema = schedule, ema
+        self._sched_record = self._sched = None   # device: the tramba_step_sched and its views; host: {"step", "lr_factor"}
         self._key = None            # what the buffers below were laid out for
         self._device_path = None
         self._record = self._fields = self._flat = self._workspace = None
@@ -451,6 +729,8 @@ class StepControl:
         self._start = {"skipped_steps": 0}
         if loss_scale is not None:
             self._start.update(scale=loss_scale.init, good_steps=0, backoffs=0)
+        if self._scheduled:
+            self._start["sched_step"] = 0
         self._plans = {}
         self._used = set()          # parameters that had a gradient in a micro-batch of the step under way
         self._dirty = set()         # parameters whose accumulator holds an earlier step's sums
@@ -485,21 +765,48 @@ class StepControl:
         """how often a skipped step has cut the scale"""
         return self._scaler_field("backoffs", "scale_backoffs")
 
+    @property
+    def _scheduled(self):
+        return self.schedule is not None or self.ema is not None
+
+    def _sched_field(self, name, what):
+        if not self._scheduled:
+            raise RuntimeError(f"StepControl.{what}: this control has neither a schedule nor an EMA")
+        if self._key is None:
+            raise RuntimeError(f"StepControl.{what}: no step has run yet")
+        return self._sched[name]
+
+    @property
+    def lr_factor(self):
+        """what the next step multiplies every group's lr by (a 0-dim fp64 tensor; 1.0 without a schedule)"""
+        return self._sched_field("lr_factor", "lr_factor")
+
+    @property
+    def sched_step(self):
+        """optimizer steps attempted so far, skipped ones included: the index the next step reads its tables at"""
+        return self._sched_field("step", "sched_step")
+
     def state_dict(self):
-        """host numbers (reading them is a sync): skipped_steps, and with a loss scale its scale, good_steps, backoffs"""
+        """host numbers (reading them is a sync): skipped_steps, with a loss scale its scale, good_steps, backoffs, and with
+        a schedule or an EMA sched_step"""
         if self._key is None:
             return dict(self._start)
         sd = {"skipped_steps": int(self.skipped_steps)}
         if self.scaler is not None:
             sd.update(scale=float(self._ls["scale"]), good_steps=int(self._ls["good_steps"]), backoffs=int(self._ls["backoffs"]))
+        if self._scheduled:
+            sd["sched_step"] = int(self._sched["step"])
         return sd
 
     def load_state_dict(self, sd):
         want = {"skipped_steps"} | ({"scale", "good_steps", "backoffs"} if self.scaler is not None else set())
+        want |= {"sched_step"} if self._scheduled else set()
         if set(sd) != want:
             raise ValueError(f"StepControl.load_state_dict: keys {sorted(sd)} for a control that keeps {sorted(want)}")
         if self.scaler is not None and not (_is_pow2(float(sd["scale"])) and 2.0 ** -126 <= sd["scale"] <= 2.0 ** 126):
             raise ValueError(f"StepControl.load_state_dict: scale {sd['scale']!r} is no power of two in 2^-126 .. 2^126")
+        if self._scheduled and (int(sd["sched_step"]) != sd["sched_step"] or sd["sched_step"] < 0):
+            raise ValueError(f"StepControl.load_state_dict: sched_step {sd['sched_step']!r} is no step count")
         self._start = {k: (float(v) if k == "scale" else int(v)) for k, v in sd.items()}
         if self._key is not None:
             self._fill_state()
@@ -514,6 +821,12 @@ class StepControl:
             self._ls["backoffs"].fill_(st["backoffs"])
             if self._device_path:
                 self._ls["inv_scale"].fill_(1.0 / st["scale"])
+        if self._scheduled:
+            t = st["sched_step"]
+            self._sched["step"].fill_(t)
+            self._sched["lr_factor"].fill_(1.0 if self.schedule is None else self.schedule.factor(t))
+            if self._device_path:
+                self._sched["ema_weight"].fill_(0.0 if self.ema is None else self.ema.weight(t))
 
     # ------------------------------------------------------------------ buffers
     def _bind(self, opt, reducer=None):
@@ -525,6 +838,8 @@ class StepControl:
         if reducer is not None:
             reducer.begin_accumulation()
         key = (tuple(id(p) for p in params), id(reducer), None if reducer is None else tuple(f.data_ptr() for f in reducer.flat))
+        if self.ema is not None:
+            self.ema._bind(opt)                    # (averages for parameters it has not met; the others keep theirs)
         if key == self._key:
             return self._params
         dev = params[0].device
@@ -560,6 +875,8 @@ class StepControl:
             numel = (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat])
             nbytes = hip.grad_norm_workspace(numel, len(self._flat))
             self._workspace = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+            if self._scheduled:
+                self._sched_record, self._sched = hip.step_sched_record(dev)
         else:
             self._norm = torch.zeros((), dtype=params[0].dtype if params[0].dtype.is_floating_point else torch.float32, device=dev)
             self._skipped = torch.zeros((), dtype=torch.int64, device=dev)
@@ -568,10 +885,19 @@ class StepControl:
                 self._ls = {"scale": torch.zeros((), dtype=torch.float32, device=dev),
                             "good_steps": torch.zeros((), dtype=torch.int32, device=dev),
                             "backoffs": torch.zeros((), dtype=torch.int64, device=dev)}
+            if self._scheduled:
+                self._sched_record = None
+                self._sched = {"step": torch.zeros((), dtype=torch.int64, device=dev),
+                               "lr_factor": torch.ones((), dtype=torch.float64, device=dev)}
         self._device_path, self._params, self._key, self._plans = device_path, params, key, {}
         self._fill_state()
         self._dirty = set(params) if reducer is not None else set()    # own buffers start as zeros, a reducer's buckets may not
         return params
+
+    def _tables(self, device):
+        """(lr table, ema table) on the device, None where there is none: what tramba_step_sched_advance reads"""
+        return (None if self.schedule is None else self.schedule.table(device),
+                None if self.ema is None else self.ema.table(device))
 
     def _begin_step(self):
         """a step starts with no micro-batch accumulated, whatever became of the last one (a step that raised between two
@@ -585,6 +911,10 @@ class StepControl:
         ts = [self._record] if self._device_path else [self._norm, self._skipped]
         if self.scaler is not None:
             ts += [self._ls_record] if self._device_path else list(self._ls.values())
+        if self._scheduled:
+            ts += [self._sched_record] if self._device_path else list(self._sched.values())
+        if self.ema is not None:
+            ts += self.ema.tensors()
         return ts + list(self._flat)
 
     def _backward_seed(self, loss):
@@ -663,9 +993,15 @@ class StepControl:
             else:
                 hip.grad_norm_scaled_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
                                          self._record, self._ls_record, self._workspace)
-            opt.step(gscale=self._fields["scale"], skip=self._fields["skip"])
+            if self._scheduled:
+                opt.step(gscale=self._fields["scale"], skip=self._fields["skip"], sched=self._sched_record,
+                         ema=None if self.ema is None else self.ema._avg)
+            else:
+                opt.step(gscale=self._fields["scale"], skip=self._fields["skip"])
             if self.scaler is not None:
                 hip.loss_scale_update_raw(self._ls_record, self._record, *self.scaler.key())
+            if self._scheduled:                     # behind the optimizer's launches and the scale's move; skipped or not
+                hip.step_sched_advance_raw(self._sched_record, *self._tables(params[0].device))
             return
         with torch.no_grad():
             grads = [p.grad for p in used]
@@ -676,10 +1012,28 @@ class StepControl:
                 torch._foreach_mul_(grads, 1.0 / scale)
             norm = torch.nn.utils.clip_grad_norm_(used, float("inf") if self.clip_norm is None else self.clip_norm)
             self._norm.copy_(norm)
+        if self._scheduled:
+            t = int(self._sched["step"])
         if finite:
-            opt.step()
+            if self.schedule is None:
+                opt.step()
+            else:                                   # every group at its own rate times the factor of this step; between
+                bases = [g["lr"] for g in opt.param_groups]     # steps the groups hold their base rates, as on the device path
+                try:
+                    for g, base in zip(opt.param_groups, bases):
+                        g["lr"] = base * self.schedule.factor(t)
+                    opt.step()
+                finally:
+                    for g, base in zip(opt.param_groups, bases):
+                        g["lr"] = base
+            if self.ema is not None:                # a skipped step leaves the averages alone
+                with torch.no_grad():
+                    torch._foreach_lerp_([self.ema.average(p) for p in used], [p.detach() for p in used], self.ema.weight(t))
         else:
             self._skipped += 1
+        if self._scheduled:                         # skipped or not: the index counts attempted steps
+            self._sched["step"].fill_(t + 1)
+            self._sched["lr_factor"].fill_(1.0 if self.schedule is None else self.schedule.factor(t + 1))
         if self.scaler is not None:
             scale, good = self.scaler.moved(scale, good, not finite)
             self._ls["scale"].fill_(scale)
@@ -790,41 +1144,48 @@ def _ckpt_dir(save_model, method):
 
 
 def save_resume(save_model, method, model, opt, epoch, control=None):
-    """train.py:254-262 (written every 5th epoch there).  A `control` with a loss scale adds its state under the extra
-    key "step_control" (the reference's loader reads the three keys it knows and ignores a fourth); without one the file
-    holds the reference's three keys and nothing else."""
+    """train.py:254-262 (written every 5th epoch there).  A `control` with a loss scale, a schedule or an EMA adds its
+    state under the extra key "step_control" (the reference's loader reads the three keys it knows and ignores the
+    others), one with an EMA the averages under "ema"; without any of them the file holds the reference's three keys and
+    nothing else."""
     d = _ckpt_dir(save_model, method)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, f"{method}_resume.pth")
     ck = {"model": model.state_dict(), "optimizer": opt.state_dict(), "epoch": epoch}
-    if control is not None and control.scaler is not None:
+    if control is not None and (control.scaler is not None or control._scheduled):
         ck["step_control"] = control.state_dict()
+    if control is not None and control.ema is not None:
+        ck["ema"] = control.ema.state_dict()
     torch.save(ck, path)
     return path
 
 
-def save_best(save_model, method, model, mae, epoch):
-    """train.py:250-253: `<method>_MAE_<mae>_<epoch+1>.pth` holds the bare state_dict."""
+def save_best(save_model, method, model, mae, epoch, ema=None):
+    """train.py:250-253: `<method>_MAE_<mae>_<epoch+1>.pth` holds the bare state_dict -- with `ema` (WeightEMA) the
+    averaged weights the MAE was measured with."""
     d = _ckpt_dir(save_model, method)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, f"{method}_MAE_{mae}_{epoch + 1}.pth")
-    torch.save(model.state_dict(), path)
+    torch.save(model.state_dict() if ema is None else ema.model_state_dict(model), path)
     return path
 
 
 def load_resume(resume, save_model, method, model, opt, map_location=None, control=None):
     """train.py:214-229.  resume=None -> 0; "last" -> the resume file (model + optimizer, continues at epoch+1);
     anything else is a state_dict path whose file name ends in `_<epoch>.pth` (continues at that number).
-    `control`: a StepControl with a loss scale continues from the state `save_resume(..., control=)` wrote, when the file
-    has one (a file written without a scaler leaves the control as it is: a fresh one starts at its `init`)."""
+    `control`: a StepControl with a loss scale, a schedule or an EMA continues from the state `save_resume(..., control=)`
+    wrote, when the file has one (a file written without leaves the control as it is: a fresh one starts at its `init`,
+    at step 0 and with averages equal to the loaded weights)."""
     if resume is None:
         return 0
     if resume == "last":
         ck = torch.load(os.path.join(_ckpt_dir(save_model, method), f"{method}_resume.pth"), map_location=map_location)
         model.load_state_dict(ck["model"], strict=True)
         opt.load_state_dict(ck["optimizer"])
-        if control is not None and control.scaler is not None and "step_control" in ck:
+        if control is not None and (control.scaler is not None or control._scheduled) and "step_control" in ck:
             control.load_state_dict(ck["step_control"])
+        if control is not None and control.ema is not None and "ema" in ck:
+            control.ema.load_state_dict(ck["ema"])
         return ck["epoch"] + 1
     model.load_state_dict(torch.load(resume, map_location=map_location), strict=True)
     return int(os.path.basename(resume).split("_")[-1].split(".")[0])
@@ -856,16 +1217,30 @@ def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_
     `control` (StepControl): `control.accumulate` consecutive batches of `batches(epoch)` make one optimizer step; a short
     last group is a step over the batches it has, as a short last batch is a step today.  With a loss scale its state
     goes into the resume file (`save_resume(..., control=)`; hand the same control to `load_resume`).
+    With `control.schedule` (LrSchedule) the rate follows the schedule per optimizer step and `adjust_learning_rate` is
+    not called: `decay_epochs` / `decay_factors` must be empty or None (two rules at once are refused), the groups' `lr`
+    stay as `get_opt` set them, a graphed step is never re-captured for the rate, and history's "lr" is base_lr times
+    the factor of the epoch's first step (from the host table).  With `control.ema` (WeightEMA) `evaluate` runs inside
+    `ema.applied(model)` and the best-MAE file holds the averaged weights.
     `loss` (SodLoss): the loss every step uses (None: `tramba_loss`)."""
     loss_fn = loss
     step_fn = train_step
+    schedule = None if control is None else control.schedule
+    ema = None if control is None else control.ema
+    if schedule is not None and (decay_epochs or decay_factors):
+        raise ValueError("fit: control.schedule sets the learning rate per step: decay_epochs / decay_factors must be empty "
+                         "(LrSchedule.step_decay states the epoch rule as a schedule)")
+    steps_done = control.state_dict()["sched_step"] if schedule is not None else 0   # (one read before the first step)
     if graph:
         from .graph import GraphedTrainStep
         graphed = GraphedTrainStep(model, opt, reducer=reducer, control=control, loss=loss_fn)
         step_fn = lambda m_, o_, images, label, reducer=None, **kw: graphed(images, label)  # noqa: E731
     history = []
     for epoch in range(start_epoch, epochs):
-        lr = adjust_learning_rate(opt, epoch, decay_epochs, base_lr, decay_factors)
+        if schedule is None:
+            lr = adjust_learning_rate(opt, epoch, decay_epochs, base_lr, decay_factors)
+        else:
+            lr = base_lr * schedule.factor(steps_done)
         total, n = None, 0
         for images, label in (batches(epoch) if control is None else _grouped(batches(epoch), control.accumulate)):
             if control is None:
@@ -874,12 +1249,17 @@ def fit(model, opt, batches, epochs, base_lr, decay_epochs, decay_factors, save_
                 loss = step_fn(model, opt, images, label, reducer=reducer, control=control, loss=loss_fn)
             total = loss.clone() if total is None else total + loss     # clone: a graphed step reuses its loss buffer
             n += 1
+        steps_done += n
         mean_loss = float(total / max(n, 1)) if total is not None else float("nan")   # one host sync per epoch
         mae = None
         if evaluate is not None and epoch + 1 >= see:
-            mae = evaluate(model, epoch)
+            if ema is None:
+                mae = evaluate(model, epoch)
+            else:
+                with ema.applied(model):
+                    mae = evaluate(model, epoch)
             if is_main and (best_mae is None or mae < best_mae):
-                save_best(save_model, method, model, mae, epoch)
+                save_best(save_model, method, model, mae, epoch, ema=ema)
         if is_main and (epoch + 1) % 5 == 0:
             save_resume(save_model, method, model, opt, epoch, control=control)
         history.append({"epoch": epoch, "lr": lr, "loss": mean_loss, "mae": mae})
