@@ -14,6 +14,11 @@ DEV = "cuda"
 SIZES = [1, 3, 4, 5, 4095, 8191, 8192, 8193, 20000]      # the vector tail, the edges of a chunk of 8192, three chunks
 MANY = [4] * 150                                          # more than two launches' worth in either argument struct
 LAYOUTS = {"aligned": (SIZES, 4), "odd": (SIZES, 1), "many": (MANY, 4)}
+EDGE_CYCLE = [1, 3, 4, 5, 8191, 8192, 8193]               # the sizes of a table filled to its last slot, and of one slot more
+
+
+def edge_sizes(count):
+    return [EDGE_CYCLE[i % len(EDGE_CYCLE)] for i in range(count)]
 HYPER = dict(beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=1e-2)
 LR = 3.7e-4
 
@@ -47,7 +52,7 @@ class _Set:
     same bits"""
 
     def __init__(self, layout, seed=3):
-        sizes, start = LAYOUTS[layout]
+        sizes, start = LAYOUTS[layout] if isinstance(layout, str) else layout
         self.sizes, self.start = sizes, start
         self.gen = torch.Generator().manual_seed(seed)
         rnd = lambda scale: (lambda n: torch.randn(n, generator=self.gen) * scale)     # noqa: E731
@@ -188,6 +193,35 @@ def test_a_set_skip_flag_leaves_every_bit_and_the_record_still_advances(layout):
     torch.cuda.synchronize()
     after = a.bits()
     assert all(not torch.equal(x, y) for x, y in zip(after[:1] + after[2:], before[:1] + before[2:])) and a.guards_intact()
+
+
+@pytest.mark.parametrize("count", [64, 65])                    # kAdamSchedTensors = 64 in csrc/loss_optim.hip
+def test_a_full_argument_table_and_one_tensor_more(count):
+    """64 tensors fill the one launch's table to its last slot (no padding, first[64] alone is the grid); 65 make two launches
+    of 33 and 32.  With record and averages, at factor 1.0: p, g, m, v as the ctl step (one launch of its 72 slots) leaves
+    them, every average moved, every tensor touched, nothing beside them."""
+    from tramba_amd import hip
+    layout = (edge_sizes(count), 4)
+    a, b = _Set(layout), _Set(layout)
+    w = float(np.float32(0.1))
+    rec, _ = hip.step_sched_record(DEV, lr_factor=1.0, ema_weight=0.1)
+    _, f = _ctl(0.5, 0)
+    for k in range(2):
+        old = {name: [v.clone() for v in getattr(a, name).views] for name in "pmve"}
+        e_old = a.e.flat.clone()
+        a.step_sched(LR, gscale=f["scale"], skip=f["skip"], sched=rec, ema=True)
+        b.step_ctl(LR, gscale=f["scale"], skip=f["skip"])
+        torch.cuda.synchronize()
+        assert _equal(a.bits()[:4], b.bits()[:4]) and torch.equal(a.steps_flat, b.steps_flat), k
+        assert bool((a.steps_flat == 3.0 + k).all())
+        inside = ~a.e.guard
+        assert _ema_misses(a.e.flat[inside], e_old[inside], a.p.flat[inside], w) == 0, k
+        for name, views in old.items():
+            same = [i for i, (x, y) in enumerate(zip(views, getattr(a, name).views)) if torch.equal(x, y)]
+            assert not same, (k, name, same)
+        assert a.guards_intact() and b.guards_intact(), k
+        a.new_grads()
+        b.new_grads()
 
 
 # ------------------------------------------------------------------------------------------------- 2. tramba_step_sched_advance

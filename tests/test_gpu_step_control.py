@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from oracle import ops as oo
+from test_gpu_sched_ema import _Flat, edge_sizes
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -86,6 +87,23 @@ def test_grad_accumulate_many_tensors_span_several_launches():
     assert all(torch.equal(c, x + y) for c, x, y in zip(acc, a, b))
 
 
+@pytest.mark.parametrize("count", [128, 129])                  # kAccTensors = 128 in csrc/loss_optim.hip
+def test_grad_accumulate_fills_its_table_and_one_slot_more(count):
+    """128 tensors fill the one launch's table to its last slot; 129 make two launches of 65 and 64"""
+    from tramba_amd import hip
+    g = torch.Generator().manual_seed(16)
+    sizes = edge_sizes(count)
+    a = [torch.randn(n, generator=g).to(DEV) for n in sizes]
+    b = [torch.randn(n, generator=g).to(DEV) for n in sizes]
+    acc = [torch.full((n,), float("nan"), device=DEV) for n in sizes]      # a tensor that no workgroup visits keeps its NaNs
+    rec, f = hip.step_ctl_record(DEV)
+    for gs in (a, b):
+        hip.grad_accumulate_raw(hip.pointer_array(acc), hip.pointer_array(gs), _numel(acc), count, rec)
+    assert int(f["micro"]) == 2
+    wrong = [i for i, (c, x, y) in enumerate(zip(acc, a, b)) if not torch.equal(c, x + y)]
+    assert not wrong, wrong
+
+
 # ------------------------------------------------------------------------------------------------- tramba_grad_norm
 def _norm(tensors, mean_scale=1.0, max_norm=0.0, skip_nonfinite=True, rec=None):
     from tramba_amd import hip
@@ -134,6 +152,27 @@ def test_grad_norm_many_tensors_span_several_launches():
     assert torch.equal(_norm(ts, 0.5, 0.0)[0], rec)
     ts[650][-1] = float("nan")                                   # a small tensor of a late launch
     assert int(_norm(ts, 0.5, 0.0)[1]["skip"]) == 1
+
+
+@pytest.mark.parametrize("count", [160, 161])                  # kNormTensors = 160 in csrc/loss_optim.hip
+def test_grad_norm_fills_its_table_and_one_slot_more(count):
+    """160 tensors fill the one launch's table to its last slot; 161 make two launches of 81 and 80"""
+    g = torch.Generator().manual_seed(17)
+    host = [torch.randn(n, generator=g) * 10.0 ** (i % 4 - 2) for i, n in enumerate(edge_sizes(count))]
+    want = float(np.sqrt(sum(float((t.numpy().astype(np.float64) ** 2).sum()) for t in host)))
+    ts = [t.to(DEV) for t in host]
+    rec, f = _norm(ts, 0.5, 0.0)
+    print(f"{count} tensors: norm {float(f['norm'])!r} want {0.5 * want!r} rel {abs(float(f['norm']) / (0.5 * want) - 1):.3e}")
+    assert abs(float(f["norm"]) - 0.5 * want) <= BOUND * 0.5 * want and int(f["skip"]) == 0
+    assert torch.equal(_norm(ts, 0.5, 0.0)[0], rec)                        # two runs: identical bits
+    # the sum would not miss a single element at 0.01: a NaN in the last element of each tensor in turn, the last tensor's
+    # among them, must raise the flag
+    for i in range(count):
+        was = ts[i][-1].clone()
+        ts[i][-1] = float("nan")
+        assert int(_norm(ts, 0.5, 0.0)[1]["skip"]) == 1, i
+        ts[i][-1] = was
+    assert torch.equal(_norm(ts, 0.5, 0.0)[0], rec)
 
 
 def test_grad_norm_survives_a_square_that_overflows_fp32():
@@ -241,6 +280,40 @@ def test_adam_step_ctl(wd):
     st = [opt.state[p] for p in params]
     assert _same(([p.detach() for p in params], [s["exp_avg"] for s in st], [s["exp_avg_sq"] for s in st],
                   [s["step"] for s in st]), two)
+
+
+@pytest.mark.parametrize("count", [72, 73])                    # kAdamTensors = 72 in csrc/loss_optim.hip
+def test_adam_step_ctl_fills_its_table_and_one_slot_more(count):
+    """72 tensors fill the one launch's table to its last slot; 73 make two launches of 37 and 36.  Every tensor against the
+    fp64 oracle at test_adam_step_ctl's tolerance, guard elements on either side of each."""
+    from tramba_amd import hip
+    g = torch.Generator().manual_seed(18)
+    sizes = edge_sizes(count)
+    init = [torch.randn(n, generator=g) for n in sizes]
+    steps = [[torch.randn(n, generator=g) * (10.0 ** (i % 3 - 2)) for i, n in enumerate(sizes)] for _ in range(2)]
+    start = iter(init)
+    p = _Flat(sizes, 4, lambda n: next(start))
+    gr, m, v = (_Flat(sizes, 4, torch.zeros) for _ in range(3))
+    ts = torch.zeros(count, device=DEV)
+    sc, zero = torch.full((), 0.3, device=DEV), torch.zeros((), dtype=torch.int32, device=DEV)
+    for grads in steps:
+        for view, x in zip(gr.views, grads):
+            view.copy_(x)
+        rc = hip.lib().tramba_adam_step_ctl(hip.pointer_array(p.views), hip.pointer_array(gr.views), hip.pointer_array(m.views),
+                                            hip.pointer_array(v.views), hip.pointer_array([ts[i] for i in range(count)]),
+                                            (ctypes.c_int64 * count)(*sizes), count, 1e-2, 0.9, 0.999, 1e-8, 0.01,
+                                            sc.data_ptr(), zero.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert rc == 0
+    torch.cuda.synchronize()
+    want_p, want_m, want_v = oo.adam_steps(init, [[x.double() * float(sc) for x in grads] for grads in steps], 1e-2, (0.9, 0.999),
+                                           1e-8, 0.01)
+    for i in range(count):
+        errs = _rel_l2(p.views[i], want_p[i]), _rel_l2(m.views[i], want_m[i]), _rel_l2(v.views[i], want_v[i])
+        assert max(errs) < 1e-6, (i, sizes[i], errs)
+    assert bool((ts == 2.0).all())
+    assert all(t.guards_intact() for t in (p, gr, m, v))
+    for view, x in zip(gr.views, steps[-1]):                               # the gradients are read, never written
+        assert torch.equal(view.cpu(), x)
 
 
 def test_adam_step_ctl_replay_follows_the_record():

@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace tramba {
@@ -347,7 +348,31 @@ __global__ __launch_bounds__(256) void loss_weight_map_kernel(const float *__res
 }
 
 // ------------------------------------------------------------------------------------------------- Adam
-constexpr int kAdamTensors = 72, kAdamChunk = 8192, kAdamThreads = 256, kBumpTensors = 448;
+constexpr int kAdamTensors = 72, kAdamSchedTensors = 64, kAdamChunk = 8192, kAdamThreads = 256, kBumpTensors = 448;
+
+// The tensors of one launch, BY VALUE in the kernel arguments: a workgroup per chunk of kAdamChunk elements, tensor after
+// tensor.  Every multi-tensor kernel of the optimizer step takes one of these (with its own fields behind it) and finds
+// its tensor with tensor_of_block; deal_launches (below, on the host) fills them.
+template <class T, int CAP>
+struct TensorTable {
+    static constexpr int kCap = CAP;
+    T t[CAP];                      // (unused slots: zeros)
+    int first[CAP + 1];            // first workgroup of each tensor (ascending); first[count..CAP] = the grid
+    int count;
+};
+
+// the tensor this workgroup works on: first[i] <= blockIdx.x < first[i + 1]
+template <typename A>
+__device__ __forceinline__ int tensor_of_block(const A &a)
+{
+    int lo = 0, hi = a.count;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 struct AdamTensor {
     float *p;
     const float *g;
@@ -355,20 +380,30 @@ struct AdamTensor {
     const float *step;
     long n;
 };
-struct AdamArgs {
-    AdamTensor t[kAdamTensors];
-    int first[kAdamTensors + 1];   // first workgroup of each tensor (ascending); first[count] = the grid
-    int count;
+struct AdamSchedTensor : AdamTensor {
+    float *e;                      // the average (null: this tensor keeps none)
+};
+struct AdamHyper {
     double lr, beta1, beta2, eps, weight_decay;
     const float *gscale;           // device scalar the gradient is multiplied by first (null: the gradient as it is)
     const int *skip;               // device flag: non-zero = this launch changes nothing (null: never)
+};
+// tramba_adam_step / _ctl: 72 tensors of six words.  tramba_adam_step_sched with a record: a seventh pointer per tensor,
+// so 64 of them (3912 of the 4096 bytes), and the record the learning-rate factor and the averages' weight live in.
+struct AdamArgs : TensorTable<AdamTensor, kAdamTensors> {
+    AdamHyper h;
+};
+struct AdamSchedArgs : TensorTable<AdamSchedTensor, kAdamSchedTensors> {
+    AdamHyper h;
+    const tramba_step_sched *sched;   // never null (the entry hands a call without one to adam_kernel)
 };
 struct BumpArgs {
     float *step[kBumpTensors];
     int count;
     const int *skip;
 };
-static_assert(sizeof(AdamArgs) <= 4096 && sizeof(BumpArgs) <= 4096, "kernel arguments are limited to 4 KB");
+static_assert(sizeof(AdamArgs) <= 4096 && sizeof(AdamSchedArgs) <= 4096 && sizeof(BumpArgs) <= 4096,
+              "kernel arguments are limited to 4 KB");
 
 __global__ __launch_bounds__(kBumpTensors) void adam_bump_kernel(BumpArgs a)
 {
@@ -413,119 +448,15 @@ __device__ __forceinline__ void adam_math(float &p, float g, float &m, float &v,
     p -= c.step_size * m / denom;
 }
 
-template <bool ALIGNED>
-__device__ __forceinline__ void adam_chunk(const AdamTensor &t, long off, const AdamCoef &c)
-{
-    const long left = t.n - off;
-    const int here = left < kAdamChunk ? (int)left : kAdamChunk;
-    const int nvec = here >> 2;
-    float *p = t.p + off, *m = t.m + off, *v = t.v + off;
-    const float *g = t.g + off;
-    constexpr int U = 4;
-    for (int j0 = threadIdx.x; j0 < nvec; j0 += U * kAdamThreads) {
-        adam_f4 pp[U], gg[U], mm[U], vv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * kAdamThreads;
-            if (j < nvec) {
-                gg[u] = adam_load<ALIGNED>(g + 4 * j);
-                pp[u] = adam_load<ALIGNED>(p + 4 * j);
-                mm[u] = adam_load<ALIGNED>(m + 4 * j);
-                vv[u] = adam_load<ALIGNED>(v + 4 * j);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int j = j0 + u * kAdamThreads;
-            if (j < nvec) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float pe = pp[u][e], me = mm[u][e], ve = vv[u][e];
-                    adam_math(pe, gg[u][e], me, ve, c);
-                    pp[u][e] = pe;
-                    mm[u][e] = me;
-                    vv[u][e] = ve;
-                }
-                adam_store<ALIGNED>(p + 4 * j, pp[u]);
-                adam_store<ALIGNED>(m + 4 * j, mm[u]);
-                adam_store<ALIGNED>(v + 4 * j, vv[u]);
-            }
-        }
-    }
-    const int j = (nvec << 2) + threadIdx.x;     // < 4 trailing elements of the tensor
-    if (j < here) {
-        float pe = p[j], me = m[j], ve = v[j];
-        adam_math(pe, g[j], me, ve, c);
-        p[j] = pe;
-        m[j] = me;
-        v[j] = ve;
-    }
-}
-
-__global__ __launch_bounds__(kAdamThreads) void adam_kernel(AdamArgs a)
-{
-    __shared__ float corr[2];
-    if (a.skip && *a.skip) return;                // (uniform over the grid: parameters and moments keep their bits)
-    int lo = 0, hi = a.count;                     // the tensor this workgroup works on: first[lo] <= blockIdx.x < first[lo + 1]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const AdamTensor t = a.t[lo];
-    const long off = (long)((int)blockIdx.x - a.first[lo]) * kAdamChunk;
-    if (threadIdx.x == 0) {                       // the bias corrections in double, as the reference's optimizer computes them
-        const double s = (double)*t.step;
-        corr[0] = (float)(a.lr / (1.0 - pow(a.beta1, s)));
-        corr[1] = (float)sqrt(1.0 - pow(a.beta2, s));
-    }
-    __syncthreads();
-    AdamCoef c;
-    c.step_size = corr[0];
-    c.bc2_sqrt = corr[1];
-    c.b1w = (float)(1.0 - a.beta1);
-    c.beta2 = (float)a.beta2;
-    c.b2w = (float)(1.0 - a.beta2);
-    c.eps = (float)a.eps;
-    c.wd = (float)a.weight_decay;
-    c.scaled = a.gscale != nullptr;
-    c.gs = c.scaled ? *a.gscale : 1.f;
-    const bool al = ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
-                      reinterpret_cast<uintptr_t>(t.v)) & 15) == 0;
-    if (al) adam_chunk<true>(t, off, c); else adam_chunk<false>(t, off, c);
-}
-
-// ------------------------------------------------------------------------------------------------- scheduled Adam (+ EMA)
-// tramba_adam_step_sched: adam_kernel's step with the learning rate multiplied by a factor that lives in a device record
-// (tramba_step_sched) and, when the tensor has one, an exponential moving average of the parameter moved in the same pass:
-// e = fmaf(w, p_new - e, e), one more read and write per element (36 B instead of 28).  A tensor carries a seventh
-// pointer here, so a launch holds fewer of them; adam_kernel and its argument struct stay as they are.
-constexpr int kAdamSchedTensors = 64;
-struct AdamSchedTensor {
-    float *p;
-    const float *g;
-    float *m, *v;
-    const float *step;
-    long n;
-    float *e;                      // the average (null: this tensor keeps none)
-};
-struct AdamSchedArgs {
-    AdamSchedTensor t[kAdamSchedTensors];
-    int first[kAdamSchedTensors + 1];
-    int count;
-    double lr, beta1, beta2, eps, weight_decay;
-    const float *gscale;
-    const int *skip;
-    const tramba_step_sched *sched;   // never null here (the entry hands a call without one to adam_kernel)
-};
-static_assert(sizeof(AdamSchedArgs) <= 4096, "kernel arguments are limited to 4 KB");
-
+// One chunk of one tensor.  EMA: the tensor keeps an average, moved in the same pass by e = fmaf(w, p_new - e, e): one more
+// read and write per element (36 B instead of 28).
 template <bool ALIGNED, bool EMA>
-__device__ __forceinline__ void adam_sched_chunk(const AdamSchedTensor &t, long off, const AdamCoef &c, float w)
+__device__ __forceinline__ void adam_chunk(const AdamTensor &t, float *avg, long off, const AdamCoef &c, float w)
 {
     const long left = t.n - off;
     const int here = left < kAdamChunk ? (int)left : kAdamChunk;
     const int nvec = here >> 2;
-    float *p = t.p + off, *m = t.m + off, *v = t.v + off, *e = EMA ? t.e + off : nullptr;
+    float *p = t.p + off, *m = t.m + off, *v = t.v + off, *e = EMA ? avg + off : nullptr;
     const float *g = t.g + off;
     constexpr int U = 4;
     for (int j0 = threadIdx.x; j0 < nvec; j0 += U * kAdamThreads) {
@@ -572,44 +503,51 @@ __device__ __forceinline__ void adam_sched_chunk(const AdamSchedTensor &t, long 
     }
 }
 
-__global__ __launch_bounds__(kAdamThreads) void adam_sched_kernel(AdamSchedArgs a)
+// The one Adam kernel body.  With a schedule record (AdamSchedArgs) the step runs at lr times the record's factor, and a
+// tensor that carries an average moves it; without one (AdamArgs) neither is compiled in and no record is read.
+template <class ARGS>
+__device__ __forceinline__ void adam_body(const ARGS &a)
 {
+    constexpr bool SCHED = std::is_same<ARGS, AdamSchedArgs>::value;
     __shared__ float corr[2];
-    if (a.skip && *a.skip) return;                // (uniform over the grid: the averages keep their bits with everything else)
-    int lo = 0, hi = a.count;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    const AdamSchedTensor t = a.t[lo];
-    const long off = (long)((int)blockIdx.x - a.first[lo]) * kAdamChunk;
-    if (threadIdx.x == 0) {                       // adam_kernel's corrections at lr * factor: one more double product
+    if (a.h.skip && *a.h.skip) return;            // (uniform over the grid: parameters, moments and averages keep their bits)
+    const int ti = tensor_of_block(a);
+    const auto t = a.t[ti];
+    const long off = (long)((int)blockIdx.x - a.first[ti]) * kAdamChunk;
+    if (threadIdx.x == 0) {                       // the bias corrections in double, as the reference's optimizer computes them
         const double s = (double)*t.step;
-        const double lr = a.lr * a.sched->lr_factor;
-        corr[0] = (float)(lr / (1.0 - pow(a.beta1, s)));
-        corr[1] = (float)sqrt(1.0 - pow(a.beta2, s));
+        double lr = a.h.lr;
+        if constexpr (SCHED) lr = a.h.lr * a.sched->lr_factor;
+        corr[0] = (float)(lr / (1.0 - pow(a.h.beta1, s)));
+        corr[1] = (float)sqrt(1.0 - pow(a.h.beta2, s));
     }
     __syncthreads();
     AdamCoef c;
     c.step_size = corr[0];
     c.bc2_sqrt = corr[1];
-    c.b1w = (float)(1.0 - a.beta1);
-    c.beta2 = (float)a.beta2;
-    c.b2w = (float)(1.0 - a.beta2);
-    c.eps = (float)a.eps;
-    c.wd = (float)a.weight_decay;
-    c.scaled = a.gscale != nullptr;
-    c.gs = c.scaled ? *a.gscale : 1.f;
-    const uintptr_t bits = reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
-                           reinterpret_cast<uintptr_t>(t.v) | reinterpret_cast<uintptr_t>(t.e);
+    c.b1w = (float)(1.0 - a.h.beta1);
+    c.beta2 = (float)a.h.beta2;
+    c.b2w = (float)(1.0 - a.h.beta2);
+    c.eps = (float)a.h.eps;
+    c.wd = (float)a.h.weight_decay;
+    c.scaled = a.h.gscale != nullptr;
+    c.gs = c.scaled ? *a.h.gscale : 1.f;
+    uintptr_t bits = reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.g) | reinterpret_cast<uintptr_t>(t.m) |
+                     reinterpret_cast<uintptr_t>(t.v);
+    if constexpr (SCHED) bits |= reinterpret_cast<uintptr_t>(t.e);
     const bool al = (bits & 15) == 0;
-    if (t.e) {
-        const float w = a.sched->ema_weight;
-        if (al) adam_sched_chunk<true, true>(t, off, c, w); else adam_sched_chunk<false, true>(t, off, c, w);
-    } else {
-        if (al) adam_sched_chunk<true, false>(t, off, c, 0.f); else adam_sched_chunk<false, false>(t, off, c, 0.f);
+    if constexpr (SCHED) {
+        if (t.e) {
+            const float w = a.sched->ema_weight;
+            if (al) adam_chunk<true, true>(t, t.e, off, c, w); else adam_chunk<false, true>(t, t.e, off, c, w);
+            return;
+        }
     }
+    if (al) adam_chunk<true, false>(t, nullptr, off, c, 0.f); else adam_chunk<false, false>(t, nullptr, off, c, 0.f);
 }
+
+__global__ __launch_bounds__(kAdamThreads) void adam_kernel(AdamArgs a) { adam_body(a); }
+__global__ __launch_bounds__(kAdamThreads) void adam_sched_kernel(AdamSchedArgs a) { adam_body(a); }
 
 // The schedule record's move after a step: one lane, behind the optimizer's launches (and the loss scale's move).  It does
 // not read the skip flag: the index counts the steps that were attempted.
@@ -632,35 +570,19 @@ struct AccTensor {
     const float *g;                // null: this micro-batch produced no gradient for the tensor (zeros)
     long n;
 };
-struct AccArgs {
-    AccTensor t[kAccTensors];
-    int first[kAccTensors + 1];
-    int count;
+struct AccArgs : TensorTable<AccTensor, kAccTensors> {
     const tramba_step_ctl *ctl;
 };
 struct NormTensor {
     const float *g;
     long n;
 };
-struct NormArgs {
-    NormTensor t[kNormTensors];
-    int first[kNormTensors + 1];
-    int count, chunk_base;         // this launch's first slot in the tables of partials
+struct NormArgs : TensorTable<NormTensor, kNormTensors> {
+    int chunk_base;                // this launch's first slot in the tables of partials
     double *part;
     unsigned *bad;
 };
 static_assert(sizeof(AccArgs) <= 4096 && sizeof(NormArgs) <= 4096, "kernel arguments are limited to 4 KB");
-
-template <typename A>
-__device__ __forceinline__ int tensor_of_block(const A &a)
-{
-    int lo = 0, hi = a.count;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (a.first[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // acc = g on the first micro-batch of a step (ctl->micro == 0), acc += g afterwards
 template <bool ALIGNED>
@@ -856,6 +778,43 @@ static std::vector<std::vector<int>> snake_bins(const int64_t *numel, int count,
     return bins;
 }
 
+// chunks (= workgroups) over all tensors of a call, -1 beyond what a grid holds
+static long norm_chunks(const int64_t *numel, int count)
+{
+    long n = 0;
+    for (int i = 0; i < count; ++i) {
+        if (numel[i] <= 0) return -1;
+        n += (numel[i] + kAdamChunk - 1) / kAdamChunk;
+        if (n >= 2147483647L) return -1;
+    }
+    return n;
+}
+
+// The launches of one call over `count` tensors of numel[] elements: the tensors are dealt to ceil(count / ARGS::kCap)
+// launches (a launch of 72 bias vectors alone would put 72 workgroups on 256 CUs; the order does not matter, the tensors
+// are independent), make(j) is the record of tensor j, launch(table, workgroups) fills in the kernel's own fields and
+// starts it.  A call that would not fit a grid is refused before its first launch.
+template <class ARGS, class MAKE, class LAUNCH>
+static int deal_launches(const char *who, const int64_t *numel, int count, MAKE make, LAUNCH launch)
+{
+    TRAMBA_CHECK(norm_chunks(numel, count) > 0, "%s: too many workgroups", who);
+    for (const std::vector<int> &bin : snake_bins(numel, count, ARGS::kCap)) {
+        ARGS a;
+        long blocks = 0;
+        const int c = (int)bin.size();             // <= kCap by construction
+        for (int i = 0; i < c; ++i) {
+            a.t[i] = make(bin[i]);
+            a.first[i] = (int)blocks;
+            blocks += (numel[bin[i]] + kAdamChunk - 1) / kAdamChunk;
+        }
+        for (int i = c; i < ARGS::kCap; ++i) a.t[i] = {};
+        for (int i = c; i <= ARGS::kCap; ++i) a.first[i] = (int)blocks;
+        a.count = c;
+        if (const int e = launch(a, (unsigned)blocks)) return e;
+    }
+    return TRAMBA_OK;
+}
+
 }  // namespace tramba
 
 using namespace tramba;
@@ -1020,17 +979,23 @@ extern "C" int tramba_sod_wloss_grad(const float *logits, const float *label, co
                      wout, stream);
 }
 
-static int adam_step_impl(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
-                          float *const *steps, const int64_t *numel, int count, double lr, double beta1, double beta2,
-                          double eps, double weight_decay, const float *gscale, const int *skip, void *stream)
+// The one Adam entry behind tramba_adam_step (gscale, skip, ema, sched null), tramba_adam_step_ctl (ema, sched null) and
+// tramba_adam_step_sched; `who` names the entry in the error texts.  sched null: adam_kernel, which reads no record.
+static int adam_step_impl(const char *who, float *const *params, const float *const *grads, float *const *exp_avg,
+                          float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, const float *gscale, const int *skip, float *const *ema,
+                          const tramba_step_sched *sched, void *stream)
 {
-    TRAMBA_CHECK(params && grads && exp_avg && exp_avg_sq && steps && numel && count > 0, "adam_step: empty input");
+    TRAMBA_CHECK(params && grads && exp_avg && exp_avg_sq && steps && numel && count > 0, "%s: empty input", who);
     TRAMBA_CHECK(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0,
-                 "adam_step: bad hyper-parameters");
+                 "%s: bad hyper-parameters", who);
     hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < count; ++i)
+    for (int i = 0; i < count; ++i) {
         TRAMBA_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && steps[i] && numel[i] > 0,
-                     "adam_step: tensor %d: null pointer or no elements", i);
+                     "%s: tensor %d: null pointer or no elements", who, i);
+        TRAMBA_CHECK(!ema || ema[i], "%s: tensor %d: null average", who, i);
+    }
+    TRAMBA_CHECK(norm_chunks(numel, count) > 0, "%s: too many workgroups", who);   // (before the counters move)
     for (int base = 0; base < count; base += kBumpTensors) {     // t += 1 on the device (the counters are part of the state_dict)
         BumpArgs b;
         b.count = count - base < kBumpTensors ? count - base : kBumpTensors;
@@ -1039,39 +1004,32 @@ static int adam_step_impl(float *const *params, const float *const *grads, float
         hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(kBumpTensors), 0, s, b);
         TRAMBA_LAUNCH_CHECK();
     }
-    // Launches of equal weight: the tensors are dealt to ceil(count / 72) launches largest first, in snake order (a launch of
-    // 72 bias vectors alone would put 72 workgroups on 256 CUs; the order of the updates does not matter, they are independent).
-    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAdamTensors);
-    for (size_t l = 0; l < bins.size(); ++l) {
-        AdamArgs a;
-        long blocks = 0;
-        const int c = (int)bins[l].size();           // <= kAdamTensors by construction
-        for (int i = 0; i < c; ++i) {
-            const int j = bins[l][i];
-            const long nb = (numel[j] + kAdamChunk - 1) / kAdamChunk;
-            TRAMBA_CHECK(blocks + nb < 2147483647L, "adam_step: too many workgroups");
-            a.t[i] = AdamTensor{params[j], grads[j], exp_avg[j], exp_avg_sq[j], steps[j], (long)numel[j]};
-            a.first[i] = (int)blocks;
-            blocks += nb;
-        }
-        a.count = c;
-        for (int i = c; i <= kAdamTensors; ++i) a.first[i] = (int)blocks;
-        for (int i = c; i < kAdamTensors; ++i) a.t[i] = AdamTensor{nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-        a.gscale = gscale;
-        a.skip = skip;
-        hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
-        TRAMBA_LAUNCH_CHECK();
-    }
-    return TRAMBA_OK;
+    const AdamHyper h{lr, beta1, beta2, eps, weight_decay, gscale, skip};
+    auto tensor = [&](int j) { return AdamTensor{params[j], grads[j], exp_avg[j], exp_avg_sq[j], steps[j], (long)numel[j]}; };
+    if (!sched)
+        return deal_launches<AdamArgs>(who, numel, count, tensor, [&](AdamArgs &a, unsigned blocks) -> int {
+            a.h = h;
+            hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(kAdamThreads), 0, s, a);
+            TRAMBA_LAUNCH_CHECK();
+            return TRAMBA_OK;
+        });
+    return deal_launches<AdamSchedArgs>(
+        who, numel, count, [&](int j) { return AdamSchedTensor{tensor(j), ema ? ema[j] : nullptr}; },
+        [&](AdamSchedArgs &a, unsigned blocks) -> int {
+            a.h = h;
+            a.sched = sched;
+            hipLaunchKernelGGL(adam_sched_kernel, dim3(blocks), dim3(kAdamThreads), 0, s, a);
+            TRAMBA_LAUNCH_CHECK();
+            return TRAMBA_OK;
+        });
 }
 
 extern "C" int tramba_adam_step(float *const *params, const float *const *grads, float *const *exp_avg,
                                 float *const *exp_avg_sq, float *const *steps, const int64_t *numel, int count, double lr,
                                 double beta1, double beta2, double eps, double weight_decay, void *stream)
 {
-    return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, nullptr,
-                          nullptr, stream);
+    return adam_step_impl("adam_step", params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay,
+                          nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" int tramba_adam_step_ctl(float *const *params, const float *const *grads, float *const *exp_avg,
@@ -1079,8 +1037,8 @@ extern "C" int tramba_adam_step_ctl(float *const *params, const float *const *gr
                                     double beta1, double beta2, double eps, double weight_decay, const float *gscale,
                                     const int *skip, void *stream)
 {
-    return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, gscale,
-                          skip, stream);
+    return adam_step_impl("adam_step_ctl", params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps,
+                          weight_decay, gscale, skip, nullptr, nullptr, stream);
 }
 
 extern "C" int tramba_adam_step_sched(float *const *params, const float *const *grads, float *const *exp_avg,
@@ -1089,51 +1047,8 @@ extern "C" int tramba_adam_step_sched(float *const *params, const float *const *
                                       const int *skip, float *const *ema, const tramba_step_sched *sched, void *stream)
 {
     TRAMBA_CHECK(sched || !ema, "adam_step_sched: an average needs the schedule record (its weight lives there)");
-    if (!sched)
-        return adam_step_impl(params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps, weight_decay, gscale,
-                              skip, stream);
-    TRAMBA_CHECK(params && grads && exp_avg && exp_avg_sq && steps && numel && count > 0, "adam_step_sched: empty input");
-    TRAMBA_CHECK(lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0 && weight_decay >= 0.0,
-                 "adam_step_sched: bad hyper-parameters");
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < count; ++i) {
-        TRAMBA_CHECK(params[i] && grads[i] && exp_avg[i] && exp_avg_sq[i] && steps[i] && numel[i] > 0,
-                     "adam_step_sched: tensor %d: null pointer or no elements", i);
-        TRAMBA_CHECK(!ema || ema[i], "adam_step_sched: tensor %d: null average", i);
-    }
-    for (int base = 0; base < count; base += kBumpTensors) {
-        BumpArgs b;
-        b.count = count - base < kBumpTensors ? count - base : kBumpTensors;
-        for (int i = 0; i < kBumpTensors; ++i) b.step[i] = i < b.count ? steps[base + i] : nullptr;
-        b.skip = skip;
-        hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(kBumpTensors), 0, s, b);
-        TRAMBA_LAUNCH_CHECK();
-    }
-    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAdamSchedTensors);
-    for (size_t l = 0; l < bins.size(); ++l) {
-        AdamSchedArgs a;
-        long blocks = 0;
-        const int c = (int)bins[l].size();           // <= kAdamSchedTensors by construction
-        for (int i = 0; i < c; ++i) {
-            const int j = bins[l][i];
-            const long nb = (numel[j] + kAdamChunk - 1) / kAdamChunk;
-            TRAMBA_CHECK(blocks + nb < 2147483647L, "adam_step_sched: too many workgroups");
-            a.t[i] = AdamSchedTensor{params[j], grads[j], exp_avg[j], exp_avg_sq[j], steps[j], (long)numel[j],
-                                     ema ? ema[j] : nullptr};
-            a.first[i] = (int)blocks;
-            blocks += nb;
-        }
-        a.count = c;
-        for (int i = c; i <= kAdamSchedTensors; ++i) a.first[i] = (int)blocks;
-        for (int i = c; i < kAdamSchedTensors; ++i) a.t[i] = AdamSchedTensor{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-        a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.weight_decay = weight_decay;
-        a.gscale = gscale;
-        a.skip = skip;
-        a.sched = sched;
-        hipLaunchKernelGGL(adam_sched_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
-        TRAMBA_LAUNCH_CHECK();
-    }
-    return TRAMBA_OK;
+    return adam_step_impl("adam_step_sched", params, grads, exp_avg, exp_avg_sq, steps, numel, count, lr, beta1, beta2, eps,
+                          weight_decay, gscale, skip, ema, sched, stream);
 }
 
 extern "C" int tramba_step_sched_advance(tramba_step_sched *rec, const double *lr_table, int64_t n_lr, const float *ema_table,
@@ -1148,18 +1063,6 @@ extern "C" int tramba_step_sched_advance(tramba_step_sched *rec, const double *l
     return TRAMBA_OK;
 }
 
-// chunks (= workgroups) over all tensors of a call, -1 beyond what a grid holds
-static long norm_chunks(const int64_t *numel, int count)
-{
-    long n = 0;
-    for (int i = 0; i < count; ++i) {
-        if (numel[i] <= 0) return -1;
-        n += (numel[i] + kAdamChunk - 1) / kAdamChunk;
-        if (n >= 2147483647L) return -1;
-    }
-    return n;
-}
-
 extern "C" int tramba_grad_accumulate(float *const *acc, const float *const *grads, const int64_t *numel, int count,
                                       tramba_step_ctl *ctl, void *stream)
 {
@@ -1167,26 +1070,16 @@ extern "C" int tramba_grad_accumulate(float *const *acc, const float *const *gra
     TRAMBA_CHECK(count > 0, "grad_accumulate: count must be positive (got %d)", count);
     for (int i = 0; i < count; ++i)
         TRAMBA_CHECK(acc[i] && numel[i] > 0, "grad_accumulate: tensor %d: null accumulator or no elements", i);
-    TRAMBA_CHECK(norm_chunks(numel, count) > 0, "grad_accumulate: too many workgroups");   // (before the first launch)
     hipStream_t s = (hipStream_t)stream;
-    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kAccTensors);
-    for (size_t l = 0; l < bins.size(); ++l) {
-        AccArgs a;
-        long blocks = 0;
-        const int c = (int)bins[l].size();
-        for (int i = 0; i < c; ++i) {
-            const int j = bins[l][i];
-            a.t[i] = AccTensor{acc[j], grads[j], (long)numel[j]};
-            a.first[i] = (int)blocks;
-            blocks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
-        }
-        a.count = c;
-        for (int i = c; i <= kAccTensors; ++i) a.first[i] = (int)blocks;
-        for (int i = c; i < kAccTensors; ++i) a.t[i] = AccTensor{nullptr, nullptr, 0};
-        a.ctl = ctl;
-        hipLaunchKernelGGL(grad_accumulate_kernel, dim3((unsigned)blocks), dim3(kAdamThreads), 0, s, a);
-        TRAMBA_LAUNCH_CHECK();
-    }
+    const int e = deal_launches<AccArgs>(
+        "grad_accumulate", numel, count, [&](int j) { return AccTensor{acc[j], grads[j], (long)numel[j]}; },
+        [&](AccArgs &a, unsigned blocks) -> int {
+            a.ctl = ctl;
+            hipLaunchKernelGGL(grad_accumulate_kernel, dim3(blocks), dim3(kAdamThreads), 0, s, a);
+            TRAMBA_LAUNCH_CHECK();
+            return TRAMBA_OK;
+        });
+    if (e) return e;
     hipLaunchKernelGGL(step_ctl_advance_kernel, dim3(1), dim3(kWave), 0, s, ctl);   // after every read of the counter
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
@@ -1209,34 +1102,25 @@ static int grad_norm_impl(const float *const *grads, const int64_t *numel, int c
     for (int i = 0; i < count; ++i)
         TRAMBA_CHECK(grads[i] && numel[i] > 0, "grad_norm: tensor %d: null pointer or no elements", i);
     const long nchunk = norm_chunks(numel, count);
-    TRAMBA_CHECK(nchunk > 0, "grad_norm: too many workgroups");
+    TRAMBA_CHECK(nchunk > 0, "grad_norm: too many workgroups");   // (here: the workspace's layout follows from the count)
     TRAMBA_CHECK(workspace_bytes >= tramba_grad_norm_workspace(numel, count) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                  "grad_norm: an 8-byte aligned workspace of %zu bytes needed", tramba_grad_norm_workspace(numel, count));
     hipStream_t s = (hipStream_t)stream;
     double *part = (double *)workspace;
     unsigned *bad = (unsigned *)(part + nchunk);
-    const std::vector<std::vector<int>> bins = snake_bins(numel, count, kNormTensors);
     long base = 0;
-    for (size_t l = 0; l < bins.size(); ++l) {
-        NormArgs a;
-        long blocks = 0;
-        const int c = (int)bins[l].size();
-        for (int i = 0; i < c; ++i) {
-            const int j = bins[l][i];
-            a.t[i] = NormTensor{grads[j], (long)numel[j]};
-            a.first[i] = (int)blocks;
-            blocks += (numel[j] + kAdamChunk - 1) / kAdamChunk;
-        }
-        a.count = c;
-        for (int i = c; i <= kNormTensors; ++i) a.first[i] = (int)blocks;
-        for (int i = c; i < kNormTensors; ++i) a.t[i] = NormTensor{nullptr, 0};
-        a.chunk_base = (int)base;
-        a.part = part;
-        a.bad = bad;
-        hipLaunchKernelGGL(grad_norm_parts_kernel, dim3((unsigned)blocks), dim3(kNormThreads), 0, s, a);
-        TRAMBA_LAUNCH_CHECK();
-        base += blocks;
-    }
+    const int e = deal_launches<NormArgs>(
+        "grad_norm", numel, count, [&](int j) { return NormTensor{grads[j], (long)numel[j]}; },
+        [&](NormArgs &a, unsigned blocks) -> int {
+            a.chunk_base = (int)base;
+            a.part = part;
+            a.bad = bad;
+            hipLaunchKernelGGL(grad_norm_parts_kernel, dim3(blocks), dim3(kNormThreads), 0, s, a);
+            TRAMBA_LAUNCH_CHECK();
+            base += blocks;
+            return TRAMBA_OK;
+        });
+    if (e) return e;
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kNormFinishThreads), 0, s, part, bad, (int)nchunk, mean_scale,
                        max_norm, skip_nonfinite, ctl, ls);
     TRAMBA_LAUNCH_CHECK();

@@ -1417,24 +1417,27 @@ def sod_wloss_grad(output, label, wmap, coef, gscale=None, eps=0.0, weight_is_ra
     return _sod_loss_grad("sod_wloss_grad", output, label, (wmap,), coef, gscale, (float(eps), int(bool(weight_is_raw))))
 
 
-def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay=0.0):
-    """One Adam step on lists of fp32 device tensors (tramba_adam_step); `steps` are the 0-dim fp32 device counters of
-    torch.optim.Adam's capturable state."""
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay=0.0, gscale=None, skip=None,
+              ema=None, sched=None):
+    """One Adam step on lists of fp32 device tensors (`adam_step_raw` on their pointer arrays); `steps` are the 0-dim fp32
+    device counters of torch.optim.Adam's capturable state, `ema` a list of fp32 averages, one per parameter, or None."""
     n = len(params)
     if n == 0:
         return
-    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(steps) == n):
-        raise TrambaHipError("adam_step: the five tensor lists differ in length")
-    for group in (params, grads, exp_avgs, exp_avg_sqs, steps):
+    lists = (params, grads, exp_avgs, exp_avg_sqs) + (() if ema is None else (ema,))
+    if not all(len(group) == n for group in lists + (steps,)):
+        raise TrambaHipError("adam_step: the tensor lists differ in length")
+    for group in lists + (steps,):
         for t in group:
             if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
                 raise TrambaHipError("adam_step: contiguous fp32 tensors on a HIP device only (a sparse or strided gradient?)")
-    for p, g, m, v in zip(params, grads, exp_avgs, exp_avg_sqs):
-        if not (g.numel() == m.numel() == v.numel() == p.numel()):
-            raise TrambaHipError("adam_step: gradient / state of another size than the parameter")
+    for group in lists[1:]:
+        for p, t in zip(params, group):
+            if t.numel() != p.numel():
+                raise TrambaHipError("adam_step: gradient / state / average of another size than the parameter")
     adam_step_raw(pointer_array(params), pointer_array(grads), pointer_array(exp_avgs), pointer_array(exp_avg_sqs),
                   pointer_array(steps), (ctypes.c_int64 * n)(*[t.numel() for t in params]), n, lr, beta1, beta2, eps,
-                  weight_decay)
+                  weight_decay, gscale=gscale, skip=skip, ema=None if ema is None else pointer_array(ema), sched=sched)
 
 
 def pointer_array(tensors):
@@ -1443,22 +1446,26 @@ def pointer_array(tensors):
 
 
 def adam_step_raw(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, lr, beta1, beta2, eps, weight_decay=0.0, gscale=None,
-                  skip=None):
+                  skip=None, ema=None, sched=None):
     """`adam_step` on prepared pointer arrays (tramba_amd.train.Adam keeps those of the parameters and of the state between
     steps and rebuilds only the gradients'); the caller vouches for fp32, contiguous, same-size device tensors.
     `gscale` (fp32) / `skip` (int32): device scalars of a step-control record -- the gradient is multiplied by the first, a
-    non-zero second makes the call change nothing (tramba_adam_step_ctl)."""
-    if gscale is None and skip is None:
-        _check(lib().tramba_adam_step(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
-                                      float(beta2), float(eps), float(weight_decay), _stream()), "adam_step")
-        return
+    non-zero second makes the call change nothing.  `sched`: the record tensor of `step_sched_record` -- the step runs at
+    lr * its lr_factor, read on the device when the kernel runs.  `ema`: a pointer array of fp32 averages, one per
+    parameter, moved in the same pass by the record's ema_weight (needs `sched`).  One entry, tramba_adam_step_sched: with
+    `ema` and `sched` None it runs the launches of tramba_adam_step_ctl, with all four None those of tramba_adam_step."""
     if gscale is not None and (gscale.dtype != torch.float32 or not gscale.is_cuda):
         raise TrambaHipError("adam_step: gscale is an fp32 scalar on the device")
     if skip is not None and (skip.dtype != torch.int32 or not skip.is_cuda):
         raise TrambaHipError("adam_step: skip is an int32 scalar on the device")
-    _check(lib().tramba_adam_step_ctl(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
-                                      float(beta2), float(eps), float(weight_decay), _ptr(gscale), _ptr(skip), _stream()),
-           "adam_step_ctl")
+    if sched is not None and (sched.dtype != torch.int64 or not sched.is_cuda or sched.numel() * 8 < STEP_SCHED_BYTES):
+        raise TrambaHipError("adam_step: sched is a tramba_step_sched record on the device (step_sched_record)")
+    _check(lib().tramba_adam_step_sched(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
+                                        float(beta2), float(eps), float(weight_decay), _ptr(gscale), _ptr(skip), ema,
+                                        _ptr(sched), _stream()), "adam_step")
+
+
+adam_step_sched, adam_step_sched_raw = adam_step, adam_step_raw      # second names of the same functions, still in use
 
 
 STEP_CTL_BYTES = 24      # struct tramba_step_ctl: float norm, float scale, int32 skip, int32 micro, int64 skipped_steps
@@ -1482,12 +1489,17 @@ def grad_norm_workspace(numel, n):
     return lib().tramba_grad_norm_workspace(numel, n)
 
 
-def grad_norm_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, workspace):
-    """global L2 norm of the tensors -> the record's norm / scale / skip (tramba_grad_norm); `workspace`: a device tensor of
-    at least grad_norm_workspace() bytes"""
-    _check(lib().tramba_grad_norm(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
-                                  ctl.data_ptr(), workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
-           "grad_norm")
+def grad_norm_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, workspace, ls=None):
+    """global L2 norm of the tensors -> the record's norm / scale / skip (tramba_grad_norm_scaled); `workspace`: a device
+    tensor of at least grad_norm_workspace() bytes.  `ls`: the loss-scale record whose scale the gradients carry -- norm
+    and scale come out for the unscaled mean gradient, the un-scaling rides in the record's scale (None: as they are)."""
+    _check(lib().tramba_grad_norm_scaled(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
+                                         ctl.data_ptr(), _ptr(ls), workspace.data_ptr(),
+                                         workspace.numel() * workspace.element_size(), _stream()), "grad_norm")
+
+
+def grad_norm_scaled_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, ls, workspace):
+    return grad_norm_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, workspace, ls)
 
 
 LOSS_SCALE_BYTES = 24    # struct tramba_loss_scale: float scale, float inv_scale, int32 good_steps, int32 reserved, int64 backoffs
@@ -1503,14 +1515,6 @@ def loss_scale_record(device, init=1.0):
     f, i = rec.view(torch.float32), rec.view(torch.int32)
     f[0], f[1] = float(init), 1.0 / float(init)
     return rec, {"scale": f[0], "inv_scale": f[1], "good_steps": i[2], "backoffs": rec[2]}
-
-
-def grad_norm_scaled_raw(grads, numel, n, mean_scale, max_norm, skip_nonfinite, ctl, ls, workspace):
-    """`grad_norm_raw` on gradients that carry the loss scale of the record `ls` (tramba_grad_norm_scaled): norm and scale
-    come out for the unscaled mean gradient, the un-scaling rides in the record's scale.  ls None: `grad_norm_raw`."""
-    _check(lib().tramba_grad_norm_scaled(grads, numel, n, float(mean_scale), float(max_norm or 0.0), int(bool(skip_nonfinite)),
-                                         ctl.data_ptr(), None if ls is None else ls.data_ptr(), workspace.data_ptr(),
-                                         workspace.numel() * workspace.element_size(), _stream()), "grad_norm_scaled")
 
 
 def loss_scale_update_raw(ls, ctl, growth, backoff, growth_interval, min_scale, max_scale):
@@ -1549,46 +1553,6 @@ def step_sched_advance_raw(rec, lr_table=None, ema_table=None):
     lp, ln = _sched_table("lr", lr_table, torch.float64)
     ep, en = _sched_table("ema", ema_table, torch.float32)
     _check(lib().tramba_step_sched_advance(rec.data_ptr(), lp, ln, ep, en, _stream()), "step_sched_advance")
-
-
-def adam_step_sched_raw(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, lr, beta1, beta2, eps, weight_decay=0.0,
-                        gscale=None, skip=None, ema=None, sched=None):
-    """`adam_step_raw` with a schedule record (tramba_adam_step_sched).  `sched`: the record tensor of `step_sched_record`
-    -- the step runs at lr * its lr_factor, read on the device when the kernel runs.  `ema`: a pointer array of fp32
-    averages, one per parameter, moved in the same pass by the record's ema_weight (needs `sched`).  Both None:
-    tramba_adam_step_ctl."""
-    if gscale is not None and (gscale.dtype != torch.float32 or not gscale.is_cuda):
-        raise TrambaHipError("adam_step_sched: gscale is an fp32 scalar on the device")
-    if skip is not None and (skip.dtype != torch.int32 or not skip.is_cuda):
-        raise TrambaHipError("adam_step_sched: skip is an int32 scalar on the device")
-    if sched is not None and (sched.dtype != torch.int64 or not sched.is_cuda or sched.numel() * 8 < STEP_SCHED_BYTES):
-        raise TrambaHipError("adam_step_sched: sched is a tramba_step_sched record on the device (step_sched_record)")
-    _check(lib().tramba_adam_step_sched(params, grads, exp_avgs, exp_avg_sqs, steps, numel, n, float(lr), float(beta1),
-                                        float(beta2), float(eps), float(weight_decay), _ptr(gscale), _ptr(skip), ema,
-                                        _ptr(sched), _stream()), "adam_step_sched")
-
-
-def adam_step_sched(params, grads, exp_avgs, exp_avg_sqs, steps, lr, beta1, beta2, eps, weight_decay=0.0, gscale=None,
-                    skip=None, ema=None, sched=None):
-    """One scheduled Adam step on lists of fp32 device tensors (`adam_step_sched_raw` builds on pointer arrays): `ema` is a
-    list of fp32 averages, one per parameter, or None; `sched` the record tensor or None."""
-    n = len(params)
-    if n == 0:
-        return
-    lists = (params, grads, exp_avgs, exp_avg_sqs) + (() if ema is None else (ema,))
-    if not all(len(group) == n for group in lists + (steps,)):
-        raise TrambaHipError("adam_step_sched: the tensor lists differ in length")
-    for group in lists + (steps,):
-        for t in group:
-            if t.dtype != torch.float32 or not t.is_cuda or not t.is_contiguous():
-                raise TrambaHipError("adam_step_sched: contiguous fp32 tensors on a HIP device only")
-    for group in lists[1:]:
-        for p, t in zip(params, group):
-            if t.numel() != p.numel():
-                raise TrambaHipError("adam_step_sched: gradient / state / average of another size than the parameter")
-    adam_step_sched_raw(pointer_array(params), pointer_array(grads), pointer_array(exp_avgs), pointer_array(exp_avg_sqs),
-                        pointer_array(steps), (ctypes.c_int64 * n)(*[t.numel() for t in params]), n, lr, beta1, beta2, eps,
-                        weight_decay, gscale=gscale, skip=skip, ema=None if ema is None else pointer_array(ema), sched=sched)
 
 
 def im2col3x3_cl(x, stride, pad, ckp):

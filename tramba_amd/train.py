@@ -305,20 +305,15 @@ class Adam(torch.optim.Adam):
                     raise hip.TrambaHipError("Adam: dense contiguous fp32 gradients only")
             plan = self._plan(gi, ps)
             b1, b2 = group["betas"]
-            if sched is None:
-                hip.adam_step_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps), group["lr"], b1,
-                                  b2, group["eps"], group["weight_decay"], gscale=gscale, skip=skip)
-            else:
-                avgs = None
-                if ema is not None:
-                    avgs = [ema[p] for p in ps]
-                    for p, e in zip(ps, avgs):
-                        if e.dtype != torch.float32 or e.device != p.device or not e.is_contiguous() or e.numel() != p.numel():
-                            raise hip.TrambaHipError("Adam: an average is a contiguous fp32 tensor of its parameter's size and device")
-                    avgs = hip.pointer_array(avgs)
-                hip.adam_step_sched_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps),
-                                        group["lr"], b1, b2, group["eps"], group["weight_decay"], gscale=gscale, skip=skip,
-                                        ema=avgs, sched=sched)
+            avgs = None
+            if ema is not None:
+                avgs = [ema[p] for p in ps]
+                for p, e in zip(ps, avgs):
+                    if e.dtype != torch.float32 or e.device != p.device or not e.is_contiguous() or e.numel() != p.numel():
+                        raise hip.TrambaHipError("Adam: an average is a contiguous fp32 tensor of its parameter's size and device")
+                avgs = hip.pointer_array(avgs)
+            hip.adam_step_raw(plan[1], hip.pointer_array(grads), plan[2], plan[3], plan[4], plan[5], len(ps), group["lr"], b1, b2,
+                              group["eps"], group["weight_decay"], gscale=gscale, skip=skip, ema=avgs, sched=sched)
             # the kernel writes through raw pointers: bump the version counters as an in-place torch op would (every
             # derived-weight cache of the inference path is keyed on them)
             torch.autograd.graph.increment_version(ps)
@@ -987,17 +982,10 @@ class StepControl:
             if plan is None:
                 plan = self._plans["norm"] = (hip.pointer_array(self._flat),
                                               (ctypes.c_int64 * len(self._flat))(*[f.numel() for f in self._flat]))
-            if self.scaler is None:
-                hip.grad_norm_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
-                                  self._record, self._workspace)
-            else:
-                hip.grad_norm_scaled_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite,
-                                         self._record, self._ls_record, self._workspace)
-            if self._scheduled:
-                opt.step(gscale=self._fields["scale"], skip=self._fields["skip"], sched=self._sched_record,
-                         ema=None if self.ema is None else self.ema._avg)
-            else:
-                opt.step(gscale=self._fields["scale"], skip=self._fields["skip"])
+            hip.grad_norm_raw(plan[0], plan[1], len(self._flat), 1.0 / count, self.clip_norm, self.skip_nonfinite, self._record,
+                              self._workspace, ls=self._ls_record if self.scaler is not None else None)
+            opt.step(gscale=self._fields["scale"], skip=self._fields["skip"], sched=self._sched_record,   # (None: unscheduled)
+                     ema=None if self.ema is None else self.ema._avg)
             if self.scaler is not None:
                 hip.loss_scale_update_raw(self._ls_record, self._record, *self.scaler.key())
             if self._scheduled:                     # behind the optimizer's launches and the scale's move; skipped or not
