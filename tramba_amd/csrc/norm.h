@@ -1,5 +1,7 @@
-// Wave-level LayerNorm helper shared by the norm kernels.
+// LayerNorm helpers shared by the norm kernels: the wave form's statistics, and the rows form's plan, dispatch and lanes.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace tramba {
@@ -42,6 +44,101 @@ inline int norm_vec(int c, int maxv)
     return v;
 }
 
+// row q = ((b*H + h)*W + w)*P*P + p1*P + p2 of a (B, H, W, P*P*C) map -> row of output pixel (b, h*P + p1, w*P + p2): the
+// pixel shuffle 'b (p1 p2 c) h w -> b c (h p1) (w p2)' in channels-last rows.  32-bit index arithmetic (rows < 2^31,
+// host-checked): six emulated 64-bit divisions per lane were most of the forward kernels' instructions
+__device__ __forceinline__ long shuffled_row(long row, int P, int H, int W)
+{
+    if (P <= 1) return row;
+    const unsigned r32u = (unsigned)row, pp2 = (unsigned)(P * P);
+    const unsigned pp = r32u % pp2, pix = r32u / pp2;
+    const unsigned wi = pix % (unsigned)W, bh = pix / (unsigned)W;
+    const unsigned hi = bh % (unsigned)H, b = bh / (unsigned)H;
+    return ((long)b * (H * P) + (long)(hi * P + pp / P)) * (long)(W * P) + (long)(wi * P + pp % P);
+}
+
+// ---- the rows form: LPR lanes per row, 64 / LPR rows of a wave in flight, one 16-byte pack of VM elements per lane
+// (C <= 64 * VM; VM = 8 for 16-bit, 4 for fp32).  The host plan, its dispatch and the lane's place are written down here
+// once; the kernels keep their own arithmetic around the sums.
+struct RowForm {
+    int vm, lpr;   // elements of a lane's pack; lanes per row (a power of two, 1 .. 64)
+    bool ok;       // the row fits the form
+};
+template <typename T> constexpr int kRowVec = 16 / (int)sizeof(T);   // vm as the kernels' template argument
+// LayerNorm family: one pack per lane covers the row -- lpr = the smallest power of two >= C / vm
+inline RowForm row_form(int c, int dtype)
+{
+    RowForm f{dtype == TRAMBA_F32 ? 4 : 8, 1, false};
+    f.ok = c % f.vm == 0 && c / f.vm <= kWave;
+    while (f.ok && f.lpr < c / f.vm) f.lpr <<= 1;
+    return f;
+}
+// row-dot forward: a lane strides the row by lpr packs, so lpr * vm has to DIVIDE C -- the largest such power of two <= 64
+inline RowForm row_form_dividing(int c, int dtype)
+{
+    RowForm f{dtype == TRAMBA_F32 ? 4 : 8, 1, false};
+    f.ok = c % f.vm == 0;
+    while (f.ok && f.lpr < kWave && c % (2 * f.lpr * f.vm) == 0) f.lpr <<= 1;
+    return f;
+}
+inline long rows_waves(long rows, int lpr) { return (rows + (kWave / lpr) - 1) / (kWave / lpr); }   // one row group per wave
+inline long rows_grid(long waves) { return (waves + 3) / 4; }                                      // four waves per workgroup
+// what a sizing query and its launch have to agree on: both read it from ONE function per kernel
+struct RowPlan {
+    RowForm form;
+    long per_wave;   // rows (or, norm-head backward, row groups) a wave walks
+    long parts;      // workgroups = partial rows; 0: the shape is not served
+};
+
+// f(std::integral_constant<int, L>{}) for the runtime lpr -- the one switch over the seven forms
+template <typename F> inline void with_lpr(int lpr, F &&f)
+{
+    switch (lpr) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: f(std::integral_constant<int, 64>{}); break;
+    }
+}
+// the same for norm_vec's 8 / 4 / 2 / 1 of the one-row-per-wave form (no fp32 kernel with V = 8 exists)
+template <typename T, typename F> inline void with_norm_vec(int v, F &&f)
+{
+    switch (v) {
+    case 8: if constexpr (sizeof(T) == 2) f(std::integral_constant<int, 8>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 1>{}); break;
+    }
+}
+
+// a lane's place in the form: pack `sub` of row slot `slot`
+// (lane and sub are read once and kept, so that every use sees ONE value; the rest are functions, so that each kernel names
+// them in the order its body always did -- the compiler's schedule is seeded by that order and stays what it was)
+template <int V, int LPR> struct RowLane {
+    static constexpr int RPW = kWave / LPR;
+    const int lane, sub;
+    __device__ __forceinline__ explicit RowLane(int lane_ = threadIdx.x & (kWave - 1)) : lane(lane_), sub(lane_ % LPR) {}
+    __device__ __forceinline__ int slot() const { return lane / LPR; }
+    __device__ __forceinline__ int c0() const { return sub * V; }
+    // the lane's pack lies within the row (false on the idle lanes of a C / V that is no power of two)
+    __device__ __forceinline__ bool cok(int C) const { return c0() + V <= C; }
+    // the lane's row where every wave takes ONE row group (the looping kernels add slot() to their own group's first row)
+    __device__ __forceinline__ long row() const
+    {
+        const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        return wave * RPW + slot();
+    }
+};
+// sum over the LPR lanes of a row; every lane of the row receives it
+template <int LPR> __device__ __forceinline__ float sub_sum(float s)
+{
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
+    return s;
+}
 // SS2D's z gate (vmamba.py:288-290) as the last step of a row epilogue: with GATE the row piece is stored as
 // o[v] * silu(g[v]), g = the gate's stored PRE-activation at the channels of o; without it the values are stored as they are
 // and g is never touched -- the ungated instantiation of a kernel body does the arithmetic it did, in the same order.

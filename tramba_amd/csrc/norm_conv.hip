@@ -45,17 +45,7 @@ __global__ __launch_bounds__(256) void layernorm_cl_kernel(const T *__restrict__
     }
     float mean, rstd;
     wave_layernorm<V>(acc, nit, C, lane, eps, mean, rstd);
-    long orow = row;
-    if (P > 1) {
-        // 32-bit index arithmetic (rows < 2^31, host-checked): six emulated 64-bit divisions per lane were most of
-        // this kernel's instructions
-        const unsigned r32u = (unsigned)row, pp2 = (unsigned)(P * P);
-        const unsigned pp = r32u % pp2, pix = r32u / pp2;
-        const unsigned wi = pix % (unsigned)W, bh = pix / (unsigned)W;
-        const unsigned hi = bh % (unsigned)H, b = bh / (unsigned)H;
-        orow = ((long)b * (H * P) + (long)(hi * P + pp / P)) * (long)(W * P) + (long)(wi * P + pp % P);
-    }
-    T *yr = y + orow * C;
+    T *yr = y + shuffled_row(row, P, H, W) * C;
 #pragma unroll
     for (int it = 0; it < kNormMaxIt; ++it) {
         if (it < nit) {
@@ -80,14 +70,12 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T *__restrict
                                                             int W, const float *__restrict__ head_w, float head_b,
                                                             float *__restrict__ head_out)
 {
-    constexpr int RPW = kWave / LPR;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int sub = lane % LPR;
-    const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const long row = wave * RPW + lane / LPR;
+    const RowLane<V, LPR> ln;
+    const int sub = ln.sub;
+    const long row = ln.row();
     const bool rok = row < rows;
-    const int c0 = sub * V;
-    const bool cok = c0 + V <= C;
+    const int c0 = ln.c0();
+    const bool cok = ln.cok(C);
     float v[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) v[i] = 0.f;
@@ -95,29 +83,16 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T *__restrict
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < V; ++i) s += v[i];
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mean = s / (float)C;
+    const float mean = sub_sum<LPR>(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const float t = cok ? v[i] - mean : 0.f;
         q = fmaf(t, t, q);
     }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, LPR);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    const float rstd = rsqrtf(sub_sum<LPR>(q) / (float)C + eps);
     if (!(rok && cok)) return;
-    long orow = row;
-    if (P > 1) {
-        // 32-bit index arithmetic (rows < 2^31, host-checked): six emulated 64-bit divisions per lane were most of
-        // this kernel's instructions
-        const unsigned r32u = (unsigned)row, pp2 = (unsigned)(P * P);
-        const unsigned pp = r32u % pp2, pix = r32u / pp2;
-        const unsigned wi = pix % (unsigned)W, bh = pix / (unsigned)W;
-        const unsigned hi = bh % (unsigned)H, b = bh / (unsigned)H;
-        orow = ((long)b * (H * P) + (long)(hi * P + pp / P)) * (long)(W * P) + (long)(wi * P + pp % P);
-    }
+    const long orow = shuffled_row(row, P, H, W);
     float wv[V], bv[V], o[V];
     load_pack<float, V>(w + c0, wv);
     load_pack<float, V>(bvec + c0, bv);
@@ -128,8 +103,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(const T *__restrict
         load_pack<float, V>(head_w + c0, hv);
 #pragma unroll
         for (int i = 0; i < V; ++i) d = fmaf(Cvt<T>::to_f(Cvt<T>::from_f(o[i])), hv[i], d);   // as if stored in T
-#pragma unroll
-        for (int of = LPR / 2; of > 0; of >>= 1) d += __shfl_xor(d, of, LPR);
+        d = sub_sum<LPR>(d);
         if (sub == 0) head_out[orow] = d + head_b;
         return;
     }
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(256) void norm_head_bwd_rows_kernel(const T *__rest
     constexpr int RPW = kWave / LPR;
     __shared__ float red[4][kWave * V + 1];
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
-    const int sub = lane % LPR;
+    const int sub = lane % LPR;   // (its own lane lines: RowLane changed this kernel's register counts)
     const long wave = (long)blockIdx.x * (blockDim.x >> 6) + wv;
     const int c0 = sub * V;
     const bool cok = c0 + V <= C;
@@ -171,9 +145,7 @@ __global__ __launch_bounds__(256) void norm_head_bwd_rows_kernel(const T *__rest
     float qs = 0.f;
 #pragma unroll
     for (int i = 0; i < V; ++i) qs += q[i];
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) qs += __shfl_xor(qs, o, LPR);
-    const float qbar = qs / (float)C;
+    const float qbar = sub_sum<LPR>(qs) / (float)C;
     for (int ps = 0; ps < passes; ++ps) {
         const long row = (wave * passes + ps) * RPW + lane / LPR;
         const bool rok = row < rows;
@@ -184,38 +156,24 @@ __global__ __launch_bounds__(256) void norm_head_bwd_rows_kernel(const T *__rest
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < V; ++i) s += v[i];
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-        const float mean = s / (float)C;
+        const float mean = sub_sum<LPR>(s) / (float)C;
         float var = 0.f;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             const float t = cok ? v[i] - mean : 0.f;
             var = fmaf(t, t, var);
         }
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) var += __shfl_xor(var, o, LPR);
-        const float rstd = rsqrtf(var / (float)C + eps);
+        const float rstd = rsqrtf(sub_sum<LPR>(var) / (float)C + eps);
         float xh[V], sq = 0.f;
 #pragma unroll
         for (int i = 0; i < V; ++i) {
             xh[i] = cok ? (v[i] - mean) * rstd : 0.f;
             sq = fmaf(q[i], xh[i], sq);
         }
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) sq += __shfl_xor(sq, o, LPR);
-        sq /= (float)C;
+        sq = sub_sum<LPR>(sq) / (float)C;
         float gi = 0.f;
         if (rok) {
-            long orow = row;
-            if (P > 1) {   // (32-bit index arithmetic, rows < 2^31 host-checked: see layernorm_rows_kernel)
-                const unsigned r32u = (unsigned)row, pp2 = (unsigned)(P * P);
-                const unsigned pp = r32u % pp2, pix = r32u / pp2;
-                const unsigned wi = pix % (unsigned)W, bh = pix / (unsigned)W;
-                const unsigned hi = bh % (unsigned)H, b = bh / (unsigned)H;
-                orow = ((long)b * (H * P) + (long)(hi * P + pp / P)) * (long)(W * P) + (long)(wi * P + pp % P);
-            }
-            gi = g[orow];
+            gi = g[shuffled_row(row, P, H, W)];
         }
         if (rok && cok) {
             float o[V];
@@ -253,14 +211,11 @@ template <typename T, int V, int LPR>
 __global__ __launch_bounds__(256) void rowdot_rows_kernel(const T *__restrict__ x, const float *__restrict__ w, float b,
                                                          float *__restrict__ y, long rows, int C)
 {
-    constexpr int RPW = kWave / LPR;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int sub = lane % LPR;
-    const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const long row = wave * RPW + lane / LPR;
+    const RowLane<V, LPR> ln;
+    const long row = ln.row();
     const bool rok = row < rows;
     float d = 0.f;
-    for (int c0 = sub * V; c0 < C; c0 += LPR * V) {   // LPR * V divides C (host-checked)
+    for (int c0 = ln.c0(); c0 < C; c0 += LPR * V) {   // LPR * V divides C (row_form_dividing)
         float v[V], wv[V];
 #pragma unroll
         for (int i = 0; i < V; ++i) v[i] = 0.f;
@@ -269,78 +224,46 @@ __global__ __launch_bounds__(256) void rowdot_rows_kernel(const T *__restrict__ 
 #pragma unroll
         for (int i = 0; i < V; ++i) d = fmaf(v[i], wv[i], d);
     }
-#pragma unroll
-    for (int of = LPR / 2; of > 0; of >>= 1) d += __shfl_xor(d, of, LPR);
-    if (rok && sub == 0) y[row] = d + b;
+    d = sub_sum<LPR>(d);
+    if (rok && ln.sub == 0) y[row] = d + b;
 }
 
 template <typename T>
-static int launch_layernorm(const void *x, const float *w, const float *b, void *y, long rows, int c,
+static int launch_layernorm(const void *x, const float *w, const float *b, void *y, long rows, int c, int dtype,
                             float eps, int act, int P, int H, int W, hipStream_t s,
                             const float *head_w = nullptr, float head_b = 0.f, float *head_out = nullptr)
 {
-    constexpr int VM = sizeof(T) == 2 ? 8 : 4;
     if (rows >= 2147483647L) {
         set_error("layernorm: %ld rows exceed the 32-bit row index of this build", rows);
         return TRAMBA_ERR_UNSUPPORTED;
     }
-    if (c % VM == 0 && c / VM <= kWave && aligned16(w) && aligned16(b)) {
-        const int need = c / VM;
-        int lpr = 1;
-        while (lpr < need) lpr <<= 1;
-        const long waves = (rows + (kWave / lpr) - 1) / (kWave / lpr);
-        dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-#define GOR_(L_)                                                                                            \
-    hipLaunchKernelGGL((layernorm_rows_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, w, b, (T *)y, rows, c, \
-                       eps, act, P, H, W, head_w, head_b, head_out)
-        switch (lpr) {
-        case 1: GOR_(1); break;
-        case 2: GOR_(2); break;
-        case 4: GOR_(4); break;
-        case 8: GOR_(8); break;
-        case 16: GOR_(16); break;
-        case 32: GOR_(32); break;
-        default: GOR_(64); break;
-        }
-#undef GOR_
+    const RowForm f = row_form(c, dtype);
+    const dim3 block(256);
+    if (f.ok && aligned16(w) && aligned16(b)) {   // (unaligned parameters: the wave form reads them element by element)
+        const dim3 grid((unsigned)rows_grid(rows_waves(rows, f.lpr)));
+        with_lpr(f.lpr, [&](auto L) {
+            hipLaunchKernelGGL((layernorm_rows_kernel<T, kRowVec<T>, decltype(L)::value>), grid, block, 0, s, (const T *)x, w,
+                               b, (T *)y, rows, c, eps, act, P, H, W, head_w, head_b, head_out);
+        });
         TRAMBA_LAUNCH_CHECK();
         return TRAMBA_OK;
     }
     if (head_w) {
-        set_error("shuffle_norm_head: C=%d needs C %% %d == 0 and C <= %d", c, VM, kWave * VM);
+        set_error("shuffle_norm_head: C=%d needs C %% %d == 0 and C <= %d", c, f.vm, kWave * f.vm);
         return TRAMBA_ERR_UNSUPPORTED;
     }
-    const int maxv = sizeof(T) == 2 ? 8 : 4;
-    const int v = norm_vec(c, maxv);
+    const int v = norm_vec(c, f.vm);
     if ((c + kWave * v - 1) / (kWave * v) > kNormMaxIt) {
         set_error("layernorm: C=%d too large", c);
         return TRAMBA_ERR_UNSUPPORTED;
     }
-    dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define GO_(V_)                                                                                       \
-    hipLaunchKernelGGL((layernorm_cl_kernel<T, V_>), grid, block, 0, s, (const T *)x, w, b, (T *)y, rows, c, \
-                       eps, act, P, H, W)
-    switch (v) {
-    case 8: if constexpr (sizeof(T) == 2) { GO_(8); } break;
-    case 4: GO_(4); break;
-    case 2: GO_(2); break;
-    default: GO_(1); break;
-    }
-#undef GO_
+    const dim3 grid((unsigned)rows_grid(rows));
+    with_norm_vec<T>(v, [&](auto V) {
+        hipLaunchKernelGGL((layernorm_cl_kernel<T, decltype(V)::value>), grid, block, 0, s, (const T *)x, w, b, (T *)y, rows, c,
+                           eps, act, P, H, W);
+    });
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
-}
-
-// row q = ((b*H + h)*W + w)*P*P + p1*P + p2 of a (B, H, W, P*P*C) map -> row of output pixel (b, h*P + p1, w*P + p2): the
-// pixel shuffle 'b (p1 p2 c) h w -> b c (h p1) (w p2)' in channels-last rows (32-bit arithmetic, rows < 2^31)
-__device__ __forceinline__ long shuffled_row(long row, int P, int H, int W)
-{
-    if (P <= 1) return row;
-    const unsigned r32u = (unsigned)row, pp2 = (unsigned)(P * P);
-    const unsigned pp = r32u % pp2, pix = r32u / pp2;
-    const unsigned wi = pix % (unsigned)W, bh = pix / (unsigned)W;
-    const unsigned hi = bh % (unsigned)H, b = bh / (unsigned)H;
-    return ((long)b * (H * P) + (long)(hi * P + pp / P)) * (long)(W * P) + (long)(wi * P + pp % P);
 }
 
 // LayerNorm backward (training), channels-last rows: a wave walks RPW rows, all C channels in registers.
@@ -596,7 +519,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const T *__rest
     const long wave = (long)blockIdx.x * (blockDim.x >> 6) + wv;
     const long r0 = wave * rpw;               // a wave past the end runs no row and contributes zeros
     const long rend = r0 + rpw < rows ? r0 + rpw : rows;
-    const int sub = lane % LPR, slot = lane / LPR;
+    const int sub = lane % LPR, slot = lane / LPR;   // (its own lane lines: RowLane cost this kernel 2 SGPRs)
     const int c0 = sub * V;
     const bool cok = c0 + V <= C;
     float gam[V], gw[V], gb[V];
@@ -620,18 +543,14 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const T *__rest
         float sm = 0.f;
 #pragma unroll
         for (int v = 0; v < V; ++v) sm += xv[v];
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) sm += __shfl_xor(sm, o, LPR);
-        const float mean = sm * inv_c;
+        const float mean = sub_sum<LPR>(sm) * inv_c;   // (times 1 / C here, divided by C in the forward kernels: both stay)
         float q = 0.f;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
             const float t = cok ? xv[v] - mean : 0.f;
             q = fmaf(t, t, q);
         }
-#pragma unroll
-        for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, LPR);
-        const float rstd = rsqrtf(q * inv_c + eps);
+        const float rstd = rsqrtf(sub_sum<LPR>(q) * inv_c + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int v = 0; v < V; ++v) {
@@ -694,25 +613,15 @@ __global__ __launch_bounds__(256) void layernorm_bwd_rows_kernel(const T *__rest
 }
 
 template <typename T>
-static int launch_rowdot(const void *x, const float *w, float bias, float *y, long rows, int c, hipStream_t s)
+static int launch_rowdot(const void *x, const float *w, float bias, float *y, long rows, int c, int dtype, hipStream_t s)
 {
-    constexpr int VM = sizeof(T) == 2 ? 8 : 4;
-    TRAMBA_CHECK(c % VM == 0, "rowdot_cl: C=%d must be a multiple of %d", c, VM);
-    int lpr = 1;   // lanes per row: the largest power of two <= 64 with lpr * VM dividing C
-    while (lpr < kWave && c % (2 * lpr * VM) == 0) lpr <<= 1;
-    const long waves = (rows + (kWave / lpr) - 1) / (kWave / lpr);
-    dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-#define GOD_(L_) hipLaunchKernelGGL((rowdot_rows_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, w, bias, y, rows, c)
-    switch (lpr) {
-    case 1: GOD_(1); break;
-    case 2: GOD_(2); break;
-    case 4: GOD_(4); break;
-    case 8: GOD_(8); break;
-    case 16: GOD_(16); break;
-    case 32: GOD_(32); break;
-    default: GOD_(64); break;
-    }
-#undef GOD_
+    const RowForm f = row_form_dividing(c, dtype);
+    TRAMBA_CHECK(f.ok, "rowdot_cl: C=%d must be a multiple of %d", c, f.vm);
+    const dim3 grid((unsigned)rows_grid(rows_waves(rows, f.lpr))), block(256);
+    with_lpr(f.lpr, [&](auto L) {
+        hipLaunchKernelGGL((rowdot_rows_kernel<T, kRowVec<T>, decltype(L)::value>), grid, block, 0, s, (const T *)x, w, bias, y,
+                           rows, c);
+    });
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -1573,7 +1482,7 @@ extern "C" int tramba_layernorm_cl(const void *x, const float *w, const float *b
     TRAMBA_CHECK(aligned16(x) && aligned16(y), "layernorm_cl: tensors must be 16-byte aligned");
     ProfScope prof(TRAMBA_PROF_LAYERNORM, (hipStream_t)stream, 2.0 * (double)rows * c * dtype_size(dtype));
     TRAMBA_DISPATCH_DTYPE(dtype, T,
-        return launch_layernorm<T>(x, w, b, y, rows, c, eps, act, 1, 1, 1, (hipStream_t)stream));
+        return launch_layernorm<T>(x, w, b, y, rows, c, dtype, eps, act, 1, 1, 1, (hipStream_t)stream));
     return TRAMBA_OK;
 }
 
@@ -1589,20 +1498,17 @@ static long ln_bwd_rows_per_wave(long rows, bool rows_form)
     return rpw < lo ? lo : (rpw > 128 ? 128 : rpw);
 }
 
-// rows of at most 64 lanes x 16 bytes: several rows per wave (layernorm_bwd_rows_kernel), one partial row per BLOCK
-static bool ln_bwd_rows_form(int c, int dtype)
+// rows form (layernorm_bwd_rows_kernel) where the row fits it, one row per wave otherwise; one partial row per BLOCK
+static RowPlan ln_bwd_plan(long rows, int c, int dtype)
 {
-    const int vm = dtype == TRAMBA_F32 ? 4 : 8;
-    return c % vm == 0 && c <= kWave * vm;
+    RowPlan p{row_form(c, dtype), 0, 0};
+    if (rows <= 0 || c <= 0) return p;
+    p.per_wave = ln_bwd_rows_per_wave(rows, p.form.ok);
+    p.parts = rows_grid((rows + p.per_wave - 1) / p.per_wave);
+    return p;
 }
 
-extern "C" int64_t tramba_layernorm_bwd_parts(int64_t rows, int c, int dtype)
-{
-    if (rows <= 0 || c <= 0) return 0;
-    const long rpw = ln_bwd_rows_per_wave(rows, ln_bwd_rows_form(c, dtype));
-    const long waves = (rows + rpw - 1) / rpw;
-    return (waves + 3) / 4;
-}
+extern "C" int64_t tramba_layernorm_bwd_parts(int64_t rows, int c, int dtype) { return ln_bwd_plan(rows, c, dtype).parts; }
 
 extern "C" int tramba_layernorm_bwd_cl(const void *x, const void *dy, const float *w, void *dx, float *part,
                                        int64_t rows, int c, float eps, int dtype, void *stream)
@@ -1641,32 +1547,16 @@ extern "C" int tramba_layernorm_bwd_any_cl(const void *x, const void *dy, const 
     TRAMBA_CHECK((c + kWave * v - 1) / (kWave * v) <= kNormMaxIt, "layernorm_bwd_cl: C=%d too large", c);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(TRAMBA_PROF_LAYERNORM, s, (3.0 + (gres ? 1.0 : 0.0) + (dxm ? 1.0 : 0.0)) * (double)rows * c * dtype_size(dtype));
-    const long rpw = ln_bwd_rows_per_wave(rows, ln_bwd_rows_form(c, dtype));
-    const long waves = (rows + rpw - 1) / rpw;
-    dim3 grid((unsigned)((waves + 3) / 4)), block(256);
+    const RowPlan plan = ln_bwd_plan(rows, c, dtype);
+    const long rpw = plan.per_wave;
+    const dim3 grid((unsigned)plan.parts), block(256);
     // short rows: several rows per wave, 16-byte accesses; longer rows: one row per wave
-    const int vm = dtype == TRAMBA_F32 ? 4 : 8;
-    if (ln_bwd_rows_form(c, dtype)) {
-        int lpr = 1;
-        while (lpr < c / vm) lpr <<= 1;
-#define GOB_(T, V_, L_)                                                                                             \
-    hipLaunchKernelGGL((layernorm_bwd_rows_kernel<T, V_, L_>), grid, block, 0, s, (const T *)x, (const T *)dy, w, (T *)dx, \
-                       part, (long)rows, c, eps, (int)rpw, (const T *)gres, mask, rps, (T *)dxm, P, H, W)
-#define BYL_(T, V_)                    \
-    switch (lpr) {                     \
-    case 1: GOB_(T, V_, 1); break;     \
-    case 2: GOB_(T, V_, 2); break;     \
-    case 4: GOB_(T, V_, 4); break;     \
-    case 8: GOB_(T, V_, 8); break;     \
-    case 16: GOB_(T, V_, 16); break;   \
-    case 32: GOB_(T, V_, 32); break;   \
-    default: GOB_(T, V_, 64); break;   \
-    }
-        if (dtype == TRAMBA_F32) { BYL_(float, 4) }
-        else if (dtype == TRAMBA_BF16) { BYL_(__hip_bfloat16, 8) }
-        else { BYL_(__half, 8) }
-#undef BYL_
-#undef GOB_
+    if (plan.form.ok) {
+        TRAMBA_DISPATCH_DTYPE(dtype, T, with_lpr(plan.form.lpr, [&](auto L) {
+            hipLaunchKernelGGL((layernorm_bwd_rows_kernel<T, kRowVec<T>, decltype(L)::value>), grid, block, 0, s, (const T *)x,
+                               (const T *)dy, w, (T *)dx, part, (long)rows, c, eps, (int)rpw, (const T *)gres, mask, rps,
+                               (T *)dxm, P, H, W);
+        }));
         TRAMBA_LAUNCH_CHECK();
         return TRAMBA_OK;
     }
@@ -1703,7 +1593,7 @@ extern "C" int tramba_shuffle_norm_cl(const void *x, const float *w, const float
     TRAMBA_CHECK(aligned16(x) && aligned16(y), "shuffle_norm_cl: tensors must be 16-byte aligned");
     const long rows = (long)batch * h * wd * p * p;
     TRAMBA_DISPATCH_DTYPE(dtype, T,
-        return launch_layernorm<T>(x, w, b, y, rows, c, eps, TRAMBA_ACT_NONE, p, h, wd, (hipStream_t)stream));
+        return launch_layernorm<T>(x, w, b, y, rows, c, dtype, eps, TRAMBA_ACT_NONE, p, h, wd, (hipStream_t)stream));
     return TRAMBA_OK;
 }
 
@@ -1716,7 +1606,7 @@ extern "C" int tramba_shuffle_norm_head_cl(const void *x, const float *w, const 
     TRAMBA_CHECK(aligned16(x) && aligned16(head_w), "shuffle_norm_head_cl: tensors must be 16-byte aligned");
     const long rows = (long)batch * h * wd * p * p;
     TRAMBA_DISPATCH_DTYPE(dtype, T,
-        return launch_layernorm<T>(x, w, b, nullptr, rows, c, eps, TRAMBA_ACT_NONE, p, h, wd, (hipStream_t)stream,
+        return launch_layernorm<T>(x, w, b, nullptr, rows, c, dtype, eps, TRAMBA_ACT_NONE, p, h, wd, (hipStream_t)stream,
                                    head_w, head_b, y));
     return TRAMBA_OK;
 }
@@ -1729,15 +1619,20 @@ static int norm_head_bwd_passes(long rows, int lpr)
     return (int)(passes < 1 ? 1 : passes > 64 ? 64 : passes);
 }
 
+static RowPlan norm_head_bwd_plan(int batch, int h, int wd, int c, int p, int dtype)
+{
+    RowPlan pl{row_form(c, dtype), 0, 0};
+    if (batch <= 0 || h <= 0 || wd <= 0 || c <= 0 || p < 1 || !pl.form.ok) return pl;
+    const long rows = (long)batch * h * wd * p * p;
+    pl.per_wave = norm_head_bwd_passes(rows, pl.form.lpr);
+    const long per_block = 4L * (kWave / pl.form.lpr) * pl.per_wave;
+    pl.parts = (rows + per_block - 1) / per_block;
+    return pl;
+}
+
 extern "C" int64_t tramba_shuffle_norm_head_bwd_parts(int batch, int h, int wd, int c, int p, int dtype)
 {
-    const int vm = dtype == TRAMBA_F32 ? 4 : 8;
-    if (batch <= 0 || h <= 0 || wd <= 0 || c <= 0 || p < 1 || c % vm != 0 || c / vm > kWave) return 0;
-    int lpr = 1;
-    while (lpr < c / vm) lpr <<= 1;
-    const long rows = (long)batch * h * wd * p * p;
-    const long per_block = 4L * (kWave / lpr) * norm_head_bwd_passes(rows, lpr);
-    return (rows + per_block - 1) / per_block;
+    return norm_head_bwd_plan(batch, h, wd, c, p, dtype).parts;
 }
 
 extern "C" int tramba_shuffle_norm_head_bwd_cl(const void *x, const float *g, const float *ln_w, const float *head_w, void *dx,
@@ -1747,35 +1642,16 @@ extern "C" int tramba_shuffle_norm_head_bwd_cl(const void *x, const float *g, co
     TRAMBA_CHECK(x && g && ln_w && head_w && dx && part, "shuffle_norm_head_bwd_cl: null tensor");
     TRAMBA_CHECK(batch > 0 && h > 0 && wd > 0 && c > 0 && p >= 1, "shuffle_norm_head_bwd_cl: empty shape");
     TRAMBA_CHECK(aligned16(x) && aligned16(dx) && aligned16(ln_w) && aligned16(head_w), "shuffle_norm_head_bwd_cl: tensors must be 16-byte aligned");
-    const long nparts = tramba_shuffle_norm_head_bwd_parts(batch, h, wd, c, p, dtype);
-    TRAMBA_CHECK(nparts > 0, "shuffle_norm_head_bwd_cl: C=%d needs C %% %d == 0 and C <= %d", c, dtype == TRAMBA_F32 ? 4 : 8,
-                 kWave * (dtype == TRAMBA_F32 ? 4 : 8));
+    const RowPlan plan = norm_head_bwd_plan(batch, h, wd, c, p, dtype);
+    TRAMBA_CHECK(plan.parts > 0, "shuffle_norm_head_bwd_cl: C=%d needs C %% %d == 0 and C <= %d", c, plan.form.vm,
+                 kWave * plan.form.vm);
     const long rows = (long)batch * h * wd * p * p;
-    TRAMBA_CHECK(rows < 2147483647L && nparts < 2147483647L, "shuffle_norm_head_bwd_cl: too many rows");
+    TRAMBA_CHECK(rows < 2147483647L && plan.parts < 2147483647L, "shuffle_norm_head_bwd_cl: too many rows");
     hipStream_t s = (hipStream_t)stream;
-#define GOB_(T, VM, L_)                                                                                                  \
-    hipLaunchKernelGGL((norm_head_bwd_rows_kernel<T, VM, L_>), dim3((unsigned)nparts), dim3(256), 0, s, (const T *)x, g, ln_w, \
-                       head_w, (T *)dx, part, rows, c, eps, p, h, wd, norm_head_bwd_passes(rows, L_))
-#define GOBL_(T, VM)                                                                                                     \
-    {                                                                                                                    \
-        int lpr = 1;                                                                                                     \
-        while (lpr < c / VM) lpr <<= 1;                                                                                  \
-        switch (lpr) {                                                                                                   \
-        case 1: GOB_(T, VM, 1); break;                                                                                   \
-        case 2: GOB_(T, VM, 2); break;                                                                                   \
-        case 4: GOB_(T, VM, 4); break;                                                                                   \
-        case 8: GOB_(T, VM, 8); break;                                                                                   \
-        case 16: GOB_(T, VM, 16); break;                                                                                 \
-        case 32: GOB_(T, VM, 32); break;                                                                                 \
-        default: GOB_(T, VM, 64); break;                                                                                 \
-        }                                                                                                                \
-    }
-    if (dtype == TRAMBA_F32) GOBL_(float, 4)
-    else if (dtype == TRAMBA_F16) GOBL_(__half, 8)
-    else if (dtype == TRAMBA_BF16) GOBL_(__hip_bfloat16, 8)
-    else TRAMBA_CHECK(false, "bad dtype %d", dtype);
-#undef GOBL_
-#undef GOB_
+    TRAMBA_DISPATCH_DTYPE(dtype, T, with_lpr(plan.form.lpr, [&](auto L) {
+        hipLaunchKernelGGL((norm_head_bwd_rows_kernel<T, kRowVec<T>, decltype(L)::value>), dim3((unsigned)plan.parts), dim3(256),
+                           0, s, (const T *)x, g, ln_w, head_w, (T *)dx, part, rows, c, eps, p, h, wd, (int)plan.per_wave);
+    }));
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -1786,7 +1662,7 @@ extern "C" int tramba_rowdot_cl(const void *x, const float *w, float bias, float
     TRAMBA_CHECK(x && w && y, "rowdot_cl: null tensor");
     TRAMBA_CHECK(rows > 0 && c > 0, "rowdot_cl: empty shape");
     TRAMBA_CHECK(aligned16(x) && aligned16(w), "rowdot_cl: tensors must be 16-byte aligned");
-    TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_rowdot<T>(x, w, bias, y, (long)rows, c, (hipStream_t)stream));
+    TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_rowdot<T>(x, w, bias, y, (long)rows, c, dtype, (hipStream_t)stream));
     return TRAMBA_OK;
 }
 

@@ -31,14 +31,11 @@ __device__ __forceinline__ void add_ln_rows_body(const T *__restrict__ x, const 
                                                  T *__restrict__ nact, long rows, int C, float eps, int act,
                                                  const T *__restrict__ gate)
 {
-    constexpr int RPW = kWave / LPR;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int sub = lane % LPR;
-    const long wave = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    const long row = wave * RPW + lane / LPR;
+    const RowLane<V, LPR> ln;
+    const long row = ln.row();
     const bool rok = row < rows;
-    const int c0 = sub * V;
-    const bool cok = c0 + V <= C;
+    const int c0 = ln.c0();
+    const bool cok = ln.cok(C);
     float v[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) v[i] = 0.f;
@@ -57,18 +54,14 @@ __device__ __forceinline__ void add_ln_rows_body(const T *__restrict__ x, const 
     float s = 0.f;
 #pragma unroll
     for (int i = 0; i < V; ++i) s += v[i];
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mean = s / (float)C;
+    const float mean = sub_sum<LPR>(s) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < V; ++i) {
         const float t = cok ? v[i] - mean : 0.f;
         q = fmaf(t, t, q);
     }
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, LPR);
-    const float rstd = rsqrtf(q / (float)C + eps);
+    const float rstd = rsqrtf(sub_sum<LPR>(q) / (float)C + eps);
     if (!(rok && cok)) return;
     float wv[V], bv[V], o[V];
     load_pack<float, V>(w + c0, wv);
@@ -193,56 +186,40 @@ __global__ __launch_bounds__(256) void add_ln_wave_gate_kernel(const T *__restri
 
 template <typename T>
 static int launch_add_ln(const void *x, const void *y, const float *mask, long rps, const float *w, const float *b,
-                         void *xsum, void *n, void *nact, long rows, int c, float eps, int act, hipStream_t s,
+                         void *xsum, void *n, void *nact, long rows, int c, int dtype, float eps, int act, hipStream_t s,
                          const void *gate = nullptr)
 {
-    constexpr int VM = sizeof(T) == 2 ? 8 : 4;
-    if (c % VM == 0 && c / VM <= kWave && aligned16(w) && aligned16(b)) {
-        const int need = c / VM;
-        int lpr = 1;
-        while (lpr < need) lpr <<= 1;
-        const long waves = (rows + (kWave / lpr) - 1) / (kWave / lpr);
-        dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-#define GOR_(L_)                                                                                                    \
-    if (gate)                                                                                                       \
-        hipLaunchKernelGGL((add_ln_rows_gate_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, \
-                           rps, w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);            \
-    else                                                                                                            \
-        hipLaunchKernelGGL((add_ln_rows_kernel<T, VM, L_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, \
-                           b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
-        switch (lpr) {
-        case 1: GOR_(1); break;
-        case 2: GOR_(2); break;
-        case 4: GOR_(4); break;
-        case 8: GOR_(8); break;
-        case 16: GOR_(16); break;
-        case 32: GOR_(32); break;
-        default: GOR_(64); break;
-        }
-#undef GOR_
+    const RowForm f = row_form(c, dtype);
+    const dim3 block(256);
+    if (f.ok && aligned16(w) && aligned16(b)) {   // (unaligned parameters: the wave form reads them element by element)
+        const dim3 grid((unsigned)rows_grid(rows_waves(rows, f.lpr)));
+        with_lpr(f.lpr, [&](auto L) {
+            constexpr int LPR = decltype(L)::value;
+            if (gate)
+                hipLaunchKernelGGL((add_ln_rows_gate_kernel<T, kRowVec<T>, LPR>), grid, block, 0, s, (const T *)x, (const T *)y,
+                                   mask, rps, w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);
+            else
+                hipLaunchKernelGGL((add_ln_rows_kernel<T, kRowVec<T>, LPR>), grid, block, 0, s, (const T *)x, (const T *)y, mask,
+                                   rps, w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act);
+        });
         TRAMBA_LAUNCH_CHECK();
         return TRAMBA_OK;
     }
-    const int v = norm_vec(c, VM);
+    const int v = norm_vec(c, f.vm);
     if ((c + kWave * v - 1) / (kWave * v) > kNormMaxIt) {
         set_error("add_layernorm: C=%d too large", c);
         return TRAMBA_ERR_UNSUPPORTED;
     }
-    dim3 grid((unsigned)((rows + 3) / 4)), block(256);
-#define GO_(V_)                                                                                                     \
-    if (gate)                                                                                                       \
-        hipLaunchKernelGGL((add_ln_wave_gate_kernel<T, V_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, \
-                           w, b, (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);                 \
-    else                                                                                                            \
-        hipLaunchKernelGGL((add_ln_wave_kernel<T, V_>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b, \
-                           (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act)
-    switch (v) {
-    case 8: if constexpr (sizeof(T) == 2) { GO_(8); } break;
-    case 4: GO_(4); break;
-    case 2: GO_(2); break;
-    default: GO_(1); break;
-    }
-#undef GO_
+    const dim3 grid((unsigned)rows_grid(rows));
+    with_norm_vec<T>(v, [&](auto Vc) {
+        constexpr int V = decltype(Vc)::value;
+        if (gate)
+            hipLaunchKernelGGL((add_ln_wave_gate_kernel<T, V>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b,
+                               (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act, (const T *)gate);
+        else
+            hipLaunchKernelGGL((add_ln_wave_kernel<T, V>), grid, block, 0, s, (const T *)x, (const T *)y, mask, rps, w, b,
+                               (T *)xsum, (T *)n, (T *)nact, rows, c, eps, act);
+    });
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }
@@ -414,7 +391,7 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const T *__restrict__ x
     const long wave = (long)blockIdx.x * (blockDim.x >> 6) + wv;
     const long r0 = wave * rpw;
     const long rend = r0 + rpw < rows ? r0 + rpw : rows;
-    const int sub = lane % LPR, slot = lane / LPR;
+    const int sub = lane % LPR, slot = lane / LPR;   // (its own lane lines: RowLane cost the fp32 LPR = 64 form 2 SGPRs)
     const int c0 = sub * V;
     const bool cok = c0 + V <= C;
     float wv_[V], gw[V], gb = 0.f;
@@ -518,7 +495,7 @@ extern "C" int tramba_add_layernorm_cl(const void *x, const void *y, const float
     ProfScope prof(TRAMBA_PROF_LAYERNORM, (hipStream_t)stream,
                    (2.0 + (y ? 2.0 : 0.0) + (n_act ? 1.0 : 0.0)) * (double)rows * c * dtype_size(dtype));
     TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_add_ln<T>(x, y, mask, rows_per_sample > 0 ? rows_per_sample : 1, w, b, xsum,
-                                                            n, n_act, rows, c, eps, act, (hipStream_t)stream));
+                                                            n, n_act, rows, c, dtype, eps, act, (hipStream_t)stream));
     return TRAMBA_OK;
 }
 
@@ -534,7 +511,7 @@ extern "C" int tramba_add_layernorm_gate_cl(const void *x, const void *y, const 
                  "add_layernorm_gate_cl: tensors must be 16-byte aligned");
     ProfScope prof(TRAMBA_PROF_LAYERNORM, (hipStream_t)stream, (4.0 + (y ? 2.0 : 0.0)) * (double)rows * c * dtype_size(dtype));
     TRAMBA_DISPATCH_DTYPE(dtype, T, return launch_add_ln<T>(x, y, mask, rows_per_sample > 0 ? rows_per_sample : 1, w, b, xsum,
-                                                            n, n_act, rows, c, eps, act, (hipStream_t)stream, zpre));
+                                                            n, n_act, rows, c, dtype, eps, act, (hipStream_t)stream, zpre));
     return TRAMBA_OK;
 }
 
@@ -639,45 +616,31 @@ extern "C" int tramba_dw_unpack_grad_multi(const float *const *gwt, float *const
     return TRAMBA_OK;
 }
 
-extern "C" int64_t tramba_rowdot_bwd_parts(int64_t rows, int c, int dtype)
+// the backward holds a whole row in one pack per lane like the LayerNorm kernels (row_form, not the forward's dividing rule)
+static RowPlan rowdot_bwd_plan(long rows, int c, int dtype)
 {
-    const int vm = dtype == TRAMBA_F32 ? 4 : 8;
-    if (rows <= 0 || c <= 0 || c % vm != 0 || c > kWave * vm) return 0;     // 0: shape not served by this kernel
-    const long rpw = rowdot_bwd_rpw(rows);
-    return ((rows + rpw - 1) / rpw + 3) / 4;
+    RowPlan p{row_form(c, dtype), 0, 0};
+    if (rows <= 0 || c <= 0 || !p.form.ok) return p;     // parts 0: shape not served by this kernel
+    p.per_wave = rowdot_bwd_rpw(rows);
+    p.parts = rows_grid((rows + p.per_wave - 1) / p.per_wave);
+    return p;
 }
+
+extern "C" int64_t tramba_rowdot_bwd_parts(int64_t rows, int c, int dtype) { return rowdot_bwd_plan(rows, c, dtype).parts; }
 
 extern "C" int tramba_rowdot_bwd_cl(const void *x, const float *gy, const float *w, void *gx, float *part, int64_t rows,
                                     int c, int dtype, void *stream)
 {
     TRAMBA_CHECK(x && gy && w && gx && part, "rowdot_bwd_cl: null tensor");
-    TRAMBA_CHECK(tramba_rowdot_bwd_parts(rows, c, dtype) > 0, "rowdot_bwd_cl: C=%d is not served (rows of at most 64 x 16 bytes)", c);
+    const RowPlan plan = rowdot_bwd_plan(rows, c, dtype);
+    TRAMBA_CHECK(plan.parts > 0, "rowdot_bwd_cl: C=%d is not served (rows of at most 64 x 16 bytes)", c);
     TRAMBA_CHECK(aligned16(x) && aligned16(gx) && aligned16(w), "rowdot_bwd_cl: tensors must be 16-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    const long rpw = rowdot_bwd_rpw(rows);
-    const long waves = (rows + rpw - 1) / rpw;
-    dim3 grid((unsigned)((waves + 3) / 4)), block(256);
-    const int vm = dtype == TRAMBA_F32 ? 4 : 8;
-    int lpr = 1;
-    while (lpr < c / vm) lpr <<= 1;
-#define GOB_(T, V_, L_)                                                                                                   \
-    hipLaunchKernelGGL((rowdot_bwd_kernel<T, V_, L_>), grid, block, 0, s, (const T *)x, gy, w, (T *)gx, part, (long)rows, c, \
-                       (int)rpw)
-#define BYL_(T, V_)                    \
-    switch (lpr) {                     \
-    case 1: GOB_(T, V_, 1); break;     \
-    case 2: GOB_(T, V_, 2); break;     \
-    case 4: GOB_(T, V_, 4); break;     \
-    case 8: GOB_(T, V_, 8); break;     \
-    case 16: GOB_(T, V_, 16); break;   \
-    case 32: GOB_(T, V_, 32); break;   \
-    default: GOB_(T, V_, 64); break;   \
-    }
-    if (dtype == TRAMBA_F32) { BYL_(float, 4) }
-    else if (dtype == TRAMBA_BF16) { BYL_(__hip_bfloat16, 8) }
-    else { BYL_(__half, 8) }
-#undef BYL_
-#undef GOB_
+    const dim3 grid((unsigned)plan.parts), block(256);
+    TRAMBA_DISPATCH_DTYPE(dtype, T, with_lpr(plan.form.lpr, [&](auto L) {
+        hipLaunchKernelGGL((rowdot_bwd_kernel<T, kRowVec<T>, decltype(L)::value>), grid, block, 0, s, (const T *)x, gy, w,
+                           (T *)gx, part, (long)rows, c, (int)plan.per_wave);
+    }));
     TRAMBA_LAUNCH_CHECK();
     return TRAMBA_OK;
 }

@@ -771,13 +771,20 @@ def layernorm_bwd_cl(x, dy, w, eps=1e-5, defer=False):
     fp32 leaves as they are (see _SumQueue); anything that reads or casts them must pass False."""
     _dev(x, dy, w)
     c = x.shape[-1]
-    rows = x.numel() // c
+    dx, _, dw, db = _layernorm_bwd("layernorm_bwd_cl", x, dy, w, eps, x.numel() // c, c, defer)
+    return dx, dw, db
+
+
+def _layernorm_bwd(what, x, dy, w, eps, rows, c, defer, gres=None, mask=None, want_masked=False, p=1, h=1, wd=1):
+    """the three LayerNorm backwards differ in which operands exist: (dx, dxm or None, dw, db) of
+    tramba_layernorm_bwd_any_cl, the partial table sized by the library's own query"""
     dx = torch.empty_like(x)
+    dxm = torch.empty_like(x) if want_masked else None
     part = torch.empty((lib().tramba_layernorm_bwd_parts(rows, c, dt(x)), 2, c), dtype=torch.float32, device=x.device)
-    _check(lib().tramba_layernorm_bwd_cl(_ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(part), rows, c, eps, dt(x), _stream()),
-           "layernorm_bwd_cl")
+    _check(lib().tramba_layernorm_bwd_any_cl(_ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(part), _ptr(gres), _ptr(mask),
+                                             rows // x.shape[0], _ptr(dxm), rows, c, eps, p, h, wd, dt(x), _stream()), what)
     s = slab_sum(part, defer=defer)
-    return dx, s[0], s[1]
+    return dx, dxm, s[0], s[1]
 
 
 def add_layernorm_cl(x, y, mask, w, b, eps=1e-5, act=ACT_NONE, dual=False, gate=None):
@@ -796,13 +803,10 @@ def add_layernorm_cl(x, y, mask, w, b, eps=1e-5, act=ACT_NONE, dual=False, gate=
     xsum = torch.empty_like(x) if y is not None else None
     n = torch.empty_like(x)
     na = torch.empty_like(x) if dual else None
-    if gate is not None:
-        _check(lib().tramba_add_layernorm_gate_cl(_ptr(x), _ptr(y), _ptr(mask), rows // x.shape[0], _ptr(w), _ptr(b),
-                                                  _ptr(gate), _ptr(xsum), _ptr(n), _ptr(na), rows, c, eps, act, dt(x),
-                                                  _stream()), "add_layernorm_cl")
-        return xsum, n, na
-    _check(lib().tramba_add_layernorm_cl(_ptr(x), _ptr(y), _ptr(mask), rows // x.shape[0], _ptr(w), _ptr(b), _ptr(xsum),
-                                         _ptr(n), _ptr(na), rows, c, eps, act, dt(x), _stream()), "add_layernorm_cl")
+    head = (_ptr(x), _ptr(y), _ptr(mask), rows // x.shape[0], _ptr(w), _ptr(b))
+    tail = (_ptr(xsum), _ptr(n), _ptr(na), rows, c, eps, act, dt(x), _stream())
+    _check(lib().tramba_add_layernorm_gate_cl(*head, _ptr(gate), *tail) if gate is not None
+           else lib().tramba_add_layernorm_cl(*head, *tail), "add_layernorm_cl")
     return xsum, n, na
 
 
@@ -813,14 +817,7 @@ def layernorm_bwd_res_cl(x, dy, w, eps=1e-5, gres=None, mask=None, want_masked=F
     rows = x.numel() // c
     if gres is not None and (gres.shape != x.shape or gres.dtype != x.dtype):
         raise TrambaHipError("layernorm_bwd_res_cl: gres must match x")
-    dx = torch.empty_like(x)
-    dxm = torch.empty_like(x) if want_masked else None
-    part = torch.empty((lib().tramba_layernorm_bwd_parts(rows, c, dt(x)), 2, c), dtype=torch.float32, device=x.device)
-    _check(lib().tramba_layernorm_bwd_res_cl(_ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(part), _ptr(gres), _ptr(mask),
-                                             rows // x.shape[0], _ptr(dxm), rows, c, eps, dt(x), _stream()),
-           "layernorm_bwd_res_cl")
-    s = slab_sum(part, defer=defer)
-    return dx, dxm, s[0], s[1]
+    return _layernorm_bwd("layernorm_bwd_res_cl", x, dy, w, eps, rows, c, defer, gres, mask, want_masked)
 
 
 def shuffle_norm_cl(x, w, b, p, eps=1e-5):
@@ -842,12 +839,10 @@ def shuffle_norm_bwd_cl(x, dy, w, p, eps=1e-5, defer=False):
     if dy.shape != (bb, h * p, wd * p, c) or dy.dtype != x.dtype:
         raise TrambaHipError("shuffle_norm_bwd_cl: dy does not match the shuffled map")
     rows = bb * h * wd * p * p
-    dx = torch.empty_like(x)
-    part = torch.empty((lib().tramba_layernorm_bwd_parts(rows, c, dt(x)), 2, c), dtype=torch.float32, device=x.device)
-    _check(lib().tramba_shuffle_norm_bwd_cl(_ptr(x), _ptr(dy), _ptr(w), _ptr(dx), _ptr(part), bb, h, wd, c, p, eps, dt(x),
-                                            _stream()), "shuffle_norm_bwd_cl")
-    s = slab_sum(part, defer=defer)
-    return dx, s[0], s[1]
+    if p < 1 or rows <= 0 or rows >= 2147483647:      # (the checks of the C entry of this name, which the general one lacks)
+        raise TrambaHipError("shuffle_norm_bwd_cl: empty shape, or too many rows for the 32-bit row index of this build")
+    dx, _, dw, db = _layernorm_bwd("shuffle_norm_bwd_cl", x, dy, w, eps, rows, c, defer, p=p, h=h, wd=wd)
+    return dx, dw, db
 
 
 def shuffle_norm_head_cl(x, w, b, head_w, head_b: float, p, eps=1e-5):
